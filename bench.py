@@ -8,11 +8,18 @@ For N > 1 (launched by torch.distributed.run, one rank per GPU) every rank runs 
 pairs are independent) and the flows are reassembled with one RCCL all-gather per step,
 issued asynchronously so it overlaps the next step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (milliseconds per timed step) and
   "roofline":     the level-3 warp+correlation kernel, algorithmic bytes (24 707 072 B/pair at
-                  1024^2) / its launch duration measured live with hipEvents around that launch in every timed step;
+                  1024^2) / its launch duration measured live with hipEvents around that launch in every timed step.
+A plain run does nothing else: set up, warm up, time --steps steps, write --dump-outputs, print the line.
+--full adds what takes runs of its own (each can still be left out with --lean / --no-arithmetic / --no-cpu-baseline):
+  "roofline_level1", "roofline_batch8", "roofline_conv": the level-1 launch in a few extra forwards, the batch-8 level-3
+                  launches and the level-1 128->128 convolution standalone;
+  "arithmetic":   the same forward under every fp32-class conv arithmetic, side by side;
   "cpu_baseline": the oracle (torch CPU convs + CPU correlation) timed on this box's host cores on ONE pair
-                  of the same workload (reported baseline only).
+                  of the same workload (reported baseline only), with the GPU flow's parity against it.
+--dump-outputs DIR writes the flows of the last timed step (what a caller of the timed path receives; all ranks' pairs
+when N > 1) as DIR/flow.npy in float32.  Inputs and weights are seeded, so the same arguments give the same inputs.
 """
 from __future__ import annotations
 
@@ -38,9 +45,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=1, help="pairs per step per GPU (default 1 = BASELINE configs[1])")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--model", default="piv", choices=["piv", "hui"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-arithmetic", action="store_true", help="skip the side-by-side timing of the three fp32 conv arithmetics")
-    ap.add_argument("--lean", action="store_true", help="only the timed forwards (no level-1 / batch-8 / conv roofline extras): for profiler runs")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the level-1 / batch-8 / conv rooflines, "
+                                                        "the side-by-side conv arithmetics and the CPU baseline with its parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the flows of the last timed step as DIR/flow.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-arithmetic", action="store_true", help="with --full: skip the side-by-side timing of the fp32 conv arithmetics")
+    ap.add_argument("--lean", action="store_true", help="with --full: no level-1 / batch-8 / conv roofline extras")
     ap.add_argument("--cpu-runs", type=int, default=3, help="timed warm runs of the CPU baseline (median reported)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp32_wino_mfma32", "fp32_direct", "fp32_split", "fp32_split3", "fp16"],
                     help="how the large convolutions multiply: fp32 (the library's default and the headline: the fp32 matrix instruction, "
@@ -49,7 +59,23 @@ def parse():
                          "matrix cores, exact to 2^-32); fp32_split3 (two pieces, 22-23 operand bits) and fp16 (BASELINE config #5) are "
                          "narrower than fp32 and reported under their own metric names, never as the headline")
     ap.add_argument("--profile-level", type=int, default=3, help="level whose warp+correlation launch is event-timed")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(dirname, arrays, budget=64 << 20):
+    """--dump-outputs: every array as DIR/<name>.npy in float32.  One larger than its share of `budget` bytes is written as a fixed
+    sample instead (DIR/<name>_sample.npy: the elements at sorted flat indices drawn with seed 0), so the same run gives the same file."""
+    os.makedirs(dirname, exist_ok=True)
+    share = budget // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.nbytes > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, share // 4))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def l3_algorithmic_bytes(B, H, W, L, C, stride):
@@ -497,6 +523,8 @@ def main():
     k_ms, k_empty_ms, k_n = net.profile_read() if L else (0.0, 0.0, 0)
     if L:
         net.profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"flow": gathered[(args.steps - 1) & 1] if use_dist else flow})
     devname = torch.cuda.get_device_name(dev)
     per_rank = [{"rank": 0, "pairs_per_s": round(args.steps * B / t_own, 3), "gather_wait_ms_per_step": 0.0, "device_index": local, "device_name": devname}]
     backend_world = 1
@@ -514,7 +542,7 @@ def main():
                      "device_index": who[r][0], "device_name": who[r][1]} for r, v in enumerate(allr)]
     # level-1 launch of the same kernel family (395 MB: beyond the 256 MiB Infinity Cache), timed the same way in a few extra steps
     l1 = None
-    if L == 3 and world == 1 and args.model == "piv" and args.size == 1024 and net.lowest_level == 1 and not args.lean:
+    if args.full and L == 3 and world == 1 and args.model == "piv" and args.size == 1024 and net.lowest_level == 1 and not args.lean:
         net.profile_enable(1)
         for i in range(5):
             step(i)
@@ -592,13 +620,13 @@ def main():
                                       "kernel": "warp_corr_v6_kernel<true, 2> (level 1: C=64, stride 2; 395 MB per launch, beyond the Infinity Cache; runs of 16 tiles)",
                                       "algorithmic_bytes_per_launch": alg1, "avg_launch_us": round(t1 * 1e6, 2), "launches_timed": l1[2],
                                       "rocprofv3_kernel_trace_avg_us": counter_file_value("r06_pmc_l1_warp_corr.json", "rocprofv3_kernel_trace_avg_us") if B == 1 else None}
-        if world == 1 and args.model == "piv" and S == 1024 and not args.lean:
+        if args.full and world == 1 and args.model == "piv" and S == 1024 and not args.lean:
             out["roofline_batch8"] = l3_throughput_regime(dev)
-        if world == 1 and args.precision != "fp16" and args.model == "piv" and S == 1024 and not args.lean:
+        if args.full and world == 1 and args.precision != "fp16" and args.model == "piv" and S == 1024 and not args.lean:
             out["roofline_conv"] = conv_roofline(dev, args.precision)
-        if world == 1 and args.precision != "fp16" and not args.no_arithmetic:
+        if args.full and world == 1 and args.precision != "fp16" and not args.no_arithmetic:
             out["arithmetic"] = arithmetic_modes(net, i1, i2, min(args.steps, 10), dev)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             ref, cb = cpu_baseline(args.model, S, wts, i1c, i2c, runs=args.cpu_runs)
             out["cpu_baseline"] = cb
             err = float((flow[:1].cpu() - ref).abs().max())

@@ -212,6 +212,28 @@ def test_bench_py_two_rank_rehearsal(dev):
     assert abs(j["value"] - 2 * 3 / (j["ms_per_step"] * 3e-3)) / j["value"] < 0.01                  # value = all ranks' pairs / max time
 
 
+def test_bench_py_dumps_what_the_timed_path_computed(dev, tmp_path):
+    """A plain `bench.py --dump-outputs DIR` run: one JSON line with the headline fields and none of the --full extras, and
+    DIR/flow.npy holds the last timed step's flows bit for bit -- the same forward run here on the same seeded inputs."""
+    S = 256
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--size", str(S),
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    j = lines[0]
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["unit"] == "image-pairs/s" and j["higher_is_better"] is True
+    assert j["cpu_baseline"] is None and not {"arithmetic", "roofline_batch8", "roofline_conv", "roofline_level1"} & set(j)
+    assert os.listdir(tmp_path / "out") == ["flow.npy"]
+    got = np.load(tmp_path / "out" / "flow.npy")
+    a, b = synth.particle_batch(1, S, S, seed=1234)
+    net = pivlfn.Network(model="piv", params=synth.generate_weights("piv", 0)).to(dev).eval()
+    want = net(torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)).cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == (1, 2, S, S) and np.array_equal(got, want)
+    assert np.abs(want).max() > 0.5
+
+
 def test_config3_one_ranks_share_at_length(dev):
     """A whole per-rank share of BASELINE configs[3] on one GPU: 1 251 frames of 1024 x 1024 (1 250 pairs, 157 chunks of 8) through
     run_sequence with a sink that drops the flows -- the pinned ring, the producer thread and the sink thread over a long run: every

@@ -87,8 +87,11 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 def test_reference_demo_flo_fixture():
     """tests/golden/DNS_turbulence_out.flo is the reference's own network output for its demo pair
-    (/root/reference/images/demo/, a data file, committed as a fixture): the reader must take a real .flo as it is."""
+    (images/demo/ of the reference, a data file, committed as a fixture and pinned here by its sha256): the reader must take a
+    real .flo as it is."""
+    import hashlib
     p = os.path.join(GOLDEN, "DNS_turbulence_out.flo")
+    assert hashlib.sha256(open(p, "rb").read()).hexdigest() == "5f017a8fc536fba28c756188a8fa7041b61b4750d5703b52a1881e3675d03c41"
     f = read_flow(p)
     assert f.shape == (256, 256, 2) and f.dtype == np.float32
     assert abs(float(f[..., 0].min()) - (-2.5557063)) < 1e-6 and abs(float(f[..., 0].max()) - 2.216687) < 1e-6
@@ -96,9 +99,6 @@ def test_reference_demo_flo_fixture():
     with open(p, "rb") as stream:                       # an open binary stream is accepted too (and closed)
         g = read_flow(stream)
     assert stream.closed and np.array_equal(f, g)
-    ref = "/root/reference/images/demo/DNS_turbulence_out.flo"
-    if os.path.exists(ref):
-        assert open(ref, "rb").read() == open(p, "rb").read()
 
 
 def test_flo_truncated_payload_is_an_error(tmp_path):

@@ -43,7 +43,7 @@ Sources: commit {commit}.  `--lean` leaves out the roofline_conv / arithmetic le
 ```
 {tl}```
 
-## The un-profiled bench line of the same build and box (python3 bench.py)
+## The un-profiled bench line of the same build and box (python3 bench.py --full)
 
 ```
 {bench}

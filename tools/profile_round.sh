@@ -48,5 +48,5 @@ python3 tools/bench_s2.py > $R/${RN}_bench_s2.log 2>&1 || true
 python3 tools/bench_wino.py --levels 1 --layers 128x128,128x64,64x64,32x32 --rounds 3 > $R/${RN}_bench_wino_f4.log 2>&1 || true
 python3 tools/bench_wino.py --masks 7680,7936 --levels 1,2 --rounds 3 > $R/${RN}_bench_wino_ws.log 2>&1 || true
 # 6. the bench line itself (un-profiled), with the CPU baseline and the arithmetic table
-python3 bench.py > $R/bench_default.json 2> $R/bench_default.err
+python3 bench.py --full > $R/bench_default.json 2> $R/bench_default.err
 echo "all done"
