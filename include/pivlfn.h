@@ -88,6 +88,28 @@ int pivlfn_warp_corr_nhwc_timed(const float *first, const float *second, const f
 int pivlfn_resize_bilinear(const float *in, float *out, int B, int C, int H, int W, int Ho, int Wo,
                            const float *mul, void *stream);
 
+/* ---- stereoscopic 2D3C reconstruction: stereo_run.py:153-163 (_stereo_cal) with stereo/dewarp.py:255-270 (nl_trans) per
+ * camera, then stereo/vel3d.py:4-24 (willert), fused with estimate()'s output resize.  Added without an ABI bump (additive).
+ * flow: NCHW [2B,2,h,w], batch entry 2b = left camera, 2b+1 = right camera of step b (the raw network output of an interleaved
+ * batch, or flows already at H x W);  out: [B,H,W,3] fp32, the band order of a 3-band .flo (U, V, W interleaved).
+ * When (h,w) != (H,W) each camera's u, v is resampled exactly as pivlfn_resize_bilinear does and multiplied by mul[0] (u) /
+ * mul[1] (v) (host pointer to 2 floats, NULL = 1): the per-camera values equal estimate(..., tensor=True) bit for bit.  When
+ * (h,w) == (H,W) the input is read as is and mul is not used (estimate() skips its identity resize).
+ * coeff: host pointer to 48 floats, the 24 coefficients A of the left camera then the right one, rounded to fp32.
+ * scale: host pointer to 2 floats (calib, fps), or NULL for no m/s scaling.
+ * tangents: host pointer to 4 doubles tan(theta_L), tan(theta_R), tan(beta_L), tan(beta_R) (radians, left angles negated).
+ * Arithmetic contract, every operation rounded on its own (no fma), correctly rounded divisions; x = u, y = v of one camera:
+ *   stage 1, fp32:  P(a..f) = ((((a*x + b*y) + c) + d*(x*x)) + e*(y*y)) + (f*x)*y
+ *                   x' = P(A0..A5) / P(A6..A11),  y' = P(A12..A17) / P(A18..A23);  with scale: x' = (x' * calib) * fps, same for y'
+ *   stage 2, fp64:  dT = tL - tR;  dB = bR - bL;  du = (uR' - uL') in fp32
+ *                   U = ((double)uR' * tL - (double)uL' * tR) / dT
+ *                   V = (double)((vL' + vR') / 2 in fp32) + (((double)du * dB) / dT) / 2
+ *                   W = (double)du / dT;     out = (float)U, (float)V, (float)W
+ * which is what the reference computes under NumPy >= 2 promotion.  A zero denominator in stage 1 gives inf / NaN where numpy
+ * does.  Errors (PIVLFN_ERR_ARG): null flow / out / coeff / tangents, a non-positive size, a non-finite tangent, dT == 0. */
+int pivlfn_stereo_2d3c(const float *flow, float *out, int B, int h, int w, int H, int W, const float *mul,
+                       const float *coeff, const float *scale, const double *tangents, void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

@@ -129,6 +129,12 @@ int pivlfn_resize_bilinear(const float *in, float *out, int B, int C, int H, int
                               (hipStream_t)stream);
 }
 
+int pivlfn_stereo_2d3c(const float *flow, float *out, int B, int h, int w, int H, int W, const float *mul,
+                       const float *coeff, const float *scale, const double *tangents, void *stream)
+{
+    return launch_stereo_2d3c(flow, out, B, h, w, H, W, mul, coeff, scale, tangents, (hipStream_t)stream);
+}
+
 int pivlfn_create(const pivlfn_tensor *tensors, int n_tensors, float starting_scale, int lowest_level,
                   const float rgb_mean[6], pivlfn_net **out)
 {

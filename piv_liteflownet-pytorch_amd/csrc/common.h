@@ -244,6 +244,10 @@ int launch_reg_tail(const float *dist, int dstride, const float *flow4, const fl
                     float bx, float by, int k, float *out4, float *out_nchw, float out_scale,
                     int B, int H, int W, hipStream_t st);
 int launch_flow4_to_nchw(const float *flow4, float *out, int B, int H, int W, hipStream_t st);
+
+// ---- stereo 2D3C reconstruction (stereo.hip): [2B,2,h,w] NCHW interleaved cameras -> [B,H,W,3] ------------------------
+int launch_stereo_2d3c(const float *flow, float *out, int B, int h, int w, int H, int W, const float *mul,
+                       const float *coeff, const float *scale, const double *tan4, hipStream_t st);
 int flow_mean_partials(int HW);
 
 }  // namespace pivlfn

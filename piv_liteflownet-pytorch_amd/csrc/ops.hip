@@ -2,6 +2,7 @@
 // Every kernel moves whole 16-byte lanes per thread and fuses what the reference runs as separate torch ops.
 // Citations are into /root/reference/src/models.py.
 #include "common.h"
+#include "bilinear.h"
 
 namespace pivlfn {
 
@@ -11,21 +12,6 @@ static inline int grid_for(size_t n, int cap = 16384)
 {
     size_t g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
-}
-
-// ---- per-axis source index / weights of torch's bilinear, align_corners=False -----------------------------
-struct Lin { int i0, i1; float w0, w1; };
-__device__ __forceinline__ Lin lin_src(int d, float scale, int n)
-{
-    float src = scale * ((float)d + 0.5f) - 0.5f;
-    src = src < 0.f ? 0.f : src;
-    Lin l;
-    l.i0 = (int)src;
-    if (l.i0 > n - 1) l.i0 = n - 1;
-    l.i1 = l.i0 + (l.i0 < n - 1 ? 1 : 0);
-    l.w1 = src - (float)l.i0;
-    l.w0 = 1.f - l.w1;
-    return l;
 }
 
 // ---- input: mean subtraction (:321-323) + NCHW -> [2B,H,W,4] (img1 batch then img2 batch) -------------------
@@ -98,10 +84,7 @@ __global__ __launch_bounds__(256) void resize_nchw_kernel(const float *__restric
         const int oy = (int)(r % Ho);
         const int n = (int)(r / Ho);
         const Lin ly = lin_src(oy, sy, H), lx = lin_src(ox, sx, W);
-        const float *base = in + (size_t)n * H * W;
-        const float a = base[(size_t)ly.i0 * W + lx.i0], b = base[(size_t)ly.i0 * W + lx.i1];
-        const float c = base[(size_t)ly.i1 * W + lx.i0], d = base[(size_t)ly.i1 * W + lx.i1];
-        float v = ly.w0 * (lx.w0 * a + lx.w1 * b) + ly.w1 * (lx.w0 * c + lx.w1 * d);
+        float v = bilinear_at(in + (size_t)n * H * W, W, ly, lx);
         if (use_mul) v *= (n & 1) ? m1 : m0;
         out[i] = v;
     }

@@ -34,7 +34,8 @@ def _resize(x: torch.Tensor, Ho: int, Wo: int, mul=None) -> torch.Tensor:
     return out
 
 
-def estimate(net: torch.nn.Module, img1: torch.Tensor, img2: torch.Tensor, tensor: bool = False):
+def _adapted_forward(net: torch.nn.Module, img1: torch.Tensor, img2: torch.Tensor):
+    """estimate()'s input adaptation and forward: (raw flow, H, W, sw, sh); the output resize is the caller's."""
     # Ensure that both the first and second images have the same dimension (inference.py:32-33)
     assert (img1.size(2) == img2.size(2))
     assert (img1.size(3) == img2.size(3))
@@ -53,6 +54,11 @@ def estimate(net: torch.nn.Module, img1: torch.Tensor, img2: torch.Tensor, tenso
         if net.training:                # the reference calls net.eval() unconditionally (inference.py:52); it walks every submodule
             net.eval()
         raw = net(a, b)
+    return raw, H, W, sw, sh
+
+
+def estimate(net: torch.nn.Module, img1: torch.Tensor, img2: torch.Tensor, tensor: bool = False):
+    raw, H, W, sw, sh = _adapted_forward(net, img1, img2)
     if raw.shape[2:] == (H, W) and sw == 1.0 and sh == 1.0:
         flow = raw                      # same-size bilinear resize is the identity; scale factors are 1
     else:

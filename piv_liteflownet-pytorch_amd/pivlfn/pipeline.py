@@ -47,13 +47,16 @@ def u8_to_input(x: torch.Tensor) -> torch.Tensor:
 class PairLoader:
     """Iterates `(names, img1_u8, img2_u8)` batches ([n,H,W,3] uint8 torch tensors, pinned when `pin`), in dataset order,
     over pairs [lo, hi) of a `Run`-like dataset (anything with `.image_list[i] = [path1, path2]` and `.name_list[i]`).
-    A batch never mixes image sizes.  Decoding runs on a background thread, `depth` batches ahead."""
+    A batch never mixes image sizes.  Decoding runs on a background thread, `depth` batches ahead.
+    `share`: how many following pairs may reuse a frame of the current one (1 for a frame sequence; 2 for the interleaved
+    left / right sequences of pivlfn.stereo, where frame k+1 of a camera comes back two pairs later)."""
 
     def __init__(self, dataset, lo: int, hi: int, batch: int, depth: int = 2, pin: bool = False,
-                 reader: Callable[[str], np.ndarray] = read_image_u8, workers: int = 4):
-        if batch < 1 or depth < 1 or workers < 1:
-            raise ValueError("PairLoader: batch, depth and workers must be >= 1")
+                 reader: Callable[[str], np.ndarray] = read_image_u8, workers: int = 4, share: int = 1):
+        if batch < 1 or depth < 1 or workers < 1 or share < 1:
+            raise ValueError("PairLoader: batch, depth, workers and share must be >= 1")
         self.ds, self.lo, self.hi, self.batch, self.pin, self.reader = dataset, lo, hi, batch, pin, reader
+        self.share = share
         self.workers = workers                             # decode threads (PIL releases the GIL while it decodes)
         self.last_slot = None
         self.decoded = 0                                   # frames actually decoded (tests: sequence mode decodes n+1, not 2n)
@@ -122,8 +125,8 @@ class PairLoader:
                         ahead += 1
                     p1, p2 = self.ds.image_list[i]
                     a, b = pending[p1].result(), pending[p2].result()
-                    # a frame can only be shared with the following pair (src/datasets.py:456-463): drop everything older
-                    nxt = set(self.ds.image_list[i + 1]) if i + 1 < self.hi else set()
+                    # a frame can only be shared with the following `share` pairs (src/datasets.py:456-463): drop everything older
+                    nxt = {p for j in range(i + 1, min(self.hi, i + 1 + self.share)) for p in self.ds.image_list[j]}
                     for path in (p1, p2):
                         if path not in nxt:
                             pending.pop(path, None)
@@ -166,13 +169,18 @@ class PairLoader:
 
 def stream_pairs(net, loader: PairLoader, device: torch.device, sink: Callable[..., None],
                  estimate_fn: Optional[Callable] = None, in_flight: int = 3,
-                 mods: Optional[Sequence[Tuple[float, float]]] = None) -> int:
+                 mods: Optional[Sequence[Tuple[float, float]]] = None, group: int = 1) -> int:
     """Drive `estimate` over a PairLoader.  `sink(flow_hw2, name)` is called once per pair, in order; the numpy view it gets
     owns a reference to its (pinned) batch buffer, so an asynchronous writer may keep it.  On a GPU the uploads and
     downloads run on a copy stream and overlap with compute; on the CPU (tests of the host logic, with a stand-in
     `estimate_fn`) the same code runs synchronously.
     `mods`: (brightness, contrast) factors of run.py -b/-c; every uploaded batch is then estimated once per entry, with both
-    frames modified on the device (pivlfn.imagemod), and the sink is called as `sink(flow_hw2, name, (brightness, contrast))`."""
+    frames modified on the device (pivlfn.imagemod), and the sink is called as `sink(flow_hw2, name, (brightness, contrast))`.
+    `group`: every `group` consecutive pairs of a batch make ONE output (pivlfn.stereo: a left and a right pair).  `estimate_fn`
+    then returns the outputs already in the file layout, [n / group, H, W, C], the sink gets the name of each group's first
+    pair, and the count returned is the number of outputs."""
+    if group < 1:
+        raise ValueError("stream_pairs: group must be >= 1")
     if estimate_fn is None:
         from .inference import estimate as estimate_fn      # noqa: N813
     from .imagemod import image_mod
@@ -214,7 +222,12 @@ def stream_pairs(net, loader: PairLoader, device: torch.device, sink: Callable[.
         for mod in (mods if mods is not None else (None,)):
             am, bm = (a_dev, b_dev) if mod is None else (image_mod(a_dev, *mod), image_mod(b_dev, *mod))
             flow = estimate_fn(net, u8_to_input(am), u8_to_input(bm), tensor=True)           # [n,2,H,W]
-            out = flow.permute(0, 2, 3, 1).contiguous()                                      # [n,H,W,2], the .flo layout
+            if group == 1:
+                out = flow.permute(0, 2, 3, 1).contiguous()                                  # [n,H,W,2], the .flo layout
+            else:
+                if len(names) % group:
+                    raise ValueError(f"stream_pairs: a batch of {len(names)} pairs does not split into groups of {group}")
+                out = flow.contiguous()                                                      # [n/group,H,W,C]
             if on_gpu:
                 host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
                 copy.wait_stream(main)
@@ -223,9 +236,9 @@ def stream_pairs(net, loader: PairLoader, device: torch.device, sink: Callable[.
                     ev = torch.cuda.Event()
                     ev.record(copy)
                 out.record_stream(copy)
-                pending.append((ev, host, names, mod))
+                pending.append((ev, host, names[::group], mod))
             else:
-                pending.append((None, out, names, mod))
+                pending.append((None, out, names[::group], mod))
             drain(in_flight - 1)
     drain(0)
     return done
