@@ -230,6 +230,46 @@ int pivlfn_conv2d_nhwc_cat(const pivlfn_conv *conv, int nsrc, const float *const
 int pivlfn_conv_head_nhwc(const pivlfn_conv *conv, const float *x, const float *res4, float *out4, int B, int H, int W,
                           void *stream);
 
+/* ---- per-layer checks: the level-pipeline ops that otherwise run only inside pivlfn_forward, each on the kernel and with the
+ * weight packing pivlfn_forward uses, exported so that every kernel can be checked on its own (tests/test_gpu_net_ops.py).  Not a
+ * hot path: the two entry points that take host weights pack and upload them per call and synchronise `stream` before returning.
+ * Added without an ABI bump (additive).  Layouts are the network's channels-last ones; "flow4" is [B,H,W,4] = (u, v, 0, 0).
+ *
+ * upConv_M / upCorr_M, src/models.py:144-145, 151-152 (depthwise ConvTranspose2d k4 s2 p1, no bias).  quads = 1: the flow, 2
+ * channels on 4 lanes; quads = 14: the correlation, 49 channels on 56 lanes.  w16: host, OIHW [C,1,4,4] (C = 2 or 49).  in:
+ * [B,H,W,stride_in]; out: [B,2H,2W,stride_out], lanes 0..4*quads-1 written (padding lanes as exact zeros: the input's padding
+ * lanes must be finite), the rest untouched.  Strides are multiples of 4 and >= 4*quads; 2H <= 65535, B <= 65535. */
+int pivlfn_upconv_nhwc(const float *in, const float *w16, float *out, int B, int H, int W, int quads, int stride_in,
+                       int stride_out, void *stream);
+/* Subpixel's backwarp(feat2, flow * scale), src/models.py:214: in / out [B,H,W,C] (C % 4 == 0), flow4 [B,H,W,4]; fewer than
+ * 2^31 (pixel, channel quad) work items. */
+int pivlfn_backwarp_nhwc(const float *in, const float *flow4, float scale, float *out, int B, int H, int W, int C, void *stream);
+/* Regularization front, src/models.py:275-277: mean_out [B,2] = per-image mean of (u, v); misc4 [B,H,W,4] = (||img1 - backwarp(img2,
+ * flow * scale)||_2 over the 3 colour lanes, u - mean_u, v - mean_v, 0).  img1_4 / img2_4 [B,H,W,4]; partial_ws: device scratch
+ * of 128 * B floats.  fused = 1: pivlfn_forward's path (partial sums, the mean formed inside the reg_prep kernel); fused = 0: the
+ * one-wave mean kernel, then reg_prep reads mean_out.  Both give the same bits.  1 <= B <= 65535. */
+int pivlfn_reg_prep(const float *img1_4, const float *img2_4, const float *flow4, float scale, float *misc4, float *mean_out,
+                    float *partial_ws, int B, int H, int W, int fused, void *stream);
+/* Regularization tail, src/models.py:281-302: softmax(-dist^2) over the k*k channels, the k x k unfold of (u, v) with zero padding,
+ * moduleScaleX / Y (wx, wy: DEVICE pointers to k*k floats; bx, by their biases), divided by the softmax sum.  dist [B,H,W,dstride]
+ * (first k*k lanes used, dstride >= k*k), flow4 [B,H,W,4], k in {3, 5, 7}.  out4 [B,H,W,4] = (u', v', 0, 0) and / or out_nchw
+ * [B,2,H,W] = out_scale * (u', v'); either may be NULL, not both. */
+int pivlfn_reg_tail(const float *dist, int dstride, const float *flow4, const float *wx, const float *wy, float bx, float by,
+                    int k, float *out4, float *out_nchw, float out_scale, int B, int H, int W, void *stream);
+/* Mean subtraction and image pyramid, src/models.py:321-323, 336-343: img1 / img2 NCHW [B,3,H,W]; mean6 host, 6 floats (frame 1's
+ * RGB means, then frame 2's).  out_levels receives levels 1..levels (1..6) back to back, level L = [2B, H>>(L-1), W>>(L-1), 4]
+ * (frames 1 then frames 2, lane 3 zero), each level the bilinear (align_corners=False) resize of the one before. */
+int pivlfn_prep_pyramid(const float *img1, const float *img2, const float *mean6, float *out_levels, int B, int H, int W,
+                        int levels, void *stream);
+/* NetC.conv1 (7 x 7, 3 -> 32, LeakyReLU) with level 1's NetC_ext (1 x 1, 32 -> 64, LeakyReLU) and moduleFeat (1 x 1, 32 -> 128,
+ * LeakyReLU) on top: src/models.py:70-72, 124, 227-232.  Weights host, OIHW, with their biases.  x [N,H,W,4] (lane 3 finite);
+ * out [N,H,W,32], out_ext [N,H,W,64] for every image, out_feat [B_feat,H,W,128] for the first B_feat (1..N) images only.  Where the
+ * image has >= 512 tiles of 8 x 32 pixels, the three layers run in conv1's kernel as in pivlfn_forward and *fused = 1; below, the
+ * three layers run on their own kernels and *fused = 0 (fused may be NULL). */
+int pivlfn_conv1_fused_nhwc(const float *w1, const float *b1, const float *w_ext, const float *b_ext, const float *w_feat,
+                            const float *b_feat, const float *x, float *out, float *out_ext, float *out_feat, int N, int H, int W,
+                            int B_feat, int *fused, void *stream);
+
 /* ---- measurement hooks.  With profiling on, pivlfn_forward times the level-`level` warp+correlation launch
  * with HIP events on `stream` in two ways: start/stop events attached to the dispatch itself
  * (hipExtLaunchKernelGGL: the dispatch's own begin/end timestamps) and a plain hipEventRecord pair around it

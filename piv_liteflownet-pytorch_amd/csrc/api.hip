@@ -75,6 +75,11 @@ int conv_forward_wb(const pivlfn_conv *c, const float *x, int x_stride, float *y
                     int terms, hipStream_t st);
 int conv_forward_w(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride, int B, int H, int W, int leaky,
                    hipStream_t st, int tile);
+int upconv_forward(const float *in, const float *w, float *out, int B, int H, int W, int quads, int stride_in, int stride_out,
+                   hipStream_t st);
+int conv1_fused_forward(const float *w1, const float *b1, const float *we, const float *be, const float *wf, const float *bfe,
+                        const float *x, float *out, float *out_ext, float *out_feat, int N, int H, int W, int B_feat, int *fused,
+                        hipStream_t st);
 
 }  // namespace pivlfn
 
@@ -248,6 +253,74 @@ int pivlfn_warp_corr_nhwc_timed(const float *first, const float *second, const f
     for (auto &e : ev) if (e) (void)hipEventDestroy(e);
     if (rc == PIVLFN_OK) *us_dispatch = total * 1e3 / launches;
     return rc;
+}
+
+// ---- per-layer checks of the level-pipeline ops that run only inside pivlfn_forward (include/pivlfn.h) -------------------------
+int pivlfn_upconv_nhwc(const float *in, const float *w16, float *out, int B, int H, int W, int quads, int stride_in, int stride_out,
+                       void *stream)
+{
+    return upconv_forward(in, w16, out, B, H, W, quads, stride_in, stride_out, (hipStream_t)stream);
+}
+
+int pivlfn_backwarp_nhwc(const float *in, const float *flow4, float scale, float *out, int B, int H, int W, int C, void *stream)
+{
+    PIV_REQUIRE(in && flow4 && out, "backwarp_nhwc: null argument");
+    PIV_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "backwarp_nhwc: B=%d H=%d W=%d C=%d must be positive", B, H, W, C);
+    return launch_backwarp_nhwc(in, flow4, scale, out, B, H, W, C, (hipStream_t)stream);
+}
+
+int pivlfn_reg_prep(const float *img1_4, const float *img2_4, const float *flow4, float scale, float *misc4, float *mean_out,
+                    float *partial_ws, int B, int H, int W, int fused, void *stream)
+{
+    PIV_REQUIRE(img1_4 && img2_4 && flow4 && misc4 && mean_out && partial_ws, "reg_prep: null argument");
+    PIV_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0, "reg_prep: B=%d (1..65535) H=%d W=%d", B, H, W);
+    PIV_REQUIRE((long)H * W < (1L << 31) - 65536, "reg_prep: H=%d x W=%d pixels exceed the 32-bit index range", H, W);
+    PIV_REQUIRE(fused == 0 || fused == 1, "reg_prep: fused=%d (0 or 1)", fused);
+    const hipStream_t st = (hipStream_t)stream;
+    if (fused) {      // pivlfn_forward's path: partial sums only, every reg_prep workgroup finishes the mean itself
+        if (int rc = launch_flow_mean(flow4, partial_ws, nullptr, B, H * W, st)) return rc;
+        return launch_reg_prep(img1_4, img2_4, flow4, mean_out, partial_ws, scale, misc4, B, H, W, st);
+    }
+    if (int rc = launch_flow_mean(flow4, partial_ws, mean_out, B, H * W, st)) return rc;
+    return launch_reg_prep(img1_4, img2_4, flow4, mean_out, nullptr, scale, misc4, B, H, W, st);
+}
+
+int pivlfn_reg_tail(const float *dist, int dstride, const float *flow4, const float *wx, const float *wy, float bx, float by, int k,
+                    float *out4, float *out_nchw, float out_scale, int B, int H, int W, void *stream)
+{
+    PIV_REQUIRE(dist && flow4 && wx && wy && (out4 || out_nchw), "reg_tail: null argument (dist, flow4, wx, wy and one output needed)");
+    PIV_REQUIRE(k == 3 || k == 5 || k == 7, "reg_tail: k=%d (3, 5 or 7)", k);
+    PIV_REQUIRE(B > 0 && H > 0 && W > 0 && dstride >= k * k, "reg_tail: B=%d H=%d W=%d dstride=%d (>= %d)", B, H, W, dstride, k * k);
+    PIV_REQUIRE((long)cdiv(W, 16) * cdiv(H, 16) * B < (1L << 31), "reg_tail: %d images of %d x %d exceed the grid range", B, H, W);
+    return launch_reg_tail(dist, dstride, flow4, wx, wy, bx, by, k, out4, out_nchw, out_scale, B, H, W, (hipStream_t)stream);
+}
+
+int pivlfn_prep_pyramid(const float *img1, const float *img2, const float *mean6, float *out_levels, int B, int H, int W, int levels,
+                        void *stream)
+{
+    PIV_REQUIRE(img1 && img2 && mean6 && out_levels, "prep_pyramid: null argument");
+    PIV_REQUIRE(levels >= 1 && levels <= 6, "prep_pyramid: levels=%d (1..6)", levels);
+    PIV_REQUIRE(B > 0 && (H >> (levels - 1)) > 0 && (W >> (levels - 1)) > 0,
+                "prep_pyramid: B=%d H=%d W=%d leave no pixel at level %d", B, H, W, levels);
+    PIV_REQUIRE((long)H * W < (1L << 31), "prep_pyramid: H=%d x W=%d pixels exceed the 32-bit index range", H, W);
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = launch_prep_images(img1, img2, out_levels, B, H, W, mean6, st)) return rc;
+    float *prev = out_levels;
+    for (int L = 2; L <= levels; ++L) {
+        const int h0 = H >> (L - 2), w0 = W >> (L - 2);
+        float *next = prev + (size_t)2 * B * h0 * w0 * 4;
+        if (int rc = launch_resize_nhwc4(prev, next, 2 * B, h0, w0, H >> (L - 1), W >> (L - 1), st)) return rc;
+        prev = next;
+    }
+    return PIVLFN_OK;
+}
+
+int pivlfn_conv1_fused_nhwc(const float *w1, const float *b1, const float *w_ext, const float *b_ext, const float *w_feat,
+                            const float *b_feat, const float *x, float *out, float *out_ext, float *out_feat, int N, int H, int W,
+                            int B_feat, int *fused, void *stream)
+{
+    return conv1_fused_forward(w1, b1, w_ext, b_ext, w_feat, b_feat, x, out, out_ext, out_feat, N, H, W, B_feat, fused,
+                               (hipStream_t)stream);
 }
 
 int pivlfn_profile_enable(pivlfn_net *net, int level) { return net_profile_enable(net, level); }

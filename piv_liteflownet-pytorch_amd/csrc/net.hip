@@ -271,14 +271,38 @@ static int pack_conv(pivlfn_net *net, const TMap &m, const std::string &name, in
     return upload(net, bias, &out->bias);
 }
 
+// Depthwise ConvTranspose2d k4 weights, OIHW [C,1,4,4] -> [16 taps][cpad channels] (padding channels zero: their outputs stay exact zeros)
+void pack_dw_host(const float *w, int C, int cpad, std::vector<float> &h)
+{
+    h.assign((size_t)cpad * 16, 0.f);
+    for (int c = 0; c < C; ++c)
+        for (int t = 0; t < 16; ++t) h[(size_t)t * cpad + c] = w[(size_t)c * 16 + t];
+}
+
 static int pack_dw(pivlfn_net *net, const TMap &m, const std::string &name, int C, int cpad, float **dev)
 {
     const pivlfn_tensor *w = find(m, name, C, 1, 4, 4, 4);
     if (!w) return PIVLFN_ERR_WEIGHTS;
-    std::vector<float> h((size_t)cpad * 16, 0.f);      // [16 taps][cpad channels]
-    for (int c = 0; c < C; ++c)
-        for (int t = 0; t < 16; ++t) h[(size_t)t * cpad + c] = w->data[(size_t)c * 16 + t];
+    std::vector<float> h;
+    pack_dw_host(w->data, C, cpad, h);
     return upload(net, h, dev);
+}
+
+// Level 1's NetC_ext (we [64,32], be [64]) and moduleFeat (wf [128,32], bfe [128]) in the fragment order of Conv1Fuse
+static void pack_conv1_fuse(const float *we, const float *be, const float *wf, const float *bfe, std::vector<float> &w11,
+                            std::vector<float> &b11)
+{
+    w11.assign((size_t)6 * 4 * 64 * 4, 0.f);
+    b11.assign(192, 0.f);
+    for (int blk = 0; blk < 6; ++blk)
+        for (int g = 0; g < 4; ++g)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int e = 0; e < 4; ++e) {
+                    const int c = 8 * g + 4 * (lane >> 5) + e, o = 32 * (blk < 2 ? blk : blk - 2) + (lane & 31);
+                    w11[(((size_t)blk * 4 + g) * 64 + lane) * 4 + e] = blk < 2 ? we[(size_t)o * 32 + c] : wf[(size_t)o * 32 + c];
+                }
+    for (int o = 0; o < 64; ++o) b11[o] = be[o];
+    for (int o = 0; o < 128; ++o) b11[64 + o] = bfe[o];
 }
 
 // Flow-head weights for conv_head.hip: OIHW [2,32,k,k] -> [tap][channel quad][4][output] (the two outputs of a channel adjacent:
@@ -449,16 +473,8 @@ int net_create(const pivlfn_tensor *tensors, int n, float starting_scale, int lo
         const pivlfn_tensor *wf = find(m, "NetE_R." + std::to_string(1 - lowest) + ".moduleFeat.0.weight", 128, 32, 1, 1, 4);
         const pivlfn_tensor *bfe = find(m, "NetE_R." + std::to_string(1 - lowest) + ".moduleFeat.0.bias", 128, 0, 0, 0, 1);
         if (!we || !be || !wf || !bfe) { net_destroy(net); return PIVLFN_ERR_WEIGHTS; }
-        std::vector<float> w11((size_t)6 * 4 * 64 * 4), b11(192);
-        for (int blk = 0; blk < 6; ++blk)
-            for (int g = 0; g < 4; ++g)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 4; ++e) {
-                        const int c = 8 * g + 4 * (lane >> 5) + e, o = 32 * (blk < 2 ? blk : blk - 2) + (lane & 31);
-                        w11[(((size_t)blk * 4 + g) * 64 + lane) * 4 + e] = blk < 2 ? we->data[(size_t)o * 32 + c] : wf->data[(size_t)o * 32 + c];
-                    }
-        for (int o = 0; o < 64; ++o) b11[o] = be->data[o];
-        for (int o = 0; o < 128; ++o) b11[64 + o] = bfe->data[o];
+        std::vector<float> w11, b11;
+        pack_conv1_fuse(we->data, be->data, wf->data, bfe->data, w11, b11);
         TRY(upload(net, w11, &net->fuse1_w));
         TRY(upload(net, b11, &net->fuse1_b));
     }
@@ -1115,6 +1131,83 @@ int net_forward(pivlfn_net *net, const float *img1, const float *img2, float *fl
     if (touched) { PIV_CHECK_HIP(hipStreamWaitEvent(st, net->ev_join[6], 0)); side_join.pending &= ~(1u << 6); }
 #undef RUN
     return PIVLFN_OK;
+}
+
+// ---- per-layer checks of the level-pipeline ops that have no layer of their own (pivlfn_upconv_nhwc, pivlfn_conv1_fused_nhwc) -------
+// Host weights are packed by the network's own packers and uploaded per call; the call synchronises `st` before it frees them.
+int upconv_forward(const float *in, const float *w, float *out, int B, int H, int W, int quads, int stride_in, int stride_out,
+                   hipStream_t st)
+{
+    PIV_REQUIRE(in && w && out, "upconv: null argument");
+    PIV_REQUIRE(quads == 1 || quads == 14, "upconv: quads=%d (1 = flow, 2 channels; 14 = correlation, 49 channels)", quads);
+    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "upconv: B=%d H=%d W=%d must be positive", B, H, W);
+    PIV_REQUIRE(stride_in % 4 == 0 && stride_in >= 4 * quads && stride_out % 4 == 0 && stride_out >= 4 * quads,
+                "upconv: strides %d / %d must be multiples of 4 and >= %d", stride_in, stride_out, 4 * quads);
+    PIV_REQUIRE(2 * (long)H <= 65535 && B <= 65535, "upconv: %ld output rows / %d images exceed the grid range", 2 * (long)H, B);
+    PIV_REQUIRE((long)2 * (W + 1) * quads < (1L << 30) && (long)B * 2 * H < (1L << 31),
+                "upconv: B=%d H=%d W=%d exceed the kernel's 32-bit index range", B, H, W);
+    const int C = quads == 1 ? 2 : 49, cpad = 4 * quads;
+    std::vector<float> h;
+    pack_dw_host(w, C, cpad, h);
+    pivlfn_net *owner = new pivlfn_net();
+    float *dw = nullptr;
+    int rc = upload(owner, h, &dw);
+    if (!rc) rc = launch_dwconvT(in, dw, out, B, H, W, C, stride_in, stride_out, cpad, st);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) { set_error("upconv: hipStreamSynchronize failed"); rc = PIVLFN_ERR_HIP; }
+    net_destroy(owner);
+    return rc;
+}
+
+int conv1_fused_forward(const float *w1, const float *b1, const float *we, const float *be, const float *wf, const float *bfe,
+                        const float *x, float *out, float *out_ext, float *out_feat, int N, int H, int W, int B_feat, int *fused,
+                        hipStream_t st)
+{
+    PIV_REQUIRE(w1 && b1 && we && be && wf && bfe && x && out && out_ext && out_feat, "conv1_fused: null argument");
+    PIV_REQUIRE(N > 0 && H > 0 && W > 0 && B_feat >= 1 && B_feat <= N, "conv1_fused: N=%d H=%d W=%d B_feat=%d (1 <= B_feat <= N)", N, H, W, B_feat);
+    PIV_REQUIRE((long)N * H < (1L << 31) && (long)H * W < (1L << 31), "conv1_fused: N=%d H=%d W=%d exceed the 32-bit index range", N, H, W);
+    if (fused) *fused = 0;
+    pivlfn_tensor t[6];
+    const char *names[6] = {"c1.weight", "c1.bias", "ext.weight", "ext.bias", "feat.weight", "feat.bias"};
+    const float *data[6] = {w1, b1, we, be, wf, bfe};
+    const int shapes[6][5] = {{4, 32, 3, 7, 7}, {1, 32, 0, 0, 0}, {4, 64, 32, 1, 1}, {1, 64, 0, 0, 0}, {4, 128, 32, 1, 1}, {1, 128, 0, 0, 0}};
+    TMap m;
+    for (int i = 0; i < 6; ++i) {
+        t[i].name = names[i]; t[i].data = data[i]; t[i].ndim = shapes[i][0];
+        for (int d = 0; d < 4; ++d) t[i].shape[d] = shapes[i][d + 1];
+        m[names[i]] = &t[i];
+    }
+    pivlfn_net *owner = new pivlfn_net();
+    ConvW c1, ext, feat;
+    std::vector<float> w11, b11;
+    pack_conv1_fuse(we, be, wf, bfe, w11, b11);
+    float *dw11 = nullptr, *db11 = nullptr;
+    int rc = pack_conv(owner, m, "c1", 32, 3, 7, 7, {{3, 4}}, &c1);
+    if (!rc) rc = pack_conv(owner, m, "ext", 64, 32, 1, 1, {{32, 32}}, &ext);
+    if (!rc) rc = pack_conv(owner, m, "feat", 128, 32, 1, 1, {{32, 32}}, &feat);
+    if (!rc) rc = upload(owner, w11, &dw11);
+    if (!rc) rc = upload(owner, b11, &db11);
+    if (!rc) {      // net_forward's level-1 path in the fp32 modes, on one stream and without split-K
+        t_precision = 0; t_no_b3 = false; t_scratch = nullptr; t_side = nullptr;
+        ConvParams p1;
+        memset(&p1, 0, sizeof(p1));
+        p1.seg[0] = ConvSeg{x, 4, 4}; p1.nseg = 1;
+        p1.wpk = c1.wpk; p1.bias = c1.bias; p1.out = out; p1.out_stride = 32; p1.cout_store = 32; p1.cout_pad = c1.cout_pad;
+        p1.B = N; p1.H = H; p1.W = W; p1.Ho = H; p1.Wo = W;
+        p1.KH = 7; p1.KW = 7; p1.S = 1; p1.padY = 3; p1.padX = 3;
+        p1.nchunk = c1.nchunk; p1.tail = c1.tail; p1.lrelu = 1; p1.cin_real = c1.cin;
+        const Conv1Fuse f1{dw11, db11, out_ext, out_feat, B_feat};
+        const int rc1 = launch_conv1_fused(p1, f1, st);
+        if (rc1 > 0) rc = rc1;
+        else if (rc1 == 0) { if (fused) *fused = 1; }
+        else {
+            rc = conv(c1, {{x, 4, 4}}, out, 32, 32, nullptr, 0, 1, N, H, W, 1, 3, 3, st);
+            if (!rc) rc = conv(feat, {{out, 32, 32}}, out_feat, 128, 128, nullptr, 0, 1, B_feat, H, W, 1, 0, 0, st);
+            if (!rc) rc = conv(ext, {{out, 32, 32}}, out_ext, 64, 64, nullptr, 0, 1, N, H, W, 1, 0, 0, st);
+        }
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) { set_error("conv1_fused: hipStreamSynchronize failed"); rc = PIVLFN_ERR_HIP; }
+    net_destroy(owner);
+    return rc;
 }
 
 }  // namespace pivlfn

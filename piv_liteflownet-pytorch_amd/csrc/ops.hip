@@ -306,7 +306,8 @@ __global__ __launch_bounds__(256) void flow_mean_stage1(const float *__restrict_
 
 // Second stage of the mean: the MEAN_BLOCKS partial sums of image b, tree over one wave's lanes, / HW.  Every workgroup of
 // reg_prep_kernel runs it for itself (64 loads and 6 shuffles: cheaper than the launch a separate one-wave kernel costs in the
-// dependent chain of a level); the one-wave kernel stays for the stand-alone entry point.  Same tree, same bits.
+// dependent chain of a level); the one-wave kernel is pivlfn_reg_prep's fused = 0 path.  Same tree, same bits
+// (tests/test_gpu_net_ops.py compares the two paths with torch.equal).
 __device__ __forceinline__ float2 mean_from_partials(const float *__restrict__ partial, int b, int HW, int lane)
 {
     float2 v = make_float2(partial[((size_t)b * MEAN_BLOCKS + lane) * 2], partial[((size_t)b * MEAN_BLOCKS + lane) * 2 + 1]);

@@ -46,3 +46,66 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert lib.pivlfn_workspace_bytes(None, 1, 64, 64) == 0
     with pytest.raises(ValueError):
         _lib.check(lib.pivlfn_backwarp(None, None, None, 1, 1, 1, 1, None), "backwarp")
+
+
+NEW_OPS = ("pivlfn_upconv_nhwc", "pivlfn_backwarp_nhwc", "pivlfn_reg_prep", "pivlfn_reg_tail", "pivlfn_prep_pyramid",
+           "pivlfn_conv1_fused_nhwc")
+
+
+def test_per_layer_entry_points_are_declared():
+    names = _declared()
+    for must in NEW_OPS:
+        assert must in names
+
+
+def test_per_layer_entry_points_reject_bad_arguments_without_a_gpu():
+    """Null pointers and shapes the kernels do not cover are refused on the host with PIVLFN_ERR_ARG and a message naming the
+    problem, before anything is launched or allocated (a launch on a machine without a GPU would return PIVLFN_ERR_HIP instead)."""
+    import ctypes
+    from pivlfn import _lib
+    lib = _lib.load()
+    P = 4096                      # a non-null pointer that is never dereferenced: every case below fails its checks first
+    m6 = (ctypes.c_float * 6)()
+    fused = ctypes.c_int(7)
+
+    def refused(rc, *words):
+        msg = lib.pivlfn_last_error().decode()
+        assert rc == 1, (rc, msg)
+        for w in words:
+            assert w in msg, (w, msg)
+
+    # upconv
+    refused(lib.pivlfn_upconv_nhwc(None, P, P, 1, 4, 4, 1, 4, 4, None), "upconv", "null")
+    refused(lib.pivlfn_upconv_nhwc(P, P, P, 1, 4, 4, 2, 8, 8, None), "quads=2")
+    refused(lib.pivlfn_upconv_nhwc(P, P, P, 1, 4, 4, 14, 52, 56, None), "strides")
+    refused(lib.pivlfn_upconv_nhwc(P, P, P, 1, 4, 4, 1, 6, 8, None), "multiples of 4")
+    refused(lib.pivlfn_upconv_nhwc(P, P, P, 1, 40000, 4, 1, 4, 4, None), "80000 output rows")
+    refused(lib.pivlfn_upconv_nhwc(P, P, P, 70000, 4, 4, 1, 4, 4, None), "70000 images")
+    refused(lib.pivlfn_upconv_nhwc(P, P, P, 0, 4, 4, 1, 4, 4, None), "positive")
+    # backwarp_nhwc
+    refused(lib.pivlfn_backwarp_nhwc(P, None, 1.0, P, 1, 4, 4, 4, None), "backwarp_nhwc", "null")
+    refused(lib.pivlfn_backwarp_nhwc(P, P, 1.0, P, 1, 4, 4, 6, None), "C=6", "multiple of 4")
+    refused(lib.pivlfn_backwarp_nhwc(P, P, 1.0, P, 1, 32768, 32768, 8, None), "32-bit index range")
+    refused(lib.pivlfn_backwarp_nhwc(P, P, 1.0, P, 1, 0, 4, 4, None), "positive")
+    # reg_prep
+    refused(lib.pivlfn_reg_prep(P, P, P, 1.0, P, P, None, 1, 4, 4, 1, None), "reg_prep", "null")
+    refused(lib.pivlfn_reg_prep(P, P, P, 1.0, P, P, P, 70000, 4, 4, 1, None), "B=70000")
+    refused(lib.pivlfn_reg_prep(P, P, P, 1.0, P, P, P, 1, 46341, 46341, 1, None), "32-bit index range")
+    refused(lib.pivlfn_reg_prep(P, P, P, 1.0, P, P, P, 1, 4, 4, 2, None), "fused=2")
+    # reg_tail
+    refused(lib.pivlfn_reg_tail(P, 52, P, P, P, 0.0, 0.0, 7, None, None, 1.0, 1, 4, 4, None), "reg_tail", "null")
+    refused(lib.pivlfn_reg_tail(P, 52, P, P, P, 0.0, 0.0, 4, P, None, 1.0, 1, 4, 4, None), "k=4")
+    refused(lib.pivlfn_reg_tail(P, 48, P, P, P, 0.0, 0.0, 7, P, None, 1.0, 1, 4, 4, None), "dstride=48", ">= 49")
+    refused(lib.pivlfn_reg_tail(P, 12, P, P, P, 0.0, 0.0, 3, None, P, 1.0, 1, 0, 4, None), "H=0")
+    # prep_pyramid
+    refused(lib.pivlfn_prep_pyramid(P, P, None, P, 1, 64, 64, 6, None), "prep_pyramid", "null")
+    refused(lib.pivlfn_prep_pyramid(P, P, m6, P, 1, 64, 64, 7, None), "levels=7")
+    refused(lib.pivlfn_prep_pyramid(P, P, m6, P, 1, 16, 64, 6, None), "no pixel at level 6")
+    # conv1_fused
+    args = [P] * 10
+    refused(lib.pivlfn_conv1_fused_nhwc(*args[:6], None, *args[7:], 2, 64, 64, 1, ctypes.byref(fused), None), "conv1_fused", "null")
+    refused(lib.pivlfn_conv1_fused_nhwc(*args, 2, 64, 64, 3, ctypes.byref(fused), None), "B_feat=3")
+    refused(lib.pivlfn_conv1_fused_nhwc(*args, 2, 64, 64, 0, ctypes.byref(fused), None), "B_feat=0")
+    refused(lib.pivlfn_conv1_fused_nhwc(*args, 70000, 40000, 64, 1, ctypes.byref(fused), None), "32-bit index range")
+    with pytest.raises(ValueError):
+        _lib.check(lib.pivlfn_reg_tail(P, 12, P, P, P, 0.0, 0.0, 5, P, P, 1.0, 1, 4, 4, None), "reg_tail")

@@ -99,12 +99,33 @@ def test_forward_vs_oracle_mid_size(nets, dev):
     Winograd kernel at full occupancy (two workgroups per CU, several generations) and the 7 x 1 / 7 x 7 layers run on their
     streaming matrix-core kernels -- the small fixtures never get there.  Same tolerance as every end-to-end case."""
     a, b = synth.particle_batch(1, 512, 448, seed=4242)
+    _check_levels_then_flow(nets, "piv", a, b, dev)
+
+
+def _check_levels_then_flow(nets, model, a, b, dev):
+    """Every level's M, S and R flow (the training-mode return, src/models.py:363-367) against the oracle's with the end-to-end
+    tolerance, then the final flow: where the large-image kernels run (the fused conv1 from 512 x 256 up, the 7 x 1 / 1 x 7 and
+    split-operand Winograd layers), a level that leaves the bound is localised before later levels can damp it."""
     i1, i2 = torch.from_numpy(a), torch.from_numpy(b)
-    onet = orc.make_net("piv", synth.generate_weights("piv", 0), corr="c")
+    onet = orc.make_net(model, synth.generate_weights(model, 0), corr="c")
     with torch.no_grad():
-        want = onet.forward(i1, i2).numpy()
-    got = nets["piv"](i1.to(dev), i2.to(dev)).cpu().numpy()
-    _check(got, want, "piv 1x512x448")
+        want, want_levels = onet.forward(i1, i2, return_levels=True)
+    flow, levels = nets[model].forward_levels(i1.to(dev), i2.to(dev))
+    tag = f"{model} 1x{a.shape[-2]}x{a.shape[-1]}"
+    assert len(levels) == len(want_levels)
+    for j, (trio, wtrio) in enumerate(zip(levels, want_levels)):
+        for name, t, w in zip("MSR", trio, wtrio):
+            _check(t.cpu().numpy(), w.numpy(), f"{tag} level#{j} {name}")
+    got = flow.cpu().numpy()
+    _check(got, want.numpy(), tag)
+    return got, want.numpy()
+
+
+def test_forward_vs_oracle_hui_512(nets, dev):
+    """Hui at 512 x 512 (lowest level 2): its level 2 is 256^2, where the 7 x 1 / 1 x 7 distance layers and the split-operand
+    Winograd layers run; per-level M, S, R and the final flow against the oracle."""
+    a, b = synth.particle_batch(1, 512, 512, seed=4343)
+    _check_levels_then_flow(nets, "hui", a, b, dev)
 
 
 def test_batch_consistency_and_argument_errors(nets, dev):
@@ -210,11 +231,7 @@ def test_full_size_1024_vs_oracle(nets, dev):
     sliding-window warp+correlation launches, the one-tile-per-CU launch of level 3 and every full-occupancy convolution shape
     inside one forward; same tolerance as the golden cases."""
     a, b = synth.particle_batch(1, 1024, 1024, seed=1234)
-    i1, i2 = torch.from_numpy(a), torch.from_numpy(b)
-    onet = orc.make_net("piv", synth.generate_weights("piv", 0), corr="c")
-    with torch.no_grad():
-        want = onet.forward(i1, i2).numpy()
-    got = nets["piv"](i1.to(dev), i2.to(dev)).cpu().numpy()
+    got, want = _check_levels_then_flow(nets, "piv", a, b, dev)
     assert np.abs(want).max() > 1.0
     _check(got, want, "piv 1x1024x1024 vs oracle")
 
