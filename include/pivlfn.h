@@ -125,7 +125,9 @@ size_t pivlfn_workspace_bytes(const pivlfn_net *net, int B, int H, int W);
  * :321-323 happens on an internal copy).  flow: NCHW [B,2,H/2^(lowest_level-1),W/2^(lowest_level-1)],
  * already multiplied by SCALEFACTOR[1] (:370).
  * levels (optional, may be NULL): receives the per-level [M,S,R] flows of the training-mode return
- * (:363-367), coarsest level first, each NCHW [B,2,h,w], packed back to back. */
+ * (:363-367), coarsest level first, each NCHW [B,2,h,w], packed back to back.
+ * The workspace needs no initial contents: flow and levels do not depend on what it holds before the call (alignment gaps included),
+ * and nothing outside workspace[0, workspace_bytes), flow and levels is written. */
 int pivlfn_forward(pivlfn_net *net, const float *img1, const float *img2, float *flow, float *levels,
                    int B, int H, int W, void *workspace, size_t workspace_bytes, void *stream);
 
@@ -174,9 +176,11 @@ size_t pivlfn_levels_floats(const pivlfn_net *net, int B, int H, int W);
 /* ---- one convolution layer on the network's channels-last layout (what pivlfn_forward launches for every
  * torch.nn.Conv2d of src/models.py:70-106, 124, 154-163, 197-207, 229-272); exported so the kernel can be checked and
  * timed on its own.  weight: host, OIHW [cout,cin,kh,kw]; bias: host [cout].
- * x: [B,H,W,x_stride] (first cin lanes used, x_stride % 4 == 0, lanes cin..roundup(cin,4) must be finite);
- * y: [B,Ho,Wo,y_stride], lanes cout..min(roundup(cout,4), y_stride) are written as exact zeros;
- * res (optional): same grid as y, added before the activation; leaky: LeakyReLU(0.1) on the result.
+ * x: [B,H,W,x_stride] (first cin lanes used, x_stride % 4 == 0, lanes cin..roundup(cin,4) must be finite, lanes past them are
+ * not read);  y: [B,Ho,Wo,y_stride], lanes cout..min(roundup(cout,4), y_stride) are written as exact zeros, lanes past them untouched;
+ * res (optional): same grid as y, added before the activation; its lanes cout..roundup(cout,4) are added into y's zero lanes, so they
+ * must be +0.0 (pivlfn_forward's residuals, upConv_M's flow and the previous flow head's output, hold +0.0 there), and lanes past
+ * them are not read; leaky: LeakyReLU(0.1) on the result.
  * Dispatch = the PIVLFN_PRECISION_F32 network's for the shape, except Winograd (own entry point below): the direct kernel
  * everywhere, but a 7 x 1 layer (pad 3, 0; no residual, no activation) on an image of >= 256 x 256 pixels runs on the streaming
  * matrix-core kernel pivlfn_forward uses for conv_dist_R.0 there -- not bit-comparable with the F32_DIRECT network's layer. */
@@ -188,7 +192,7 @@ int pivlfn_conv2d_nhwc(const pivlfn_conv *conv, const float *x, int x_stride, fl
                        int leaky, void *stream);
 /* The same layer in the optional reduced-precision mode (BASELINE config #5: fp16 multiplicands, fp32 accumulation, on
  * v_mfma_f32_32x32x16_f16): x is fp32 or fp16 elements (x_is_f16; stride granularity 4 / 8 elements), y is stored as fp32
- * or fp16 (y_is_f16).  No residual input. */
+ * or fp16 (y_is_f16); with fp16 x, lanes cin..roundup(cin,8) must be finite and lanes past them are not read.  No residual input. */
 int pivlfn_conv2d_nhwc_f16(const pivlfn_conv *conv, const void *x, int x_stride, int x_is_f16, void *y, int y_stride,
                            int y_is_f16, int B, int H, int W, int stride, int pad_y, int pad_x, int leaky, void *stream);
 
@@ -219,14 +223,15 @@ int pivlfn_conv2d_nhwc_wino4(const pivlfn_conv *conv, const float *x, int x_stri
  * torch.cat + Conv2d of the front layers of Matching / Subpixel / Regularization (src/models.py:171-187, 209-217, 280) -- through
  * the dispatch of PIVLFN_PRECISION_F32: the multi-source staging of the direct and the Winograd kernel, for per-layer checks.
  * weight is OIHW over the concatenated channels; channels[i] = real channels of source i; x[i] is [B,H,W,x_stride[i]] with
- * x_stride[i] a multiple of 4 and >= channels[i] rounded up to 4 (padding lanes zero); only the last source may have a channel
- * count that is 4 (mod 8) after rounding. */
+ * x_stride[i] a multiple of 4 and >= channels[i] rounded up to 4 (padding lanes zero, lanes past them not read); only the last source
+ * may have a channel count that is 4 (mod 8) after rounding. */
 int pivlfn_conv_create_cat(const float *weight, const float *bias, int cout, int nsrc, const int *channels, int kh, int kw,
                            pivlfn_conv **out);
 int pivlfn_conv2d_nhwc_cat(const pivlfn_conv *conv, int nsrc, const float *const *x, const int *x_stride, float *y, int y_stride,
                            int B, int H, int W, int leaky, void *stream);
 
-/* The 32 -> 2 channel k x k flow head (conv_M.6 / conv_S.6) on its dedicated kernel: x [B,H,W,32], res4/out4 [B,H,W,4]. */
+/* The 32 -> 2 channel k x k flow head (conv_M.6 / conv_S.6) on its dedicated kernel: x [B,H,W,32], res4/out4 [B,H,W,4].  Lanes 2-3
+ * of res4 are not read (pivlfn_forward's flow4 holds zeros there); lanes 2-3 of out4 are written as +0.0. */
 int pivlfn_conv_head_nhwc(const pivlfn_conv *conv, const float *x, const float *res4, float *out4, int B, int H, int W,
                           void *stream);
 
@@ -246,8 +251,9 @@ int pivlfn_upconv_nhwc(const float *in, const float *w16, float *out, int B, int
 int pivlfn_backwarp_nhwc(const float *in, const float *flow4, float scale, float *out, int B, int H, int W, int C, void *stream);
 /* Regularization front, src/models.py:275-277: mean_out [B,2] = per-image mean of (u, v); misc4 [B,H,W,4] = (||img1 - backwarp(img2,
  * flow * scale)||_2 over the 3 colour lanes, u - mean_u, v - mean_v, 0).  img1_4 / img2_4 [B,H,W,4]; partial_ws: device scratch
- * of 128 * B floats.  fused = 1: pivlfn_forward's path (partial sums, the mean formed inside the reg_prep kernel); fused = 0: the
- * one-wave mean kernel, then reg_prep reads mean_out.  Both give the same bits.  1 <= B <= 65535. */
+ * of 128 * B floats, no initial contents needed.  Lane 3 of img1_4 / img2_4 is not read; misc4 lane 3 is written as +0.0.
+ * fused = 1: pivlfn_forward's path (partial sums, the mean formed inside the reg_prep kernel); fused = 0: the one-wave mean kernel,
+ * then reg_prep reads mean_out.  Both give the same bits.  1 <= B <= 65535. */
 int pivlfn_reg_prep(const float *img1_4, const float *img2_4, const float *flow4, float scale, float *misc4, float *mean_out,
                     float *partial_ws, int B, int H, int W, int fused, void *stream);
 /* Regularization tail, src/models.py:281-302: softmax(-dist^2) over the k*k channels, the k x k unfold of (u, v) with zero padding,
