@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B micro-benchmarks of single kernels at the shapes of the 1024x1024 PIV forward (one process, interleaved rounds).
 
-  python tools/bench_ops.py warp_corr [--batch 1] [--variants 1,4,5,0]   (1 first generation, 4 v3 one pixel per lane, 5 v4, 0 shipped policy)
+  python tools/bench_ops.py warp_corr [--batch 1] [--variants 0,8,9]   (0 shipped policy, 8 v7, 9 v6)
 Times N back-to-back launches between two events on the current stream (so each figure includes one ~1.5 us
 kernel boundary) and checks that all variants agree.
 """
@@ -44,10 +44,11 @@ def bench_warp_corr(args):
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream(dev).cuda_stream
     B = args.batch
-    variants = [int(v) for v in args.variants.split(",")]
+    variants = [int(v) for v in (args.variants or "0,8,9").split(",")]
     for L in [int(x) for x in args.levels.split(",")]:
         C, n, s = LEVELS[L]
         n = n * args.size // 1024
+        vs = [v for v in variants if not (v == 8 and C % 64)]          # v7 needs whole 64-channel groups (not level 4's C = 96)
         f1 = torch.randn(B, n, n, C, device=dev)
         f2 = torch.randn(B, n, n, C, device=dev)
         fl = torch.zeros(B, n, n, 4, device=dev)
@@ -57,7 +58,7 @@ def bench_warp_corr(args):
         outs = {}
         alg = 4 * B * (C * no * no + C * n * n + (2 * n * n if L < 6 else 0) + 49 * no * no)
         fns = {}
-        for v in variants:
+        for v in vs:
             out = torch.empty(B, no, no, 56, device=dev)
             outs[v] = out
 
@@ -66,12 +67,12 @@ def bench_warp_corr(args):
                 _chk(lib.pivlfn_warp_corr_nhwc(f1.data_ptr(), f2.data_ptr(), flow_ptr, 1.25, out.data_ptr(), B, C, n, n, s, 1, st), "wc")
             fns[v] = fn
         # interleaved rounds (clock state and neighbours are shared by all variants): min / median over the rounds
-        times = {v: [] for v in variants}
+        times = {v: [] for v in vs}
         for _ in range(3):
-            for v in variants:
+            for v in vs:
                 fns[v]()
         for rnd in range(args.rounds):
-            for v in (variants if rnd % 2 == 0 else variants[::-1]):
+            for v in (vs if rnd % 2 == 0 else vs[::-1]):
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 fns[v]()
                 torch.cuda.synchronize()
@@ -81,14 +82,14 @@ def bench_warp_corr(args):
                 b.record()
                 torch.cuda.synchronize()
                 times[v].append(a.elapsed_time(b) / 50 * 1e3)
-        for v in variants:
+        for v in vs:
             tmin, tmed = min(times[v]), sorted(times[v])[len(times[v]) // 2]
             print(f"L{L} B={B} C={C} {n}x{n} s={s} variant {v}: min {tmin:8.2f} us  med {tmed:8.2f} us   "
                   f"{alg / tmin / 1e3:8.1f} GB/s algorithmic ({alg / 1e6:.2f} MB)", flush=True)
-        ref = outs[variants[0]]
-        for v in variants[1:]:
+        ref = outs[vs[0]]
+        for v in vs[1:]:
             d = (outs[v] - ref).abs().max().item()
-            print(f"    variant {v} vs {variants[0]}: max abs diff {d:.3e}")
+            print(f"    variant {v} vs {vs[0]}: max abs diff {d:.3e}")
     lib.pivlfn_tune(0, 0)
 
 
@@ -152,7 +153,7 @@ def bench_conv(args):
     lib.pivlfn_tune(7, args.tune7)
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream(dev).cuda_stream
-    variants = [int(v) for v in args.variants.split(",")]
+    variants = [int(v) for v in (args.variants or "6,8,5").split(",")]
     for name, co, ci, k, s, n, bm in CONV_SHAPES:
         if args.filter and args.filter not in name:
             continue
@@ -302,7 +303,7 @@ if __name__ == "__main__":
     ap.add_argument("--tune7", type=int, default=0, help="ablation mask of the fp32 conv kernel in a -DPIVLFN_STAMPS build (pivlfn_tune(7, mask))")
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--size", type=int, default=1024, help="input image size the level shapes are derived from")
-    ap.add_argument("--variants", default="6,8,5")
+    ap.add_argument("--variants", help="comma-separated variant list (default: warp_corr 0,8,9; conv 6,8,5)")
     ap.add_argument("--levels", default="3,1,2,4,5,6")
     ap.add_argument("--smooth", action="store_true", help="wc_ablate: smooth flow instead of per-pixel noise")
     ap.add_argument("--masks", default="0,8,1,2,4,3,7", help="wc_ablate: pivlfn_tune(2, .) masks")

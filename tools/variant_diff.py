@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Which level first differs between two warp+correlation kernel variants (tools build) on a real pair?
-  python tools/variant_diff.py --pair 6 --variants 5,6"""
+  python tools/variant_diff.py --pair 6 --variants 0,9     (0 shipped policy, 9 v6 everywhere; 8 = v7 needs C % 64 == 0 at every level)"""
 import argparse
 import os
 import sys
@@ -18,7 +18,7 @@ def main():
     ap.add_argument("--pair", type=int, default=6)
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=99)
-    ap.add_argument("--variants", default="5,6")
+    ap.add_argument("--variants", default="0,9")
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--chunk", type=int, default=0, help="compare a batch of CHUNK consecutive pairs starting at --pair with the pairs alone")
     a = ap.parse_args()
