@@ -110,6 +110,32 @@ int pivlfn_resize_bilinear(const float *in, float *out, int B, int C, int H, int
 int pivlfn_stereo_2d3c(const float *flow, float *out, int B, int h, int w, int H, int W, const float *mul,
                        const float *coeff, const float *scale, const double *tangents, void *stream);
 
+/* ---- derived fields of a flow batch: src/postpro.py, calc_vorticity (:5-24) and de_vort (:27-50).  Added without an ABI bump
+ * (additive).  flow: NCHW [B,2,H,W] fp32 (u, v; what estimate(..., tensor=True) returns); out: NCHW [B,3,H,W], fp64 when out_f64 = 1,
+ * else fp32 (each plane the fp64 result below rounded once).  Planes: CALC_VORTICITY -> vort, shear, normal; DE_VORT -> vort, uy, vx.
+ * Arithmetic contract, every operation rounded on its own (no fma), x[i,j] read with the edge pixel repeated outside the image:
+ *   CALC_VORTICITY, fp64:  d = 8.0 * calib;  K = [[1,0,-1],[2,0,-2],[1,0,-1]] / d, each element divided in fp64;
+ *                   conv(x, k)[i,j] = sum over the taps of k in row-major order of k[p,q] * (double)x[i+1-p, j+1-q], from +0.0
+ *                   (zero taps included: a NaN or inf reaches all 3 x 3 neighbours);  dv = conv(v, K);  du = conv(u, -K^T)
+ *                   (K^T negated elementwise: its zero taps are -0.0 for d > 0);  vort = dv - du, shear = dv + du, normal = -(dv + du)
+ *                   = scipy.signal.convolve2d(x, k, 'same', boundary='symm') as the reference calls it.
+ *   DE_VORT, fp32:  vx = (((v[i+1,j+1] + 2 v[i,j+1]) + v[i-1,j+1]) - ((v[i+1,j-1] + 2 v[i,j-1]) + v[i-1,j-1])) / float32(8 calib)
+ *                   uy = (((u[i-1,j-1] + 2 u[i-1,j]) + u[i-1,j+1]) - ((u[i+1,j-1] + 2 u[i+1,j]) + u[i+1,j+1])) / float32(8 calib)
+ *                   vort = (double)vx - (double)uy in fp64  (NumPy >= 2 with a Python-float calib).
+ * Errors (PIVLFN_ERR_ARG): null flow / out, a non-positive size, H*W >= 2^31, B > 65535, an unknown kind, out_f64 not 0 / 1, a zero or
+ * non-finite calib (the reference returns inf / NaN there). */
+#define PIVLFN_FIELDS_CALC_VORTICITY 0   /* -> vort, shear, normal */
+#define PIVLFN_FIELDS_DE_VORT        1   /* -> vort, uy, vx */
+int pivlfn_flow_fields(const float *flow, void *out, int B, int H, int W, double calib, int kind, int out_f64, void *stream);
+
+/* ---- streaming statistics of a flow sequence: acc [7,H,W] fp64 += the per-pixel sums, in this order, of u, v, u*u, v*v, u*v, w,
+ * w*w over the B frames of flow (NCHW [B,2,H,W] fp32), w = the vort plane of PIVLFN_FIELDS_CALC_VORTICITY with this calib.  u, v are
+ * widened to fp64 exactly, products are rounded in fp64 (no fma), and each pixel adds the frames in frame order to the value acc held
+ * before the call (acc is read and written once per call): any split of a sequence into calls gives the same bits, and so does a
+ * sequential fp64 loop (acc += u*u, ...).  Errors (PIVLFN_ERR_ARG): null flow / acc, a non-positive size, H*W >= 2^31, a zero or
+ * non-finite calib. */
+int pivlfn_flow_stats_accumulate(const float *flow, double *acc, int B, int H, int W, double calib, void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

@@ -140,6 +140,16 @@ int pivlfn_stereo_2d3c(const float *flow, float *out, int B, int h, int w, int H
     return launch_stereo_2d3c(flow, out, B, h, w, H, W, mul, coeff, scale, tangents, (hipStream_t)stream);
 }
 
+int pivlfn_flow_fields(const float *flow, void *out, int B, int H, int W, double calib, int kind, int out_f64, void *stream)
+{
+    return launch_flow_fields(flow, out, B, H, W, calib, kind, out_f64, (hipStream_t)stream);
+}
+
+int pivlfn_flow_stats_accumulate(const float *flow, double *acc, int B, int H, int W, double calib, void *stream)
+{
+    return launch_flow_stats(flow, acc, B, H, W, calib, (hipStream_t)stream);
+}
+
 int pivlfn_create(const pivlfn_tensor *tensors, int n_tensors, float starting_scale, int lowest_level,
                   const float rgb_mean[6], pivlfn_net **out)
 {

@@ -250,4 +250,8 @@ int launch_stereo_2d3c(const float *flow, float *out, int B, int h, int w, int H
                        const float *coeff, const float *scale, const double *tan4, hipStream_t st);
 int flow_mean_partials(int HW);
 
+// ---- derived fields and streaming statistics (postpro.hip): [B,2,H,W] NCHW flows ----------------------------------------------
+int launch_flow_fields(const float *flow, void *out, int B, int H, int W, double calib, int kind, int out_f64, hipStream_t st);
+int launch_flow_stats(const float *flow, double *acc, int B, int H, int W, double calib, hipStream_t st);
+
 }  // namespace pivlfn

@@ -163,7 +163,8 @@ class _FlowDrain:
 
 def run_sequence(net, frames_fn: Callable[[int, int], torch.Tensor], n_frames: int, chunk: int, device: torch.device,
                  write_dir: Optional[str] = None, sink: Optional[Callable[[int, "object"], None]] = None,
-                 rank: int = 0, world: int = 1, estimate_fn: Callable = estimate, gather: bool = True) -> Dict[str, float]:
+                 rank: int = 0, world: int = 1, estimate_fn: Callable = estimate, gather: bool = True,
+                 stats=None) -> Dict[str, float]:
     """Estimate all n_frames-1 pairs.  With world > 1 a process group must be initialised (`nccl` on GPUs, `gloo` for
     rehearsals).  `gather=True` (BASELINE config #4): the flows of every chunk position are reassembled with one asynchronous
     all-gather and rank 0's `sink(pair_index, flow_hw2_numpy)` -- or its `.flo` writer when `write_dir` is given -- sees every pair
@@ -171,7 +172,9 @@ def run_sequence(net, frames_fn: Callable[[int, int], torch.Tensor], n_frames: i
     a shared directory ends up with the same set) -- rank 0 then does not receive world x the device-to-host traffic.
     A pipeline (round 6): the frames of chunk c + 1 are rendered / decoded on a side stream by a producer thread while chunk c is
     estimated; nothing synchronises the host with the compute stream inside the loop (the estimation time is taken with events);
-    finished chunks leave through a pinned ring on a copy stream and a sink thread.  Returns timing / count statistics of this rank."""
+    finished chunks leave through a pinned ring on a copy stream and a sink thread.  Returns timing / count statistics of this rank.
+    `stats` (a pivlfn.postpro.FlowStats of the flow size): every rank adds the flows of its own pairs right after each estimate, on
+    the compute stream; after the loop, with world > 1, the ranks merge their sums (a collective, whatever `gather` is)."""
     if n_frames < 2 or chunk < 1:
         raise ValueError("run_sequence: need at least two frames and chunk >= 1")
     n_pairs = n_frames - 1
@@ -232,6 +235,8 @@ def run_sequence(net, frames_fn: Callable[[int, int], torch.Tensor], n_frames: i
                     t1 = time.perf_counter()
                     out = estimate_fn(net, x[:-1], x[1:], tensor=True)
                     t_est_cpu += time.perf_counter() - t1
+                if stats is not None:
+                    stats.update(out)                  # the n valid rows only, never the zero rows that pad the gather
                 shape = tuple(out.shape[1:])
                 flows = out if (n == chunk or not use_gather) else torch.cat([out, out.new_zeros((chunk - n,) + shape)])
             if use_gather:
@@ -261,6 +266,8 @@ def run_sequence(net, frames_fn: Callable[[int, int], torch.Tensor], n_frames: i
         drain.close()
     if writer is not None:
         writer.close()
+    if stats is not None and world > 1:
+        stats.merge()
     if on_gpu:
         torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0

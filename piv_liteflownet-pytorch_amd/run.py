@@ -64,6 +64,9 @@ parser.add_argument("--batch", type=int, default=4, help="pairs per forward")
 parser.add_argument("--precision", type=str, default=None, choices=["fp32", "fp32_wino_mfma32", "fp32_direct", "fp32_split", "fp32_split3", "fp16"],
                     help="how the large convolutions multiply (not a reference flag; default: the library's, fp32 -- "
                          "see Network.precision)")
+parser.add_argument("--stats", action="store_true",
+                    help="also write per-pixel statistics of each input directory's flows (mean, RMS, Reynolds stress, vorticity; "
+                         "pivlfn.postpro.FlowStats) to <save>/stats.npz (not a reference flag; not with -b/-c, single process only)")
 
 
 @dataclass(frozen=True)
@@ -118,20 +121,40 @@ def mod_flow_name(first_frame: str, savedir: str, mod: Tuple[float, float]) -> s
     return flowname_modifier(tagged, savedir, pair=False)
 
 
-def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch, rank=0, world=1):
-    """Every pair of the folder through `estimate` (reference main_dl, run.py:137-168)."""
+class _StatsEstimate:
+    """estimate() that also adds every batch of flows to a FlowStats, created at the first batch's size (stream_pairs' estimate_fn)."""
+
+    def __init__(self):
+        self.stats = None
+
+    def __call__(self, net, img1, img2, tensor=True):
+        from pivlfn.inference import estimate
+        from pivlfn.postpro import FlowStats
+        flow = estimate(net, img1, img2, tensor=True)
+        if self.stats is None:
+            self.stats = FlowStats(flow.size(2), flow.size(3), device=flow.device)
+        self.stats.update(flow)
+        return flow
+
+
+def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch, rank=0, world=1, stats_file=None):
+    """Every pair of the folder through `estimate` (reference main_dl, run.py:137-168); with `stats_file`, FlowStats over the
+    pairs go there."""
     os.makedirs(savedir, exist_ok=True)
     ds = Run(root=inputdir, is_pair=is_pair, n_images=num_images, start_at=start_id)
     lo, hi = shard_bounds(len(ds), rank, world)
     print(f"Processing {hi - lo} of {len(ds)} pairs of images (rank {rank}/{world})...")
     loader = PairLoader(ds, lo, hi, batch, depth=2, pin=device.type == "cuda")
+    est = _StatsEstimate() if stats_file is not None else None
     try:
         with FloWriter() as writer:
             n = stream_pairs(net, loader, device,
-                             lambda flow, name: writer.submit(flow, flowname_modifier(name, savedir, pair=False)))
+                             lambda flow, name: writer.submit(flow, flowname_modifier(name, savedir, pair=False)), estimate_fn=est)
     finally:
         loader.close()
     assert n == hi - lo
+    if est is not None and est.stats is not None:
+        est.stats.save(stats_file)
     return hi - lo
 
 
@@ -165,6 +188,11 @@ def load_weights(args) -> Tuple[dict, str]:
 
 def main(argv: Optional[List[str]] = None) -> int:
     args = parser.parse_args(argv)
+    if args.stats and (args.brightness is not None or args.contrast is not None):
+        raise SystemExit("run.py: --stats is not available with -b/-c (every combination is a different experiment)")
+    if args.stats and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("run.py: --stats needs a single process (run.py has no process group to merge the statistics; "
+                         "the sharded path for statistics is pivlfn.sequence.run_sequence)")
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run.py: this build has no CPU path (the reference's correlation has none either, "
                          "src/correlation.py:339-340); a GPU is required")
@@ -188,7 +216,10 @@ def main(argv: Optional[List[str]] = None) -> int:
                 for k, v in sorted(vars(args).items()):
                     f.write(f"{k}: {v}\n")
         if mods is None:
-            total += main_dl(net, imdir, lay.flow, args.is_pair, args.start, args.num_images, device, args.batch, rank, world)
+            stats_file = os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "stats", 1)[:-4] + ".npz") \
+                if args.stats else None          # stats.npz (stats_left / stats_right.npz for the halves of a stereo set)
+            total += main_dl(net, imdir, lay.flow, args.is_pair, args.start, args.num_images, device, args.batch, rank, world,
+                             stats_file)
         else:
             total += main_mod(net, imdir, lay.flow, args.start, args.num_images, device, mods, args.batch, rank, world)
     print(f"Finish processing {total} flow fields")

@@ -3,7 +3,7 @@
 the ranks and estimated by pivlfn.sequence.run_sequence (contiguous shards + one halo frame, asynchronous all-gather of the
 flows, .flo files from rank 0's background writer).
 
-  python tools/sequence_run.py --frames 65 --size 1024 [--chunk 8] [--write DIR] [--precision fp16]
+  python tools/sequence_run.py --frames 65 --size 1024 [--chunk 8] [--write DIR] [--precision fp16] [--stats PATH]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/sequence_run.py --frames 10000 ...
 
 Prints one JSON line on rank 0: pairs/s of the estimation alone and of the whole loop (rendering + estimation + gather +
@@ -20,6 +20,7 @@ import torch
 
 import pivlfn
 from pivlfn import synth
+from pivlfn.postpro import FlowStats
 from pivlfn.sequence import run_sequence
 
 
@@ -31,6 +32,8 @@ def main():
     ap.add_argument("--write", default=None, help="directory for rank 0's .flo files")
     ap.add_argument("--null-sink", action="store_true", help="hand every flow to a sink that drops it (the loop without the disk)")
     ap.add_argument("--no-gather", action="store_true", help="no all-gather: every rank hands its own shard to its own sink / writer")
+    ap.add_argument("--stats", default=None, metavar="PATH",
+                    help="per-pixel statistics of all pairs (pivlfn.postpro.FlowStats, merged over the ranks): rank 0 writes them to PATH (.npz)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp32_wino_mfma32", "fp32_direct", "fp32_split", "fp32_split3", "fp16"])
     ap.add_argument("--model", default="piv")
     ap.add_argument("--seed", type=int, default=99)
@@ -58,9 +61,11 @@ def main():
 
     def null_sink(gi, flow):
         seen[0] += 1
+    stats = FlowStats(a.size, a.size, device=dev) if a.stats else None
     st = run_sequence(net, seq.frames, a.frames, a.chunk, dev, write_dir=a.write, sink=null_sink if a.null_sink else None, rank=rank, world=world,
-                      gather=not a.no_gather)
+                      gather=not a.no_gather, stats=stats)
     rss1 = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss
+    stats_file = stats.save(a.stats) if stats is not None and rank == 0 else None
     if dist is not None:
         dist.barrier()
     if rank == 0:
@@ -70,7 +75,8 @@ def main():
                           "pairs_per_s_whole_loop": round(st["pairs_total"] / st["seconds"], 2), "seconds": round(st["seconds"], 2),
                           "flows_handed_to_the_sink": st["flows_emitted"], "max_rss_mb_before_after": [round(rss0 / 1024), round(rss1 / 1024)],
                           "flo_files_written": st["flows_emitted"] if a.write else 0,
-                          "flo_gb_written": round(st["flows_emitted"] * (12 + S * S * 8) / 1e9, 2) if a.write else 0.0}), flush=True)
+                          "flo_gb_written": round(st["flows_emitted"] * (12 + S * S * 8) / 1e9, 2) if a.write else 0.0,
+                          "stats_file": stats_file}), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 
