@@ -136,6 +136,45 @@ int pivlfn_flow_fields(const float *flow, void *out, int B, int H, int W, double
  * non-finite calib. */
 int pivlfn_flow_stats_accumulate(const float *flow, double *acc, int B, int H, int W, double calib, void *stream);
 
+/* ---- vector validation: the normalized median test (Westerweel & Scarano, Exp. Fluids 39, 2005) with masking or median
+ * replacement of the rejected vectors.  Added without an ABI bump (additive).
+ * flow: NCHW [B,2,H,W] fp32;  flag: [B,H,W] bytes, required in every mode;  out: NCHW [B,2,H,W] (NULL allowed for FLAG only), must
+ * not overlap flow;  resid: NCHW [B,2,H,W] or NULL.  At most two launches on `stream`, no allocation, no host synchronisation; a batch
+ * equals its frames one at a time, bit for bit.  No output depends on what flag / out / resid held before the call.
+ * Arithmetic contract, all fp32, every operation rounded on its own (no fma), the division correctly rounded:
+ *   unknown(p) = isnan(u) | isnan(v) | fabs(u) > 1e9f | fabs(v) > 1e9f   (the reference's _unknown_flow, src/utils_plot.py:23, 299-306)
+ *   A loaded component is canonicalised by x + 0.0f (-0.0 becomes +0.0) before it is compared or subtracted, so equal values are
+ *   indistinguishable and every sorting / selection method gives the same bits; medians are medians of canonicalised values.
+ *   Values copied to the output are copied bit for bit.
+ *   N(p), p = (y, x): the pixels (y + i*spacing, x + j*spacing), i, j in [-radius, radius], (i, j) != (0, 0), that lie inside the
+ *   image and are not unknown; n = |N(p)| is 0..8 (radius 1) or 0..24 (radius 2).  No edge replication.
+ *   median of n >= 1 values sorted ascending a[0..n-1]:  n odd -> a[(n-1)/2];  n even -> (a[n/2-1] + a[n/2]) * 0.5f
+ *   pass 1, per component c:  m_c = median{U_c(q)},  r_c = median{fabs(U_c(q) - m_c)}  over q in N(p);
+ *                   R_c = fabs(U_c(p) - m_c) / (r_c + eps);   flag(p) bit 0 (outlier) = R_u > thresh || R_v > thresh,
+ *                   bit 1 = unknown(p).  n = 0 -> R_c = 0, bit 0 clear;  unknown(p) -> R_c = 0, bit 0 clear, bit 1 set.
+ *                   resid = R_u, R_v.
+ *   pass 2:  FLAG     no flow output.
+ *            MASK     flag != 0 -> both components 1e10f (the Middlebury "unknown" value), else copied.
+ *            REPLACE  for flag(p) != 0: V(p) = the in-image neighbours (same radius, spacing) with flag(q) == 0 after pass 1 (one
+ *                     iteration, a replaced value is never used to replace another);  |V| >= 1 -> out_c = median{U_c(q), q in V(p)};
+ *                     |V| = 0 -> the input copied and bit 2 (not replaced) set in flag(p).  flag(p) == 0 -> copied.
+ * Errors (PIVLFN_ERR_ARG, before any launch): null flow / flag, null out outside FLAG, out == flow, a non-positive size,
+ * H*W >= 2^31, B > 65535, radius not 1 or 2, spacing < 1 or radius*spacing >= 2^15, eps negative or non-finite, thresh non-finite
+ * or <= 0, an unknown mode. */
+#define PIVLFN_VALIDATE_FLAG    0
+#define PIVLFN_VALIDATE_MASK    1
+#define PIVLFN_VALIDATE_REPLACE 2
+int pivlfn_flow_validate(const float *flow, float *out, unsigned char *flag, float *resid, int B, int H, int W,
+                         int radius, int spacing, float eps, float thresh, int mode, void *stream);
+
+/* ---- pivlfn_flow_stats_accumulate with a flag byte per frame and pixel (pivlfn_flow_validate's [B,H,W]): the same acc [7,H,W] fp64,
+ * order, fp64 arithmetic and frame order, but frame b adds to u, v, u*u, v*v, u*v at p only if flag[b,p] == 0, and to w, w*w only if
+ * all nine edge-clamped 3 x 3 neighbours of p have flag == 0.  cnt [2,H,W] fp64 += the number of additions of either kind (exact
+ * integers).  With an all-zero flag the seven sums are bit-identical to pivlfn_flow_stats_accumulate's.  Added without an ABI bump.
+ * Errors (PIVLFN_ERR_ARG): as pivlfn_flow_stats_accumulate, and null flag / cnt. */
+int pivlfn_flow_stats_accumulate_masked(const float *flow, const unsigned char *flag, double *acc, double *cnt,
+                                        int B, int H, int W, double calib, void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

@@ -150,6 +150,18 @@ int pivlfn_flow_stats_accumulate(const float *flow, double *acc, int B, int H, i
     return launch_flow_stats(flow, acc, B, H, W, calib, (hipStream_t)stream);
 }
 
+int pivlfn_flow_validate(const float *flow, float *out, unsigned char *flag, float *resid, int B, int H, int W, int radius, int spacing,
+                         float eps, float thresh, int mode, void *stream)
+{
+    return launch_flow_validate(flow, out, flag, resid, B, H, W, radius, spacing, eps, thresh, mode, (hipStream_t)stream);
+}
+
+int pivlfn_flow_stats_accumulate_masked(const float *flow, const unsigned char *flag, double *acc, double *cnt, int B, int H, int W,
+                                        double calib, void *stream)
+{
+    return launch_flow_stats_masked(flow, flag, acc, cnt, B, H, W, calib, (hipStream_t)stream);
+}
+
 int pivlfn_create(const pivlfn_tensor *tensors, int n_tensors, float starting_scale, int lowest_level,
                   const float rgb_mean[6], pivlfn_net **out)
 {

@@ -253,5 +253,11 @@ int flow_mean_partials(int HW);
 // ---- derived fields and streaming statistics (postpro.hip): [B,2,H,W] NCHW flows ----------------------------------------------
 int launch_flow_fields(const float *flow, void *out, int B, int H, int W, double calib, int kind, int out_f64, hipStream_t st);
 int launch_flow_stats(const float *flow, double *acc, int B, int H, int W, double calib, hipStream_t st);
+int launch_flow_stats_masked(const float *flow, const unsigned char *flag, double *acc, double *cnt, int B, int H, int W, double calib,
+                             hipStream_t st);
+
+// ---- vector validation (validate.hip): normalized median test on [B,2,H,W] NCHW flows, flag [B,H,W] bytes ------------------------
+int launch_flow_validate(const float *flow, float *out, unsigned char *flag, float *resid, int B, int H, int W, int radius,
+                         int spacing, float eps, float thresh, int mode, hipStream_t st);
 
 }  // namespace pivlfn

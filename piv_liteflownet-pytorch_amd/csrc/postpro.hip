@@ -115,6 +115,57 @@ __global__ __launch_bounds__(256) void flow_stats_kernel(const float *__restrict
     }
 }
 
+// flow_stats_kernel with a flag byte per frame and pixel (flow_validate's): frame b adds to u, v, uu, vv, uv only where its flag is 0
+// and to w, ww only where the flags of all nine edge-clamped 3 x 3 neighbours are 0; cnt [2,H,W] counts both kinds of additions.
+// A term that is left out is not computed into the sum at all (no 0 * NaN), so an all-zero flag gives flow_stats_kernel's bits.
+__global__ __launch_bounds__(256) void flow_stats_masked_kernel(const float *__restrict__ flow, const unsigned char *__restrict__ flag,
+                                                                double *__restrict__ acc, double *__restrict__ cnt, int B,
+                                                                const PostproParams p)
+{
+#pragma clang fp contract(off)
+    const unsigned HW = (unsigned)p.H * (unsigned)p.W;
+    for (unsigned pix = blockIdx.x * 256 + threadIdx.x; pix < HW; pix += gridDim.x * 256) {
+        const int y = (int)(pix / (unsigned)p.W), x = (int)(pix - (unsigned)y * (unsigned)p.W);
+        const int ys[3] = {y > 0 ? y - 1 : 0, y, y + 1 < p.H ? y + 1 : p.H - 1};
+        const int xs[3] = {x > 0 ? x - 1 : 0, x, x + 1 < p.W ? x + 1 : p.W - 1};
+        double s[7], c0 = cnt[pix], c1 = cnt[(size_t)HW + pix];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) s[k] = acc[(size_t)k * HW + pix];
+        for (int b = 0; b < B; ++b) {
+            const float *u = flow + (size_t)b * 2 * HW, *v = u + HW;
+            const unsigned char *f = flag + (size_t)b * HW;
+            unsigned any = 0;
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) any |= f[(unsigned)ys[r] * (unsigned)p.W + (unsigned)xs[c]];
+            if (f[pix] == 0) {
+                const double u0 = (double)u[pix], v0 = (double)v[pix];
+                s[0] = s[0] + u0;
+                s[1] = s[1] + v0;
+                s[2] = s[2] + u0 * u0;
+                s[3] = s[3] + v0 * v0;
+                s[4] = s[4] + u0 * v0;
+                c0 = c0 + 1.0;
+            }
+            if (any == 0) {
+                float nu[3][3], nv[3][3];
+                load3x3(u, y, x, p.H, p.W, nu);
+                load3x3(v, y, x, p.H, p.W, nv);
+                double r[3];
+                calc_vorticity_at(p, nu, nv, r);
+                s[5] = s[5] + r[0];
+                s[6] = s[6] + r[0] * r[0];
+                c1 = c1 + 1.0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 7; ++k) acc[(size_t)k * HW + pix] = s[k];
+        cnt[pix] = c0;
+        cnt[(size_t)HW + pix] = c1;
+    }
+}
+
 // Host-side checks shared by both entry points; fills the taps.
 static int postpro_params(const char *what, int B, int H, int W, double calib, PostproParams &p)
 {
@@ -178,6 +229,18 @@ int launch_flow_stats(const float *flow, double *acc, int B, int H, int W, doubl
     const int rc = postpro_params("flow_stats_accumulate", B, H, W, calib, p);
     if (rc != PIVLFN_OK) return rc;
     hipLaunchKernelGGL(flow_stats_kernel, dim3(postpro_grid(H, W, 1)), dim3(256), 0, st, flow, acc, B, p);
+    PIV_CHECK_HIP(hipGetLastError());
+    return PIVLFN_OK;
+}
+
+int launch_flow_stats_masked(const float *flow, const unsigned char *flag, double *acc, double *cnt, int B, int H, int W, double calib,
+                             hipStream_t st)
+{
+    PIV_REQUIRE(flow && flag && acc && cnt, "flow_stats_accumulate_masked: null pointer (flow, flag, acc and cnt are required)");
+    PostproParams p;
+    const int rc = postpro_params("flow_stats_accumulate_masked", B, H, W, calib, p);
+    if (rc != PIVLFN_OK) return rc;
+    hipLaunchKernelGGL(flow_stats_masked_kernel, dim3(postpro_grid(H, W, 1)), dim3(256), 0, st, flow, flag, acc, cnt, B, p);
     PIV_CHECK_HIP(hipGetLastError());
     return PIVLFN_OK;
 }

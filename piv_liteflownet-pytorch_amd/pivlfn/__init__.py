@@ -9,6 +9,7 @@ from .correlation import FunctionCorrelation, ModuleCorrelation          # noqa:
 from .models import LiteFlowNet, LiteFlowNet2, Network, backwarp, hui_liteflownet, piv_liteflownet  # noqa: F401
 from .inference import Inference, estimate                               # noqa: F401
 from .stereo import estimate_stereo                                      # noqa: F401
+from .validate import MaskedFlowStats, validate_flow                     # noqa: F401
 
 __all__ = ["FunctionCorrelation", "ModuleCorrelation", "LiteFlowNet", "LiteFlowNet2", "Network", "backwarp",
-           "hui_liteflownet", "piv_liteflownet", "estimate", "Inference", "estimate_stereo"]
+           "hui_liteflownet", "piv_liteflownet", "estimate", "Inference", "estimate_stereo", "validate_flow", "MaskedFlowStats"]

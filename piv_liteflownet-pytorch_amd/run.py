@@ -2,7 +2,7 @@
 """Counterpart of the reference's run.py on the HIP path: same flags, same output tree.
 
   python run.py --model piv -i DIR [-i DIR2 ...] -o OUT [-p] [-s N] [-n N] [-b F ...] [-c F ...] [-v 1|2]
-                [--weights FILE] [--batch B]
+                [--weights FILE] [--batch B] [--stats] [--validate flag|mask|replace]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -67,6 +67,14 @@ parser.add_argument("--precision", type=str, default=None, choices=["fp32", "fp3
 parser.add_argument("--stats", action="store_true",
                     help="also write per-pixel statistics of each input directory's flows (mean, RMS, Reynolds stress, vorticity; "
                          "pivlfn.postpro.FlowStats) to <save>/stats.npz (not a reference flag; not with -b/-c, single process only)")
+parser.add_argument("--validate", type=str, default=None, choices=["flag", "mask", "replace"],
+                    help="normalized median test on every flow, on the device (pivlfn.validate.validate_flow; not a reference flag; "
+                         "not with -b/-c, single process only): 'flag' writes the flows unchanged, 'mask' writes 1e10 for rejected "
+                         "vectors, 'replace' the median of their neighbours; all write <save>/validation.json")
+parser.add_argument("--validate-radius", type=int, default=1, help="neighbourhood radius of --validate: 1 (3 x 3) or 2 (5 x 5)")
+parser.add_argument("--validate-spacing", type=int, default=1, help="distance in pixels between the neighbours of --validate")
+parser.add_argument("--validate-eps", type=float, default=0.1, help="noise level of --validate in pixels (raise it with the spacing)")
+parser.add_argument("--validate-thresh", type=float, default=2.0, help="normalized residual above which --validate rejects a vector")
 
 
 @dataclass(frozen=True)
@@ -137,23 +145,94 @@ class _StatsEstimate:
         return flow
 
 
-def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch, rank=0, world=1, stats_file=None):
+class _ValidateEstimate:
+    """estimate() followed by validate_flow on the device (stream_pairs' estimate_fn): returns what the .flo files get -- the flow
+    itself for "flag", the masked / replaced flow otherwise.  The per-pair counts of the three flag bits are reduced on the device
+    and stay there until counts() copies them once; with `stats`, "flag" and "mask" feed (raw flow, flag) to a MaskedFlowStats and
+    "replace" feeds the replaced flow to a FlowStats."""
+
+    def __init__(self, mode, radius, spacing, eps, thresh, stats):
+        self.mode, self.params, self.want_stats = mode, dict(radius=radius, spacing=spacing, eps=eps, thresh=thresh), stats
+        self.stats = None
+        self._counts = []
+
+    def __call__(self, net, img1, img2, tensor=True):
+        from pivlfn.inference import estimate
+        from pivlfn.postpro import FlowStats
+        from pivlfn.validate import NOT_REPLACED, OUTLIER, UNKNOWN, MaskedFlowStats, validate_flow
+        flow = estimate(net, img1, img2, tensor=True)
+        res = validate_flow(flow, mode=self.mode, **self.params)
+        flat = res.flag.flatten(1)
+        self._counts.append(torch.stack([(flat & bit).ne(0).sum(1) for bit in (OUTLIER, UNKNOWN, NOT_REPLACED)], dim=1))
+        if self.want_stats:
+            if self.stats is None:
+                kind = FlowStats if self.mode == "replace" else MaskedFlowStats
+                self.stats = kind(flow.size(2), flow.size(3), device=flow.device)
+            if self.mode == "replace":
+                self.stats.update(res.flow)
+            else:
+                self.stats.update(flow, res.flag)
+        return res.flow
+
+    def counts(self):
+        """[pairs, 3] int64 on the host: outlier, unknown, not-replaced vectors of each pair, in the order of the pairs."""
+        if not self._counts:
+            return torch.zeros([0, 3], dtype=torch.int64)
+        return torch.cat(self._counts).cpu()
+
+    def save_stats(self, path):
+        import numpy as np
+        if self.mode == "replace":            # FlowStats.save's fields, and which validation the flows went through
+            st = self.stats
+            np.savez(path, acc=st.acc.cpu().numpy(), calib=np.float64(st.calib), validation=self.mode, **st.result())
+        else:
+            self.stats.save(path, validation=self.mode)
+
+
+def write_validation_json(path, est, names):
+    """<save>/validation.json: the parameters, per pair name the counts of outlier / unknown / not-replaced vectors, the totals."""
+    import json
+    rows = est.counts().tolist()
+    assert len(rows) == len(names)
+    keys = ("outlier", "unknown", "not_replaced")
+    doc = {"mode": est.mode, **est.params,
+           "pairs": {name: dict(zip(keys, row)) for name, row in zip(names, rows)},
+           "total": {k: sum(row[i] for row in rows) for i, k in enumerate(keys)}}
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+
+
+def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch, rank=0, world=1, stats_file=None,
+            validate=None, validation_file=None):
     """Every pair of the folder through `estimate` (reference main_dl, run.py:137-168); with `stats_file`, FlowStats over the
-    pairs go there."""
+    pairs go there; with `validate` (the keyword arguments of _ValidateEstimate bar `stats`), every flow goes through
+    validate_flow before it is copied back and the counts go to `validation_file`."""
     os.makedirs(savedir, exist_ok=True)
     ds = Run(root=inputdir, is_pair=is_pair, n_images=num_images, start_at=start_id)
     lo, hi = shard_bounds(len(ds), rank, world)
     print(f"Processing {hi - lo} of {len(ds)} pairs of images (rank {rank}/{world})...")
     loader = PairLoader(ds, lo, hi, batch, depth=2, pin=device.type == "cuda")
-    est = _StatsEstimate() if stats_file is not None else None
+    if validate is not None:
+        est = _ValidateEstimate(stats=stats_file is not None, **validate)
+    else:
+        est = _StatsEstimate() if stats_file is not None else None
+    seen = []
+
+    def sink(flow, name):
+        seen.append(name)
+        writer.submit(flow, flowname_modifier(name, savedir, pair=False))
     try:
         with FloWriter() as writer:
-            n = stream_pairs(net, loader, device,
-                             lambda flow, name: writer.submit(flow, flowname_modifier(name, savedir, pair=False)), estimate_fn=est)
+            n = stream_pairs(net, loader, device, sink, estimate_fn=est)
     finally:
         loader.close()
     assert n == hi - lo
-    if est is not None and est.stats is not None:
+    if validate is not None:
+        write_validation_json(validation_file, est, seen)
+        if est.stats is not None:
+            est.save_stats(stats_file)
+    elif est is not None and est.stats is not None:
         est.stats.save(stats_file)
     return hi - lo
 
@@ -193,6 +272,19 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.stats and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("run.py: --stats needs a single process (run.py has no process group to merge the statistics; "
                          "the sharded path for statistics is pivlfn.sequence.run_sequence)")
+    validate = None
+    if args.validate is not None:
+        if args.brightness is not None or args.contrast is not None:
+            raise SystemExit("run.py: --validate is not available with -b/-c (every combination is a different experiment)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("run.py: --validate needs a single process (validation.json lists the pairs of one process)")
+        from pivlfn.validate import check_params
+        validate = dict(mode=args.validate, radius=args.validate_radius, spacing=args.validate_spacing, eps=args.validate_eps,
+                        thresh=args.validate_thresh)
+        try:
+            check_params(validate["radius"], validate["spacing"], validate["eps"], validate["thresh"], validate["mode"])
+        except ValueError as e:
+            raise SystemExit(f"run.py: {e}")
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run.py: this build has no CPU path (the reference's correlation has none either, "
                          "src/correlation.py:339-340); a GPU is required")
@@ -214,12 +306,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         if rank == 0:
             with open(lay.args_file, "w") as f:
                 for k, v in sorted(vars(args).items()):
+                    if validate is None and k.startswith("validate"):
+                        continue                 # without --validate the file is what it was before the flag existed
                     f.write(f"{k}: {v}\n")
         if mods is None:
             stats_file = os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "stats", 1)[:-4] + ".npz") \
                 if args.stats else None          # stats.npz (stats_left / stats_right.npz for the halves of a stereo set)
+            validation_file = os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "validation", 1)[:-4] + ".json")
             total += main_dl(net, imdir, lay.flow, args.is_pair, args.start, args.num_images, device, args.batch, rank, world,
-                             stats_file)
+                             stats_file, validate, validation_file)
         else:
             total += main_mod(net, imdir, lay.flow, args.start, args.num_images, device, mods, args.batch, rank, world)
     print(f"Finish processing {total} flow fields")
