@@ -175,6 +175,31 @@ int pivlfn_flow_validate(const float *flow, float *out, unsigned char *flag, flo
 int pivlfn_flow_stats_accumulate_masked(const float *flow, const unsigned char *flag, double *acc, double *cnt,
                                         int B, int H, int W, double calib, void *stream);
 
+/* ---- image pre-processing in front of the network: background removal and sliding min-max normalisation (Westerweel 1993;
+ * Adrian & Westerweel, Particle Image Velocimetry, 2011) of uint8 frames.  The reference has no such step.  Added without an ABI bump
+ * (additive).  frames I: [n,H,W,3] bytes;  bg B: [H,W,3] bytes or NULL;  out: NCHW [n,3,H,W] fp32 in [0,1], must not overlap frames or
+ * bg.  One launch on `stream`, no allocation, no workspace, no host synchronisation; the channels are treated independently and
+ * identically, a batch equals its frames one at a time, and out does not depend on what it held before the call.
+ * Arithmetic contract, per frame and channel, integers up to the one division:
+ *   1. x = max(I - B, 0) with a background, x = I without: an integer 0..255.
+ *   2. k != 0 (k odd, 3 <= k <= 31, r = k/2, n = k*k; 1 <= floor <= 255).  Every coordinate is clamped to the image (edge
+ *      replication), in both passes:
+ *        lo(p) = min, hi(p) = max of x over the k x k window centred at p;
+ *        L(p) = sum of lo, S(p) = sum of hi over the k x k window centred at p (lo and hi taken at the clamped positions);
+ *        num = n*x(p) - L(p);  den = max(S(p) - L(p), floor*n);  out = (float)num / (float)den, one correctly rounded division.
+ *      num and den stay below 255*31*31 < 2^24, so both conversions are exact, and 0 <= num <= den: every window that contains p has
+ *      lo <= x(p) <= hi, and clamping only moves a window position nearer to p.  No clamp of out is needed or applied.
+ *   3. k == 0:  out = (float)x / 255.0f, correctly rounded.  With NULL bg these are the bits of ToTensor's byte -> float -> div(255).
+ * Errors (PIVLFN_ERR_ARG, before any launch): null frames / out, n, H or W < 1, H*W*3 >= 2^31, n > 65535, k not 0 or odd in 3..31,
+ * floor outside 1..255 (whatever k is), out overlapping frames or bg. */
+int pivlfn_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W,
+                             int k, int floor, void *stream);
+
+/* ---- background accumulator of a recording: bg [H,W,3] bytes = min(bg, the minimum over the n frames [n,H,W,3]), in place, byte by
+ * byte; start it at 255.  One launch, no temporaries.  Errors (PIVLFN_ERR_ARG): null frames / bg, n, H or W < 1, H*W*3 >= 2^31, bg
+ * overlapping frames. */
+int pivlfn_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

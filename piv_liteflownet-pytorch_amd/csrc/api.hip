@@ -162,6 +162,17 @@ int pivlfn_flow_stats_accumulate_masked(const float *flow, const unsigned char *
     return launch_flow_stats_masked(flow, flag, acc, cnt, B, H, W, calib, (hipStream_t)stream);
 }
 
+int pivlfn_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, void *stream)
+{
+    return launch_frames_background_min(frames, bg, n, H, W, (hipStream_t)stream);
+}
+
+int pivlfn_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W, int k, int floor,
+                             void *stream)
+{
+    return launch_frames_preprocess(frames, bg, out, n, H, W, k, floor, (hipStream_t)stream);
+}
+
 int pivlfn_create(const pivlfn_tensor *tensors, int n_tensors, float starting_scale, int lowest_level,
                   const float rgb_mean[6], pivlfn_net **out)
 {

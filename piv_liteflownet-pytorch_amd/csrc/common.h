@@ -260,4 +260,9 @@ int launch_flow_stats_masked(const float *flow, const unsigned char *flag, doubl
 int launch_flow_validate(const float *flow, float *out, unsigned char *flag, float *resid, int B, int H, int W, int radius,
                          int spacing, float eps, float thresh, int mode, hipStream_t st);
 
+// ---- image pre-processing (preproc.hip): [n,H,W,3] uint8 frames -> background minimum [H,W,3], network input [n,3,H,W] fp32 --------
+int launch_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, hipStream_t st);
+int launch_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W, int k, int floor,
+                             hipStream_t st);
+
 }  // namespace pivlfn

@@ -10,6 +10,8 @@ from .models import LiteFlowNet, LiteFlowNet2, Network, backwarp, hui_liteflowne
 from .inference import Inference, estimate                               # noqa: F401
 from .stereo import estimate_stereo                                      # noqa: F401
 from .validate import MaskedFlowStats, validate_flow                     # noqa: F401
+from .preproc import FrameBackground, preprocess_frames                  # noqa: F401
 
 __all__ = ["FunctionCorrelation", "ModuleCorrelation", "LiteFlowNet", "LiteFlowNet2", "Network", "backwarp",
-           "hui_liteflownet", "piv_liteflownet", "estimate", "Inference", "estimate_stereo", "validate_flow", "MaskedFlowStats"]
+           "hui_liteflownet", "piv_liteflownet", "estimate", "Inference", "estimate_stereo", "validate_flow", "MaskedFlowStats",
+           "preprocess_frames", "FrameBackground"]

@@ -169,7 +169,8 @@ class PairLoader:
 
 def stream_pairs(net, loader: PairLoader, device: torch.device, sink: Callable[..., None],
                  estimate_fn: Optional[Callable] = None, in_flight: int = 3,
-                 mods: Optional[Sequence[Tuple[float, float]]] = None, group: int = 1) -> int:
+                 mods: Optional[Sequence[Tuple[float, float]]] = None, group: int = 1,
+                 prep: Optional[Callable[[torch.Tensor], torch.Tensor]] = None) -> int:
     """Drive `estimate` over a PairLoader.  `sink(flow_hw2, name)` is called once per pair, in order; the numpy view it gets
     owns a reference to its (pinned) batch buffer, so an asynchronous writer may keep it.  On a GPU the uploads and
     downloads run on a copy stream and overlap with compute; on the CPU (tests of the host logic, with a stand-in
@@ -178,12 +179,15 @@ def stream_pairs(net, loader: PairLoader, device: torch.device, sink: Callable[.
     frames modified on the device (pivlfn.imagemod), and the sink is called as `sink(flow_hw2, name, (brightness, contrast))`.
     `group`: every `group` consecutive pairs of a batch make ONE output (pivlfn.stereo: a left and a right pair).  `estimate_fn`
     then returns the outputs already in the file layout, [n / group, H, W, C], the sink gets the name of each group's first
-    pair, and the count returned is the number of outputs."""
+    pair, and the count returned is the number of outputs.
+    `prep`: a callable uint8 [n,H,W,3] -> float32 [n,3,H,W] (pivlfn.preproc.Preprocessor) that takes the place of `u8_to_input` for
+    both frames of every batch."""
     if group < 1:
         raise ValueError("stream_pairs: group must be >= 1")
     if estimate_fn is None:
         from .inference import estimate as estimate_fn      # noqa: N813
     from .imagemod import image_mod
+    to_input = prep if prep is not None else u8_to_input
     on_gpu = device.type == "cuda"
     copy = torch.cuda.Stream(device) if on_gpu else None
     pending: List[Tuple[Optional[torch.cuda.Event], torch.Tensor, Sequence[str], Optional[Tuple[float, float]]]] = []
@@ -221,7 +225,7 @@ def stream_pairs(net, loader: PairLoader, device: torch.device, sink: Callable[.
             a_dev, b_dev = a8, b8
         for mod in (mods if mods is not None else (None,)):
             am, bm = (a_dev, b_dev) if mod is None else (image_mod(a_dev, *mod), image_mod(b_dev, *mod))
-            flow = estimate_fn(net, u8_to_input(am), u8_to_input(bm), tensor=True)           # [n,2,H,W]
+            flow = estimate_fn(net, to_input(am), to_input(bm), tensor=True)                 # [n,2,H,W]
             if group == 1:
                 out = flow.permute(0, 2, 3, 1).contiguous()                                  # [n,H,W,2], the .flo layout
             else:

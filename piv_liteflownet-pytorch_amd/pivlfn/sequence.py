@@ -26,12 +26,13 @@ from .inference import estimate
 from .pipeline import u8_to_input
 
 
-def frames_to_input(frames: torch.Tensor) -> torch.Tensor:
+def frames_to_input(frames: torch.Tensor, prep: Optional[Callable[[torch.Tensor], torch.Tensor]] = None) -> torch.Tensor:
     """uint8 [n,H,W] or [n,H,W,3] -> float32 [n,3,H,W] in [0,1] (grey frames replicated to three channels), the same bits as
-    ToTensor / run.py's input path: the table of correctly divided k/255 of `pipeline.u8_to_input`, not the GPU's `t * (1/255)`."""
+    ToTensor / run.py's input path: the table of correctly divided k/255 of `pipeline.u8_to_input`, not the GPU's `t * (1/255)`.
+    `prep` (uint8 [n,H,W,3] -> float32 [n,3,H,W]) takes the place of that conversion."""
     if frames.dim() == 3:
         frames = frames[..., None].expand(-1, -1, -1, 3)
-    return u8_to_input(frames.contiguous())
+    return (prep if prep is not None else u8_to_input)(frames.contiguous())
 
 
 def flow_file_name(pair_index: int) -> str:
@@ -164,7 +165,7 @@ class _FlowDrain:
 def run_sequence(net, frames_fn: Callable[[int, int], torch.Tensor], n_frames: int, chunk: int, device: torch.device,
                  write_dir: Optional[str] = None, sink: Optional[Callable[[int, "object"], None]] = None,
                  rank: int = 0, world: int = 1, estimate_fn: Callable = estimate, gather: bool = True,
-                 stats=None) -> Dict[str, float]:
+                 stats=None, prep: Optional[Callable[[torch.Tensor], torch.Tensor]] = None) -> Dict[str, float]:
     """Estimate all n_frames-1 pairs.  With world > 1 a process group must be initialised (`nccl` on GPUs, `gloo` for
     rehearsals).  `gather=True` (BASELINE config #4): the flows of every chunk position are reassembled with one asynchronous
     all-gather and rank 0's `sink(pair_index, flow_hw2_numpy)` -- or its `.flo` writer when `write_dir` is given -- sees every pair
@@ -174,7 +175,9 @@ def run_sequence(net, frames_fn: Callable[[int, int], torch.Tensor], n_frames: i
     estimated; nothing synchronises the host with the compute stream inside the loop (the estimation time is taken with events);
     finished chunks leave through a pinned ring on a copy stream and a sink thread.  Returns timing / count statistics of this rank.
     `stats` (a pivlfn.postpro.FlowStats of the flow size): every rank adds the flows of its own pairs right after each estimate, on
-    the compute stream; after the loop, with world > 1, the ranks merge their sums (a collective, whatever `gather` is)."""
+    the compute stream; after the loop, with world > 1, the ranks merge their sums (a collective, whatever `gather` is).
+    `prep` (pivlfn.preproc.Preprocessor, or any callable uint8 [n,H,W,3] -> float32 [n,3,H,W]): converts the frames in place of
+    `frames_to_input`'s division by 255; grey frames are expanded to three channels first, and each frame is still converted once."""
     if n_frames < 2 or chunk < 1:
         raise ValueError("run_sequence: need at least two frames and chunk >= 1")
     n_pairs = n_frames - 1
@@ -224,7 +227,7 @@ def run_sequence(net, frames_fn: Callable[[int, int], torch.Tensor], n_frames: i
                 if halo is not None:
                     fr = torch.cat([halo, fr])
                 halo = fr[-1:].clone()
-                x = frames_to_input(fr)
+                x = frames_to_input(fr, prep)
                 if on_gpu:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()

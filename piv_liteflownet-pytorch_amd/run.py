@@ -3,6 +3,7 @@
 
   python run.py --model piv -i DIR [-i DIR2 ...] -o OUT [-p] [-s N] [-n N] [-b F ...] [-c F ...] [-v 1|2]
                 [--weights FILE] [--batch B] [--stats] [--validate flag|mask|replace]
+                [--background min|FILE] [--minmax K] [--minmax-floor N]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -20,6 +21,9 @@ Differences, all deliberate:
     converted on the device; flows return on a copy stream and a background writer closes the .flo files while the next
     batch computes (pivlfn.pipeline); under torch.distributed.run the pairs are sharded over the ranks
     (pivlfn.dist.shard_bounds);
+  * `--background min|FILE`, `--minmax K`, `--minmax-floor N` pre-process every frame on the device before it is estimated
+    (pivlfn.preproc: background subtraction, sliding min-max normalisation); without them the frames are only divided by 255, as
+    in the reference;
   * a trailing slash on an input directory is ignored (the reference would name the output directory '');
   * with -b/-c a frame whose file name has no '_' gets the tag appended (<stem>_<BBB>_<CCC>_out.flo) -- the reference splits
     the whole path at its last '_' and then either fails or lets the combinations overwrite each other.
@@ -28,6 +32,7 @@ import argparse
 import os
 import sys
 from dataclasses import dataclass
+from types import SimpleNamespace
 from itertools import product
 from typing import List, Optional, Sequence, Tuple
 
@@ -75,6 +80,17 @@ parser.add_argument("--validate-radius", type=int, default=1, help="neighbourhoo
 parser.add_argument("--validate-spacing", type=int, default=1, help="distance in pixels between the neighbours of --validate")
 parser.add_argument("--validate-eps", type=float, default=0.1, help="noise level of --validate in pixels (raise it with the spacing)")
 parser.add_argument("--validate-thresh", type=float, default=2.0, help="normalized residual above which --validate rejects a vector")
+parser.add_argument("--background", type=str, default=None, metavar="min|FILE",
+                    help="subtract a static background from every frame on the device before it is estimated "
+                         "(pivlfn.preproc; not a reference flag; not with -b/-c): 'min' takes the per-pixel minimum over the frames "
+                         "of each input directory first and writes it to <save>/background.png (single process only); FILE is such "
+                         "an image")
+parser.add_argument("--minmax", type=int, default=None, metavar="K",
+                    help="sliding min-max normalisation of every frame over K x K windows, K odd in 3..31, after the background "
+                         "(pivlfn.preproc.preprocess_frames; not with -b/-c)")
+parser.add_argument("--minmax-floor", type=int, default=None, metavar="N",
+                    help="smallest local contrast, in grey levels 1..255, that --minmax stretches to full scale (default 16)")
+PREP_FLAGS = ("background", "minmax", "minmax_floor")
 
 
 @dataclass(frozen=True)
@@ -203,13 +219,70 @@ def write_validation_json(path, est, names):
         f.write("\n")
 
 
+class _SizedPrep:
+    """pivlfn.preproc.Preprocessor that checks the background's size against the first batch and names both sizes if they differ."""
+
+    def __init__(self, background, minmax, floor):
+        from pivlfn.preproc import Preprocessor
+        self.prep, self.checked = Preprocessor(background, minmax, floor), background is None
+
+    def __call__(self, frames):
+        if not self.checked:
+            have, want = tuple(self.prep.background.shape[:2]), tuple(frames.shape[1:3])
+            if have != want:
+                raise SystemExit(f"run.py: --background is {have[0]} x {have[1]} (H x W) but the frames are {want[0]} x {want[1]}")
+            self.checked = True
+        return self.prep(frames)
+
+
+def background_min(ds, device, batch):
+    """The per-pixel minimum over every distinct frame of `ds` (a Run), each decoded once on PairLoader's threads: a
+    pivlfn.preproc.FrameBackground.  All frames must have one size."""
+    from pivlfn.preproc import FrameBackground
+    paths = list(dict.fromkeys(p for pair in ds.image_list for p in pair))
+    odd = len(paths) % 2
+    twos = SimpleNamespace(image_list=[[paths[i], paths[min(i + 1, len(paths) - 1)]] for i in range(0, len(paths), 2)])
+    twos.name_list = [a for a, _ in twos.image_list]
+    loader = PairLoader(twos, 0, len(twos.image_list), batch, depth=2, pin=device.type == "cuda", share=1)
+    bg, seen = None, 0
+    try:
+        for names, a8, b8 in loader:
+            seen += len(names)
+            if odd and seen == len(twos.image_list):
+                b8 = b8[:-1]                        # the last frame of an odd count stands in both places of its pair
+            if bg is None:
+                bg = FrameBackground(a8.size(1), a8.size(2), device)
+            if tuple(a8.shape[1:3]) != (bg.H, bg.W):
+                raise SystemExit(f"run.py: --background min needs frames of one size: '{names[0]}' is {a8.size(1)} x {a8.size(2)} "
+                                 f"(H x W), the frames before it are {bg.H} x {bg.W}")
+            for t in (a8, b8):
+                if t.size(0):
+                    bg.update(t.to(device, non_blocking=True))
+            torch.cuda.current_stream(device).synchronize()      # the loader refills its pinned staging once a batch is consumed
+    except ValueError as e:                         # PairLoader: the two frames of one pair differ in size
+        raise SystemExit(f"run.py: --background min needs frames of one size: {e}")
+    finally:
+        loader.close()
+    assert bg is not None and bg.count == len(paths)
+    return bg
+
+
 def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch, rank=0, world=1, stats_file=None,
-            validate=None, validation_file=None):
+            validate=None, validation_file=None, prep=None, background_file=None):
     """Every pair of the folder through `estimate` (reference main_dl, run.py:137-168); with `stats_file`, FlowStats over the
     pairs go there; with `validate` (the keyword arguments of _ValidateEstimate bar `stats`), every flow goes through
-    validate_flow before it is copied back and the counts go to `validation_file`."""
+    validate_flow before it is copied back and the counts go to `validation_file`.  `prep` = (background, minmax, floor): the
+    frames go through pivlfn.preproc.preprocess_frames; a background of "min" is computed from the folder first and written to
+    `background_file`."""
     os.makedirs(savedir, exist_ok=True)
     ds = Run(root=inputdir, is_pair=is_pair, n_images=num_images, start_at=start_id)
+    if prep is not None:
+        background, minmax, floor = prep
+        if isinstance(background, str):
+            bg = background_min(ds, device, batch)
+            print(f"Background: minimum over {bg.count} frames -> '{bg.save(background_file)}'")
+            background = bg.image()
+        prep = _SizedPrep(background, minmax, floor)
     lo, hi = shard_bounds(len(ds), rank, world)
     print(f"Processing {hi - lo} of {len(ds)} pairs of images (rank {rank}/{world})...")
     loader = PairLoader(ds, lo, hi, batch, depth=2, pin=device.type == "cuda")
@@ -224,7 +297,7 @@ def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch
         writer.submit(flow, flowname_modifier(name, savedir, pair=False))
     try:
         with FloWriter() as writer:
-            n = stream_pairs(net, loader, device, sink, estimate_fn=est)
+            n = stream_pairs(net, loader, device, sink, estimate_fn=est, prep=prep)
     finally:
         loader.close()
     assert n == hi - lo
@@ -285,6 +358,25 @@ def main(argv: Optional[List[str]] = None) -> int:
             check_params(validate["radius"], validate["spacing"], validate["eps"], validate["thresh"], validate["mode"])
         except ValueError as e:
             raise SystemExit(f"run.py: {e}")
+    prep = None
+    if any(getattr(args, k) is not None for k in PREP_FLAGS):
+        if args.brightness is not None or args.contrast is not None:
+            raise SystemExit("run.py: --background / --minmax are not available with -b/-c (every combination is a different "
+                             "experiment)")
+        if args.background == "min" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("run.py: --background min needs a single process (run.py has no process group to merge the minima of "
+                             "the ranks; compute the background once and pass --background FILE)")
+        if args.minmax_floor is not None and args.minmax is None:
+            raise SystemExit("run.py: --minmax-floor needs --minmax")
+        if args.background not in (None, "min") and not os.path.isfile(args.background):
+            raise SystemExit(f"run.py: --background '{args.background}' is neither 'min' nor an image file")
+        from pivlfn.preproc import check_params as check_prep
+        minmax, floor = (0 if args.minmax is None else args.minmax), (16 if args.minmax_floor is None else args.minmax_floor)
+        try:
+            check_prep(minmax, floor)
+        except ValueError as e:
+            raise SystemExit(f"run.py: {e}")
+        prep = (args.background, minmax, floor)
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run.py: this build has no CPU path (the reference's correlation has none either, "
                          "src/correlation.py:339-340); a GPU is required")
@@ -295,6 +387,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     net = Network(model=args.model, params=weights, version=args.version).to(device).eval()
     if args.precision is not None:
         net.precision = args.precision
+    if prep is not None and prep[0] not in (None, "min"):
+        from pivlfn.preproc import FrameBackground
+        prep = (FrameBackground.load(prep[0], device).image(),) + prep[1:]
     mods = None
     if args.brightness is not None or args.contrast is not None:
         mods = list(product(tuple(args.brightness or (1.0,)), tuple(args.contrast or (1.0,))))
@@ -306,15 +401,16 @@ def main(argv: Optional[List[str]] = None) -> int:
         if rank == 0:
             with open(lay.args_file, "w") as f:
                 for k, v in sorted(vars(args).items()):
-                    if validate is None and k.startswith("validate"):
-                        continue                 # without --validate the file is what it was before the flag existed
+                    if (validate is None and k.startswith("validate")) or (prep is None and k in PREP_FLAGS):
+                        continue                 # without these flags the file is what it was before they existed
                     f.write(f"{k}: {v}\n")
         if mods is None:
             stats_file = os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "stats", 1)[:-4] + ".npz") \
                 if args.stats else None          # stats.npz (stats_left / stats_right.npz for the halves of a stereo set)
             validation_file = os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "validation", 1)[:-4] + ".json")
             total += main_dl(net, imdir, lay.flow, args.is_pair, args.start, args.num_images, device, args.batch, rank, world,
-                             stats_file, validate, validation_file)
+                             stats_file, validate, validation_file, prep,
+                             os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "background", 1)[:-4] + ".png"))
         else:
             total += main_mod(net, imdir, lay.flow, args.start, args.num_images, device, mods, args.batch, rank, world)
     print(f"Finish processing {total} flow fields")

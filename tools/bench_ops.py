@@ -295,9 +295,63 @@ def bench_head(args):
     lib.pivlfn_tune(1, 0)
 
 
+HBM_BYTES_PER_S = 8.0e12      # the MI355X's HBM peak the shares below refer to
+
+
+def preproc_hbm_bound_us(n, H, W, background):
+    """The time the algorithmic traffic of pivlfn_frames_preprocess takes at the HBM peak: 3 bytes per pixel read (6 with a
+    background, counted once per frame) and 12 written."""
+    return ((6 if background else 3) + 12) * n * H * W / HBM_BYTES_PER_S * 1e6
+
+
+def bench_preproc(args):
+    """pivlfn_frames_preprocess (csrc/preproc.hip) on particle-like frames with a background: n = 2 and 16 frames of --size squared,
+    k = 0, 15, 31; and pivlfn_frames_background_min over 16 frames.  Beside each time its share of the HBM bound.  `--once`: one
+    launch per shape and nothing else, for a kernel trace (rocprofv3 --kernel-trace --stats -- python tools/bench_ops.py preproc
+    --once)."""
+    from pivlfn import _lib
+    lib = _lib.load()                      # no knobs: the production library
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream(dev).cuda_stream
+    S = args.size
+    g = torch.Generator().manual_seed(1)
+    sparse = (torch.rand(16, S, S, 3, generator=g) < 0.05).to(torch.uint8) * torch.randint(60, 200, (16, S, S, 3), generator=g, dtype=torch.uint8)
+    bg = torch.randint(0, 56, (S, S, 3), generator=g, dtype=torch.uint8)
+    frames = (sparse + bg[None]).to(dev)
+    bg = bg.to(dev)
+    for n in (2, 16):
+        out = torch.empty(n, 3, S, S, device=dev)
+        for k in (0, 15, 31):
+            def fn(k=k, n=n, out=out):
+                _lib.check(lib.pivlfn_frames_preprocess(frames.data_ptr(), bg.data_ptr(), out.data_ptr(), n, S, S, k, 16, st), "preproc")
+            bound = preproc_hbm_bound_us(n, S, S, True)
+            if args.once:
+                fn()
+                torch.cuda.synchronize()
+                print(f"preprocess n={n:2d} {S}x{S} k={k:2d}: HBM bound {bound:7.1f} us", flush=True)
+                continue
+            tmin, tmed = time_it(fn, n=20, rounds=5)
+            print(f"preprocess n={n:2d} {S}x{S} k={k:2d}: min {tmin:8.1f} us  med {tmed:8.1f} us  {tmed / n:7.1f} us/frame  "
+                  f"HBM bound {bound:7.1f} us = {100 * bound / tmed:5.1f} % of the time", flush=True)
+    acc = torch.full((S, S, 3), 255, dtype=torch.uint8, device=dev)
+
+    def fn_bg():
+        _lib.check(lib.pivlfn_frames_background_min(frames.data_ptr(), acc.data_ptr(), 16, S, S, st), "background_min")
+    bound = (16 * 3 + 6) * S * S / HBM_BYTES_PER_S * 1e6
+    if args.once:
+        fn_bg()
+        torch.cuda.synchronize()
+        print(f"background_min n=16 {S}x{S}: HBM bound {bound:7.1f} us", flush=True)
+    else:
+        tmin, tmed = time_it(fn_bg, n=20, rounds=5)
+        print(f"background_min n=16 {S}x{S}: min {tmin:8.1f} us  med {tmed:8.1f} us  HBM bound {bound:7.1f} us = "
+              f"{100 * bound / tmed:5.1f} % of the time", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head"])
+    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc"])
+    ap.add_argument("--once", action="store_true", help="preproc: one launch per shape, for a kernel trace")
     ap.add_argument("--filter", default="")
     ap.add_argument("--tune3", type=int, default=0, help="ablation mask of the fp16 conv kernel (pivlfn_tune(3, mask))")
     ap.add_argument("--tune7", type=int, default=0, help="ablation mask of the fp32 conv kernel in a -DPIVLFN_STAMPS build (pivlfn_tune(7, mask))")
@@ -309,4 +363,5 @@ if __name__ == "__main__":
     ap.add_argument("--masks", default="0,8,1,2,4,3,7", help="wc_ablate: pivlfn_tune(2, .) masks")
     ap.add_argument("--rounds", type=int, default=8, help="interleaved timing rounds per variant (warp_corr)")
     a = ap.parse_args()
-    {"conv_stamps": bench_conv_stamps, "warp_corr": bench_warp_corr, "wc_ablate": bench_wc_ablate, "conv": bench_conv, "head": bench_head}[a.what](a)
+    {"conv_stamps": bench_conv_stamps, "warp_corr": bench_warp_corr, "wc_ablate": bench_wc_ablate, "conv": bench_conv, "head": bench_head,
+     "preproc": bench_preproc}[a.what](a)
