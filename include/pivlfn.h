@@ -200,6 +200,46 @@ int pivlfn_frames_preprocess(const unsigned char *frames, const unsigned char *b
  * overlapping frames. */
 int pivlfn_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, void *stream);
 
+/* ---- scoring of flows against a known field: the sums behind the reference's src/loss.py (EPE :12-21, L1 :24-38, L2 :41-55, the
+ * evaluation branch of MultiScale :144-148, LevelLoss :151-190), per pair.  Added without an ABI bump (additive).
+ * flow: NCHW [B,2,h,w] fp32;  truth: NCHW [B,2,H,W] fp32;  mask: [B,H,W] bytes or NULL, nonzero = leave out;  k: pool exponent 0..5,
+ * h = H >> k, w = W >> k, H and W multiples of 2^k;  sums: [B,7] fp64;  err_map: NCHW [B,3,h,w] fp32 or NULL;  workspace: 8-byte
+ * aligned, at least pivlfn_flow_errors_workspace_bytes(B,H,W) bytes, needs no initial contents.  Launches only on `stream`, no
+ * allocation, no host synchronisation, no floating-point atomics.
+ * Arithmetic contract, all fp64, every operation rounded on its own (no fma):
+ *   pooled truth:  k steps of a 2 x 2 tree on the fp32 values widened to fp64; one step is (a + b) + (c + d), a, b the upper row and
+ *                  c, d the lower row of the window;  P = (tree / 4^k) * div_flow  (nn.AvgPool2d(2^k) of div_flow * truth up to rounding).
+ *   per pixel:     du = (double)flow_u - P_u, dv likewise;  sq = du*du + dv*dv;  epe = sqrt(sq);  l1 = fabs(du) + fabs(dv).
+ *   excluded:      a pixel whose 2^k x 2^k truth window holds an unknown value (NaN or fabs(x) > 1e9f, in u or v: the rule of
+ *                  pivlfn_flow_validate) or a nonzero mask byte.  It is +0.0 in every sum and absent from the count and the maximum;
+ *                  its terms do not enter a sum (no 0 * NaN).  A non-finite *estimated* flow is not excluded: the sums turn non-finite.
+ *   sums[b] = (n, sum l1, sum epe, sum sq, sum du, sum dv, max epe).  Each sum is the root of the same 2 x 2 tree continued over the
+ *                  h x w term map until 1 x 1; a map with an odd size is padded with +0.0 on the bottom / right at that step; the
+ *                  root + 0.0 is reported (a sum of -0.0 reads +0.0, so further zero padding never shows).  The order is fixed by
+ *                  this contract and not by the launch geometry: a pair gives the same bits alone or inside any batch, and from
+ *                  run to run.  n is exact.  The maximum is 0 when n = 0 and NaN when an included epe is NaN.
+ *   err_map:       planes du, dv, epe, each rounded once from fp64; NaN in all three where the pixel is excluded.
+ * Errors (PIVLFN_ERR_ARG, before any launch): null flow / truth / sums / workspace, a non-positive size, k outside 0..5, H or W not
+ * a multiple of 2^k, H*W >= 2^31, B > 65535, a non-finite div_flow, a misaligned or too-small workspace. */
+size_t pivlfn_flow_errors_workspace_bytes(int B, int H, int W);
+int pivlfn_flow_errors(const float *flow, const float *truth, const unsigned char *mask, int B, int H, int W, int k,
+                       double div_flow, double *sums, float *err_map, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- pivlfn_flow_errors for every flow pivlfn_forward writes into `levels` (coarsest level first, M, S, R per level, packed back to
+ * back), in one pass over the truth: sums [B, nlev, 3, 7] fp64, nlev = 7 - lowest_level, entry [b, i, s] = the sums of stage s of
+ * level L = 6 - i scored with k = L - 1.  Bit-identical to nlev * 3 calls of pivlfn_flow_errors.  H and W must be multiples of 32.
+ * Errors: as pivlfn_flow_errors, and lowest_level outside 1..6. */
+int pivlfn_level_errors(const float *levels, int lowest_level, const float *truth, const unsigned char *mask, int B, int H, int W,
+                        double div_flow, double *sums, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- streaming per-pixel error statistics of a sequence: acc [6,H,W] fp64 += the per-pixel sums, in this order, of 1, du, dv, du*du,
+ * dv*dv, epe over the B frames of flow against truth (both NCHW [B,2,H,W] fp32; k = 0, div_flow = 1; du, dv, epe as above), a frame
+ * left out at a pixel where its truth is unknown or its mask byte (mask [B,H,W] or NULL) is nonzero.  Each pixel adds the frames in
+ * frame order to the value acc held before the call (acc is read and written once per call): any split of a sequence into calls
+ * gives the same bits.  Errors (PIVLFN_ERR_ARG): null flow / truth / acc, a non-positive size, H*W >= 2^31. */
+int pivlfn_error_stats_accumulate(const float *flow, const float *truth, const unsigned char *mask, double *acc, int B, int H, int W,
+                                  void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

@@ -173,6 +173,27 @@ int pivlfn_frames_preprocess(const unsigned char *frames, const unsigned char *b
     return launch_frames_preprocess(frames, bg, out, n, H, W, k, floor, (hipStream_t)stream);
 }
 
+size_t pivlfn_flow_errors_workspace_bytes(int B, int H, int W) { return flow_errors_workspace_bytes(B, H, W); }
+
+int pivlfn_flow_errors(const float *flow, const float *truth, const unsigned char *mask, int B, int H, int W, int k, double div_flow,
+                       double *sums, float *err_map, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return launch_flow_errors(flow, truth, mask, B, H, W, k, div_flow, sums, err_map, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int pivlfn_level_errors(const float *levels, int lowest_level, const float *truth, const unsigned char *mask, int B, int H, int W,
+                        double div_flow, double *sums, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return launch_level_errors(levels, lowest_level, truth, mask, B, H, W, div_flow, sums, workspace, workspace_bytes,
+                               (hipStream_t)stream);
+}
+
+int pivlfn_error_stats_accumulate(const float *flow, const float *truth, const unsigned char *mask, double *acc, int B, int H, int W,
+                                  void *stream)
+{
+    return launch_error_stats(flow, truth, mask, acc, B, H, W, (hipStream_t)stream);
+}
+
 int pivlfn_create(const pivlfn_tensor *tensors, int n_tensors, float starting_scale, int lowest_level,
                   const float rgb_mean[6], pivlfn_net **out)
 {

@@ -260,6 +260,14 @@ int launch_flow_stats_masked(const float *flow, const unsigned char *flag, doubl
 int launch_flow_validate(const float *flow, float *out, unsigned char *flag, float *resid, int B, int H, int W, int radius,
                          int spacing, float eps, float thresh, int mode, hipStream_t st);
 
+// ---- scoring against a known field (evaluate.hip): [B,2,h,w] NCHW flows, [B,2,H,W] truth, mask [B,H,W] bytes or nullptr ------------
+size_t flow_errors_workspace_bytes(int B, int H, int W);
+int launch_flow_errors(const float *flow, const float *truth, const unsigned char *mask, int B, int H, int W, int k, double div_flow,
+                       double *sums, float *err_map, void *ws, size_t ws_bytes, hipStream_t st);
+int launch_level_errors(const float *levels, int lowest_level, const float *truth, const unsigned char *mask, int B, int H, int W,
+                        double div_flow, double *sums, void *ws, size_t ws_bytes, hipStream_t st);
+int launch_error_stats(const float *flow, const float *truth, const unsigned char *mask, double *acc, int B, int H, int W, hipStream_t st);
+
 // ---- image pre-processing (preproc.hip): [n,H,W,3] uint8 frames -> background minimum [H,W,3], network input [n,3,H,W] fp32 --------
 int launch_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, hipStream_t st);
 int launch_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W, int k, int floor,

@@ -11,7 +11,8 @@ from .inference import Inference, estimate                               # noqa:
 from .stereo import estimate_stereo                                      # noqa: F401
 from .validate import MaskedFlowStats, validate_flow                     # noqa: F401
 from .preproc import FrameBackground, preprocess_frames                  # noqa: F401
+from .evaluate import ErrorStats, FlowErrors, flow_errors, level_errors  # noqa: F401
 
 __all__ = ["FunctionCorrelation", "ModuleCorrelation", "LiteFlowNet", "LiteFlowNet2", "Network", "backwarp",
            "hui_liteflownet", "piv_liteflownet", "estimate", "Inference", "estimate_stereo", "validate_flow", "MaskedFlowStats",
-           "preprocess_frames", "FrameBackground"]
+           "preprocess_frames", "FrameBackground", "flow_errors", "level_errors", "FlowErrors", "ErrorStats"]

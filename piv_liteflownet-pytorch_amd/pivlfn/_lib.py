@@ -42,6 +42,12 @@ SIGNATURES = {
     "pivlfn_flow_stats_accumulate_masked": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_double, ctypes.c_void_p]),
     "pivlfn_frames_background_min": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
     "pivlfn_frames_preprocess": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    "pivlfn_flow_errors_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "pivlfn_flow_errors": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_double] + [ctypes.c_void_p] * 3
+                           + [ctypes.c_size_t, ctypes.c_void_p]),
+    "pivlfn_level_errors": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_double]
+                            + [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "pivlfn_error_stats_accumulate": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
     "pivlfn_create": (ctypes.c_int, [ctypes.POINTER(Tensor), ctypes.c_int, ctypes.c_float, ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_void_p)]),
     "pivlfn_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "pivlfn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_void_p] + [ctypes.c_int] * 3),

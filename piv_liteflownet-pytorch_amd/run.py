@@ -3,7 +3,7 @@
 
   python run.py --model piv -i DIR [-i DIR2 ...] -o OUT [-p] [-s N] [-n N] [-b F ...] [-c F ...] [-v 1|2]
                 [--weights FILE] [--batch B] [--stats] [--validate flag|mask|replace]
-                [--background min|FILE] [--minmax K] [--minmax-floor N]
+                [--background min|FILE] [--minmax K] [--minmax-floor N] [--truth DIR [--truth-levels]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -24,6 +24,9 @@ Differences, all deliberate:
   * `--background min|FILE`, `--minmax K`, `--minmax-floor N` pre-process every frame on the device before it is estimated
     (pivlfn.preproc: background subtraction, sliding min-max normalisation); without them the frames are only divided by 255, as
     in the reference;
+  * `--truth DIR` scores every flow against the known field DIR/<name>_flow.flo on the device before it is copied back
+    (pivlfn.evaluate: AEE, RMSE, L1, bias and the largest error per pair in <save>/errors.json, per-pixel bias and random-error
+    maps in <save>/error_maps.npz); `--truth-levels` adds the table of pyramid level x stage errors;
   * a trailing slash on an input directory is ignored (the reference would name the output directory '');
   * with -b/-c a frame whose file name has no '_' gets the tag appended (<stem>_<BBB>_<CCC>_out.flo) -- the reference splits
     the whole path at its last '_' and then either fails or lets the combinations overwrite each other.
@@ -90,7 +93,18 @@ parser.add_argument("--minmax", type=int, default=None, metavar="K",
                          "(pivlfn.preproc.preprocess_frames; not with -b/-c)")
 parser.add_argument("--minmax-floor", type=int, default=None, metavar="N",
                     help="smallest local contrast, in grey levels 1..255, that --minmax stretches to full scale (default 16)")
+parser.add_argument("--truth", type=str, default=None, metavar="DIR",
+                    help="score every flow against the known field DIR/<name>_flow.flo (<name>: what the flow file is called without "
+                         "_out.flo) on the device (pivlfn.evaluate; not a reference flag; not with -b/-c; sharded over ranks like the "
+                         "flows, the records meeting on rank 0): writes <save>/errors.json (a value that is not finite, such as the AEE of "
+                         "a pair with nothing to score, is written as null) and <save>/error_maps.npz; with --validate flag|mask the "
+                         "rejected vectors are left out, with --validate replace the replaced flow is scored (--validate itself is "
+                         "single process only)")
+parser.add_argument("--truth-levels", action="store_true",
+                    help="with --truth: also the average end-point error of every pyramid level and stage (M, S, R) in errors.json; "
+                         "the frame sizes must be multiples of 32")
 PREP_FLAGS = ("background", "minmax", "minmax_floor")
+TRUTH_FLAGS = ("truth", "truth_levels")
 
 
 @dataclass(frozen=True)
@@ -178,6 +192,7 @@ class _ValidateEstimate:
         from pivlfn.validate import NOT_REPLACED, OUTLIER, UNKNOWN, MaskedFlowStats, validate_flow
         flow = estimate(net, img1, img2, tensor=True)
         res = validate_flow(flow, mode=self.mode, **self.params)
+        self.last_raw, self.last_flag = flow, res.flag          # what --truth scores for "flag" and "mask"
         flat = res.flag.flatten(1)
         self._counts.append(torch.stack([(flat & bit).ne(0).sum(1) for bit in (OUTLIER, UNKNOWN, NOT_REPLACED)], dim=1))
         if self.want_stats:
@@ -217,6 +232,206 @@ def write_validation_json(path, est, names):
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
+
+
+def truth_files(ds, truth_dir, levels=False):
+    """The truth file of every pair of `ds` (a Run), DIR/<stem>_flow.flo with the stem flowname_modifier gives the flow file.  Every
+    file must exist and have the size of the pair's first frame (a multiple of 32 both ways for `levels`): checked here, from the
+    headers alone, before anything is launched."""
+    import struct
+    import PIL.Image
+    paths = []
+    for name, pair in zip(ds.name_list, ds.image_list):
+        path = flowname_modifier(name, truth_dir, ext="_flow.flo", pair=False)
+        if not os.path.isfile(path):
+            raise SystemExit(f"run.py: --truth: no truth file '{path}' for pair '{name}'")
+        with open(path, "rb") as f:
+            head = f.read(12)
+        if len(head) != 12 or head[:4] != b"PIEH":
+            raise SystemExit(f"run.py: --truth: '{path}' is not a .flo file")
+        w, h = struct.unpack("<ii", head[4:])
+        with PIL.Image.open(pair[0]) as im:
+            fw, fh = im.size
+        if (w, h) != (fw, fh):
+            raise SystemExit(f"run.py: --truth: '{path}' is {h} x {w} (H x W) but the frames of pair '{name}' are {fh} x {fw}")
+        if levels and (fw % 32 or fh % 32):
+            raise SystemExit(f"run.py: --truth-levels needs frame sizes that are multiples of 32, pair '{name}' is {fh} x {fw} (H x W)")
+        paths.append(path)
+    return paths
+
+
+class _TruthPrefetch:
+    """Reads the truth files of the pairs in order on a few threads, `depth` files ahead, each straight from the file into a pinned
+    [H,W,2] float32 tensor (the .flo payload as it is; the headers were checked by truth_files).  A 1024 x 1024 field is 8 MB: one
+    thread going through read_flow, a host transpose and pin_memory() -- four passes over it -- held the fp16 loop back."""
+
+    def __init__(self, paths, pin, depth=8, workers=4):
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+        self.paths, self.pin, self.depth, self.at = list(paths), pin, depth, 0
+        self.pool = ThreadPoolExecutor(max_workers=workers)
+        self.pending = deque()
+        self._fill()
+
+    def _read(self, path):
+        import struct
+        import numpy as np
+        with open(path, "rb") as f:
+            w, h = struct.unpack("<ii", f.read(12)[4:])
+            buf = torch.empty([h, w, 2], dtype=torch.float32, pin_memory=self.pin)
+            got = f.readinto(buf.numpy().reshape(-1).view(np.uint8))      # little-endian float32, the layout of the file
+        if got != buf.numel() * 4:
+            raise SystemExit(f"run.py: --truth: '{path}' holds {got} of {buf.numel() * 4} payload bytes")
+        return buf
+
+    def _fill(self):
+        while len(self.pending) < self.depth and self.at < len(self.paths):
+            self.pending.append(self.pool.submit(self._read, self.paths[self.at]))
+            self.at += 1
+
+    def take(self, n):
+        out = []
+        for _ in range(n):
+            out.append(self.pending.popleft().result())
+            self._fill()
+        return out
+
+    def close(self):
+        for f in self.pending:
+            f.cancel()
+        self.pool.shutdown(wait=True)
+
+
+class _LevelsNet:
+    """Stands in for the network inside estimate(): the same forward, with the per-level flows of the last call kept."""
+
+    def __init__(self, net):
+        self.net, self.training, self.levels = net, False, None
+
+    def eval(self):
+        return self
+
+    def __call__(self, a, b):
+        out, self.levels = self.net.forward_levels(a, b)
+        return out
+
+
+class _TruthEstimate:
+    """An estimate_fn (plain estimate() when `inner` is None) whose flows are scored against the next truth fields on the device before
+    they are returned: per-pair sums (pivlfn.evaluate.flow_errors) stay on the device until records() copies them once, and an
+    ErrorStats collects the per-pixel maps.  With a _ValidateEstimate inside, "flag" and "mask" score the raw flow with the flags
+    as the mask, "replace" scores the replaced flow.  `levels`: also level_errors on the per-level flows of the same forward."""
+
+    def __init__(self, paths, inner, levels, div_flow, pin):
+        self.inner, self.levels, self.div_flow = inner, levels, div_flow
+        self.prefetch = _TruthPrefetch(paths, pin)
+        self.copy = None                                        # the truth goes up on its own stream, under the forward
+        self.stats = None
+        self._sums, self._excluded, self._level_sums = [], [], []
+
+    def __call__(self, net, img1, img2, tensor=True):
+        from pivlfn.evaluate import ErrorStats, flow_errors, level_errors
+        from pivlfn.inference import estimate
+        dev = img1.device
+        main = torch.cuda.current_stream(dev)
+        if self.copy is None:
+            self.copy = torch.cuda.Stream(dev)
+        with torch.cuda.stream(self.copy):
+            raw = torch.stack([t.to(dev, non_blocking=True) for t in self.prefetch.take(img1.size(0))])        # [n,H,W,2]
+        run_net = _LevelsNet(net) if self.levels else net
+        flow = estimate(run_net, img1, img2, tensor=True) if self.inner is None else self.inner(run_net, img1, img2, tensor=True)
+        main.wait_stream(self.copy)
+        raw.record_stream(main)
+        truth = raw.permute(0, 3, 1, 2).contiguous()
+        scored, mask = flow, None
+        mode = getattr(self.inner, "mode", None)
+        if mode in ("flag", "mask"):
+            scored, mask = self.inner.last_raw, self.inner.last_flag
+            self._excluded.append(mask.flatten(1).ne(0).sum(1))
+        err = flow_errors(scored, truth, mask)
+        self._sums.append(torch.stack(list(err[:7]), dim=1))
+        if self.stats is None:
+            self.stats = ErrorStats(flow.size(2), flow.size(3), device=dev)
+        self.stats.update(scored, truth, mask)
+        if self.levels:
+            table = level_errors(net, run_net.levels, truth, self.div_flow, mask)
+            self._level_sums.append(torch.stack([torch.stack([torch.stack(list(e[:7]), dim=1) for e in row], dim=1) for row in table],
+                                                dim=1))
+        return flow
+
+    def close(self):
+        self.prefetch.close()
+
+    def records(self):
+        """([pairs,7] float64 sums, [pairs] excluded counts or None, [pairs,nlev,3,7] level sums or None), on the host."""
+        cat = lambda parts: torch.cat(parts).cpu() if parts else None      # noqa: E731
+        return cat(self._sums), cat(self._excluded), cat(self._level_sums)
+
+
+def write_errors_json(path, names, sums, excluded, levels, mode, div_flow):
+    """<save>/errors.json: per pair name n, aee, rmse, l1, bias_u, bias_v, max (pixels; null where the value is not finite: nothing
+    scored, or a non-finite estimated flow); the totals over the run, formed from the per-pair sums in pair order; with --validate flag|mask the vectors left out; with --truth-levels the level x stage AEE tables.
+    sums [pairs,7], excluded [pairs] or None, levels [pairs,nlev,3,7] or None: host tensors (_TruthEstimate.records)."""
+    import json
+    import math
+    rows = sums.tolist() if sums is not None else []
+    assert len(rows) == len(names)
+
+    def record(s):
+        n = s[0]
+        div = (lambda x: x / n) if n else (lambda x: float("nan"))
+        return {"n": int(n), "aee": div(s[2]), "rmse": math.sqrt(div(s[3])) if n else float("nan"), "l1": div(s[1]) / 2.0,
+                "bias_u": div(s[4]), "bias_v": div(s[5]), "max": s[6]}
+    total = [0.0] * 7
+    for s in rows:                  # the largest error of the run is NaN if a pair's is (Python's max would drop it)
+        total = [a + b for a, b in zip(total[:6], s[:6])] + [s[6] if s[6] != s[6] or s[6] > total[6] else total[6]]
+    doc = {"pairs": {name: record(s) for name, s in zip(names, rows)}, "total": record(total)}
+    if excluded is not None:
+        ex = excluded.tolist()
+        doc["validate"] = mode
+        doc["excluded"] = {"pairs": dict(zip(names, ex)), "total": sum(ex)}
+    if levels is not None:
+        tot = levels[0].clone()
+        for s in levels[1:]:
+            tot += s                                            # the pairs' sums in pair order
+        aee = (tot[:, :, 2] / tot[:, :, 0]).tolist()            # [nlev][3] in level units (flow * div_flow at that level's resolution)
+        doc["levels"] = {"div_flow": div_flow, "stages": ["M", "S", "R"], "levels": [6 - i for i in range(len(aee))],
+                         "aee_level_units": aee, "aee_px": [[v / div_flow for v in row] for row in aee]}
+    def strict(x):                  # JSON has no NaN or Infinity: null stands for every value that is not finite
+        if isinstance(x, dict):
+            return {k: strict(v) for k, v in x.items()}
+        if isinstance(x, list):
+            return [strict(v) for v in x]
+        return None if isinstance(x, float) and not math.isfinite(x) else x
+    with open(path, "w") as f:
+        json.dump(strict(doc), f, indent=1, allow_nan=False)
+        f.write("\n")
+
+
+def finish_truth(scorer, names, errors_file, maps_file, rank, world, device):
+    """Writes errors.json and error_maps.npz.  Sharded runs (world > 1, a process group exists): the per-pair records of all ranks
+    are gathered in rank order -- the shards are contiguous, so that is pair order -- the maps are merged (ErrorStats.merge), and
+    rank 0 writes."""
+    sums, excluded, levels = scorer.records()
+    mode = getattr(scorer.inner, "mode", None)
+    size = None if scorer.stats is None else (scorer.stats.H, scorer.stats.W)
+    if world > 1:
+        import torch.distributed as dist
+        from pivlfn.evaluate import ErrorStats
+        parts = [None] * world
+        dist.all_gather_object(parts, (names, sums, excluded, levels, size))
+        names = [n for p in parts for n in p[0]]
+        sums, excluded, levels = (torch.cat([p[i] for p in parts if p[i] is not None]) if any(p[i] is not None for p in parts) else None
+                                  for i in (1, 2, 3))
+        size = next((p[4] for p in parts if p[4] is not None), None)
+        if size is not None:
+            if scorer.stats is None:                            # a rank without pairs still takes part in the merge
+                scorer.stats = ErrorStats(size[0], size[1], device=device)
+            scorer.stats.merge()
+    if rank == 0:
+        write_errors_json(errors_file, names, sums, excluded, levels, mode, scorer.div_flow)
+        if scorer.stats is not None and scorer.stats.count > 0:
+            scorer.stats.save(maps_file)
 
 
 class _SizedPrep:
@@ -268,14 +483,19 @@ def background_min(ds, device, batch):
 
 
 def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch, rank=0, world=1, stats_file=None,
-            validate=None, validation_file=None, prep=None, background_file=None):
+            validate=None, validation_file=None, prep=None, background_file=None, truth=None):
     """Every pair of the folder through `estimate` (reference main_dl, run.py:137-168); with `stats_file`, FlowStats over the
     pairs go there; with `validate` (the keyword arguments of _ValidateEstimate bar `stats`), every flow goes through
     validate_flow before it is copied back and the counts go to `validation_file`.  `prep` = (background, minmax, floor): the
     frames go through pivlfn.preproc.preprocess_frames; a background of "min" is computed from the folder first and written to
-    `background_file`."""
+    `background_file`.  `truth` = (directory or the truth_files() list of it, levels, errors file, maps file): every flow is scored against its truth file
+    (_TruthEstimate)."""
     os.makedirs(savedir, exist_ok=True)
     ds = Run(root=inputdir, is_pair=is_pair, n_images=num_images, start_at=start_id)
+    truth_paths = None
+    if truth is not None:          # a list: main() has checked these files already; a directory: check them now
+        truth_paths = truth_files(ds, truth[0], truth[1]) if isinstance(truth[0], str) else list(truth[0])
+        assert len(truth_paths) == len(ds)
     if prep is not None:
         background, minmax, floor = prep
         if isinstance(background, str):
@@ -290,6 +510,10 @@ def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch
         est = _ValidateEstimate(stats=stats_file is not None, **validate)
     else:
         est = _StatsEstimate() if stats_file is not None else None
+    scorer = None
+    if truth is not None:
+        scorer = _TruthEstimate(truth_paths[lo:hi], est, truth[1], 1.0 / (5.0 if net.starting_scale == 10 else 20.0),
+                                pin=device.type == "cuda")
     seen = []
 
     def sink(flow, name):
@@ -297,10 +521,14 @@ def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch
         writer.submit(flow, flowname_modifier(name, savedir, pair=False))
     try:
         with FloWriter() as writer:
-            n = stream_pairs(net, loader, device, sink, estimate_fn=est, prep=prep)
+            n = stream_pairs(net, loader, device, sink, estimate_fn=scorer if scorer is not None else est, prep=prep)
     finally:
         loader.close()
+        if scorer is not None:
+            scorer.close()
     assert n == hi - lo
+    if scorer is not None:
+        finish_truth(scorer, seen, truth[2], truth[3], rank, world, device)
     if validate is not None:
         write_validation_json(validation_file, est, seen)
         if est.stats is not None:
@@ -358,6 +586,16 @@ def main(argv: Optional[List[str]] = None) -> int:
             check_params(validate["radius"], validate["spacing"], validate["eps"], validate["thresh"], validate["mode"])
         except ValueError as e:
             raise SystemExit(f"run.py: {e}")
+    if args.truth_levels and args.truth is None:
+        raise SystemExit("run.py: --truth-levels needs --truth")
+    if args.truth is not None:
+        if args.brightness is not None or args.contrast is not None:
+            raise SystemExit("run.py: --truth is not available with -b/-c (every combination is a different experiment)")
+        if not os.path.isdir(args.truth):
+            raise SystemExit(f"run.py: --truth '{args.truth}' is not a directory")
+        # every truth file of every directory, before the first forward
+        truth_paths = {imdir: truth_files(Run(root=imdir, is_pair=args.is_pair, n_images=args.num_images, start_at=args.start),
+                                          args.truth, args.truth_levels) for imdir in args.input}
     prep = None
     if any(getattr(args, k) is not None for k in PREP_FLAGS):
         if args.brightness is not None or args.contrast is not None:
@@ -383,6 +621,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())   # ranks may share a card
     torch.cuda.set_device(device)
+    if args.truth is not None and world > 1:        # the ranks' records and maps meet on rank 0: a small host-side exchange
+        import torch.distributed as dist
+        if not dist.is_initialized():
+            dist.init_process_group("gloo", rank=rank, world_size=world)
     weights, netname = load_weights(args)
     net = Network(model=args.model, params=weights, version=args.version).to(device).eval()
     if args.precision is not None:
@@ -401,7 +643,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         if rank == 0:
             with open(lay.args_file, "w") as f:
                 for k, v in sorted(vars(args).items()):
-                    if (validate is None and k.startswith("validate")) or (prep is None and k in PREP_FLAGS):
+                    if (validate is None and k.startswith("validate")) or (prep is None and k in PREP_FLAGS) or \
+                            (args.truth is None and k in TRUTH_FLAGS):
                         continue                 # without these flags the file is what it was before they existed
                     f.write(f"{k}: {v}\n")
         if mods is None:
@@ -410,9 +653,17 @@ def main(argv: Optional[List[str]] = None) -> int:
             validation_file = os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "validation", 1)[:-4] + ".json")
             total += main_dl(net, imdir, lay.flow, args.is_pair, args.start, args.num_images, device, args.batch, rank, world,
                              stats_file, validate, validation_file, prep,
-                             os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "background", 1)[:-4] + ".png"))
+                             os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "background", 1)[:-4] + ".png"),
+                             None if args.truth is None else
+                             (truth_paths[imdir], args.truth_levels,
+                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "errors", 1)[:-4] + ".json"),
+                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "error_maps", 1)[:-4] + ".npz")))
         else:
             total += main_mod(net, imdir, lay.flow, args.start, args.num_images, device, mods, args.batch, rank, world)
+    if args.truth is not None and world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
     print(f"Finish processing {total} flow fields")
     return total
 

@@ -348,9 +348,48 @@ def bench_preproc(args):
               f"{100 * bound / tmed:5.1f} % of the time", flush=True)
 
 
+def bench_evaluate(args):
+    """pivlfn_flow_errors at 8 x --size squared, k = 0 (with and without the error map), pivlfn_level_errors on the piv pyramid (levels
+    6..1, three stages each) and pivlfn_error_stats_accumulate, on the production library.  Beside each time the share of it that
+    the bytes it must move take at the HBM peak: 8 B of truth and 8 B of flow per pixel (level_errors: the flows of all levels and
+    stages, 3 x 4/3 x 8 B per pixel; the error map adds 12 B; error_stats reads and writes 48 B of sums per pixel and call)."""
+    from pivlfn import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream(dev).cuda_stream
+    B, S = 8, args.size
+    truth = torch.randn(B, 2, S, S, device=dev)
+    flow = truth + 0.1 * torch.randn(B, 2, S, S, device=dev)
+    levels = torch.randn(sum(3 * B * 2 * (S >> k) * (S >> k) for k in range(6)), device=dev)
+    nws = lib.pivlfn_flow_errors_workspace_bytes(B, S, S)
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    sums = torch.empty(B, 6, 3, 7, dtype=torch.float64, device=dev)
+    emap = torch.empty(B, 3, S, S, device=dev)
+    acc = torch.zeros(6, S, S, dtype=torch.float64, device=dev)
+    px = B * S * S
+
+    def fe(m):
+        _lib.check(lib.pivlfn_flow_errors(flow.data_ptr(), truth.data_ptr(), None, B, S, S, 0, 1.0, sums.data_ptr(), m, ws.data_ptr(), nws, st),
+                   "flow_errors")
+
+    def le():
+        _lib.check(lib.pivlfn_level_errors(levels.data_ptr(), 1, truth.data_ptr(), None, B, S, S, 0.2, sums.data_ptr(), ws.data_ptr(), nws, st),
+                   "level_errors")
+
+    def es():
+        _lib.check(lib.pivlfn_error_stats_accumulate(flow.data_ptr(), truth.data_ptr(), None, acc.data_ptr(), B, S, S, st), "error_stats")
+    for name, fn, nbytes in (("flow_errors k=0", lambda: fe(None), 16 * px), ("flow_errors k=0 + err_map", lambda: fe(emap.data_ptr()), 28 * px),
+                             ("level_errors piv (18 flows)", le, 8 * px + 4 * levels.numel()),
+                             ("error_stats_accumulate", es, 16 * px + 96 * S * S)):
+        bound = nbytes / HBM_BYTES_PER_S * 1e6
+        tmin, tmed = time_it(fn, n=20, rounds=5)
+        print(f"{name:28s} B={B} {S}x{S}: min {tmin:8.1f} us  med {tmed:8.1f} us  HBM bound {bound:7.1f} us = "
+              f"{100 * bound / tmed:5.1f} % of the time", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc"])
+    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate"])
     ap.add_argument("--once", action="store_true", help="preproc: one launch per shape, for a kernel trace")
     ap.add_argument("--filter", default="")
     ap.add_argument("--tune3", type=int, default=0, help="ablation mask of the fp16 conv kernel (pivlfn_tune(3, mask))")
@@ -364,4 +403,4 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=8, help="interleaved timing rounds per variant (warp_corr)")
     a = ap.parse_args()
     {"conv_stamps": bench_conv_stamps, "warp_corr": bench_warp_corr, "wc_ablate": bench_wc_ablate, "conv": bench_conv, "head": bench_head,
-     "preproc": bench_preproc}[a.what](a)
+     "preproc": bench_preproc, "evaluate": bench_evaluate}[a.what](a)
