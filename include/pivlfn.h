@@ -240,6 +240,60 @@ int pivlfn_level_errors(const float *levels, int lowest_level, const float *trut
 int pivlfn_error_stats_accumulate(const float *flow, const float *truth, const unsigned char *mask, double *acc, int B, int H, int W,
                                   void *stream);
 
+/* ---- pictures of flows and scalar fields: the reference's motion_to_color (src/utils_plot.py:199-256) with compute_color
+ * (src/utils_color.py:23-93), a colour map for scalar fields, the maxima that normalise both, and cell means for quiver plots.  Added
+ * without an ABI bump (additive).  flow: NCHW [B,2,H,W] fp32;  mask: [B,H,W] bytes or NULL, nonzero = leave out (the flag of
+ * pivlfn_flow_validate);  pictures: packed bytes [B,H,W,3].  Launches only on `stream`, no allocation, no host synchronisation, no
+ * floating-point atomics; no output depends on what it held before the call, and a batch equals its images one at a time.
+ *   unknown(p) = isnan(u) | isnan(v) | fabs(u) > 1e9f | fabs(v) > 1e9f      (the reference's _unknown_flow, as pivlfn_flow_validate)
+ *
+ * pivlfn_flow_maxrad: maxrad[b] (fp32 [B]) = the largest sqrtf(u*u + v*v) over the pixels of image b that are neither unknown nor
+ *   masked, each operation rounded on its own in fp32 (no fma); 0 where nothing is left.  A maximum does not depend on the order it is
+ *   formed in.  The maximum of a batch is the maximum of its entries.
+ *   Deliberate divergence: the reference takes rad.max() over everything, so one 1e10 vector of a masked flow normalises the whole
+ *   picture to white; the Middlebury color_flow.cpp it was adapted from leaves unknown flow out, and so does this.  Without unknown
+ *   vectors the two agree bit for bit.
+ *
+ * pivlfn_flow_to_color: norm: fp32 [B] on the device, one normaliser per image (an entry of maxrad, the batch maximum or a fixed
+ *   value); n = (norm[b] == 0 ? 1 : norm[b]).  Per pixel, in the types NumPy uses in the reference for float32 flows:
+ *     fp32, every operation rounded on its own, both divisions IEEE (no reciprocal):
+ *       fx = u / n;  fy = v / n;  rad = sqrtf(fx*fx + fy*fy);  a = atan2f(-fy, -fx) / (float)pi;  fk = (a + 1) / 2 * 54
+ *       k0 = (int)fk (truncated, 0..54);  k1 = (k0 + 1) % 55
+ *     fp64:  f = (double)fk - k0 (WHEEL_INTERP) or 0 (WHEEL_ORIGINAL);  per channel c of the 55-entry wheel T = colorwheel / 255.0:
+ *       col = (1 - f) * T[k0][c] + f * T[k1][c];   rad <= 1: col = 1 - (double)rad * (1 - col);   rad > 1: col = col * 0.75
+ *       byte = (int)(255.0 * col), truncated.
+ *   ORDER_BGR stores the wheel's (r, g, b) as the reference does (colim[..., 2 - c]); ORDER_RGB stores r, g, b.  Unknown and masked
+ *   pixels are 0, 0, 0.  atan2f is the device library's: its last-bit differences from another libm move a byte by at most one
+ *   level; signed zeros are honoured (a = -1 for (1, +0.0) is wheel entry 0, a = +1 for (1, -0.0) is entry 54).
+ *
+ * pivlfn_field_absmax: absmax[b] (fp64 [B]) = the largest fabs(x) over the finite, unmasked values of image b of field ([B,H,W] fp32,
+ *   or fp64 with is_f64 = 1), exact; 0 where nothing is left.
+ *
+ * pivlfn_scalar_to_color: field as above;  lut: 256 x 3 bytes (r, g, b) on the device;  scale = 256.0 / (vmax - vmin), formed once
+ *   on the host;  idx = floor(((double)x - vmin) * scale) in fp64, two operations each rounded on its own, clamped to 0..255;  the
+ *   pixel is lut[idx].  A non-finite x or a masked pixel is bad_rgb (0xRRGGBB).  vmax < vmin reverses the map.
+ *
+ * pivlfn_flow_decimate: mean: NCHW [B,2,ch,cw] fp32, count: [B,ch,cw] int32, ch = ceil(H / cell), cw = ceil(W / cell).  Cell (i, j)
+ *   covers rows i*cell .. min(H, (i+1)*cell) - 1 and the columns likewise (a ragged last cell averages what it has).  The vectors of
+ *   a cell that are neither unknown nor masked are added in row-major order in fp64, from +0.0;  mean = (float)(sum / (double)count);
+ *   an empty cell is 1e10f in both components with count 0.
+ *
+ * Errors (PIVLFN_ERR_ARG, before any launch): a null pointer other than mask, a non-positive size, H*W >= 2^31, B > 65535, an unknown
+ * wheel or order, is_f64 not 0 / 1, non-finite or equal vmin and vmax (or a range so narrow that scale overflows), bad_rgb outside
+ * 0..0xFFFFFF, cell outside 1..32768. */
+#define PIVLFN_WHEEL_INTERP   0
+#define PIVLFN_WHEEL_ORIGINAL 1
+#define PIVLFN_ORDER_RGB      0
+#define PIVLFN_ORDER_BGR      1
+int pivlfn_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, void *stream);
+int pivlfn_flow_to_color(const float *flow, const float *norm, const unsigned char *mask, unsigned char *out, int B, int H, int W,
+                         int wheel, int order, void *stream);
+int pivlfn_field_absmax(const void *field, int is_f64, const unsigned char *mask, double *absmax, int B, int H, int W, void *stream);
+int pivlfn_scalar_to_color(const void *field, int is_f64, const unsigned char *mask, const unsigned char *lut, unsigned char *out,
+                           int B, int H, int W, double vmin, double vmax, int bad_rgb, void *stream);
+int pivlfn_flow_decimate(const float *flow, const unsigned char *mask, float *mean, int *count, int B, int H, int W, int cell,
+                         void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

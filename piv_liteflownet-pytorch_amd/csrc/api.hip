@@ -194,6 +194,34 @@ int pivlfn_error_stats_accumulate(const float *flow, const float *truth, const u
     return launch_error_stats(flow, truth, mask, acc, B, H, W, (hipStream_t)stream);
 }
 
+int pivlfn_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, void *stream)
+{
+    return launch_flow_maxrad(flow, mask, maxrad, B, H, W, (hipStream_t)stream);
+}
+
+int pivlfn_flow_to_color(const float *flow, const float *norm, const unsigned char *mask, unsigned char *out, int B, int H, int W,
+                         int wheel, int order, void *stream)
+{
+    return launch_flow_to_color(flow, norm, mask, out, B, H, W, wheel, order, (hipStream_t)stream);
+}
+
+int pivlfn_field_absmax(const void *field, int is_f64, const unsigned char *mask, double *absmax, int B, int H, int W, void *stream)
+{
+    return launch_field_absmax(field, is_f64, mask, absmax, B, H, W, (hipStream_t)stream);
+}
+
+int pivlfn_scalar_to_color(const void *field, int is_f64, const unsigned char *mask, const unsigned char *lut, unsigned char *out, int B,
+                           int H, int W, double vmin, double vmax, int bad_rgb, void *stream)
+{
+    return launch_scalar_to_color(field, is_f64, mask, lut, out, B, H, W, vmin, vmax, bad_rgb, (hipStream_t)stream);
+}
+
+int pivlfn_flow_decimate(const float *flow, const unsigned char *mask, float *mean, int *count, int B, int H, int W, int cell,
+                         void *stream)
+{
+    return launch_flow_decimate(flow, mask, mean, count, B, H, W, cell, (hipStream_t)stream);
+}
+
 int pivlfn_create(const pivlfn_tensor *tensors, int n_tensors, float starting_scale, int lowest_level,
                   const float rgb_mean[6], pivlfn_net **out)
 {

@@ -268,6 +268,16 @@ int launch_level_errors(const float *levels, int lowest_level, const float *trut
                         double div_flow, double *sums, void *ws, size_t ws_bytes, hipStream_t st);
 int launch_error_stats(const float *flow, const float *truth, const unsigned char *mask, double *acc, int B, int H, int W, hipStream_t st);
 
+// ---- pictures (viz.hip): [B,2,H,W] NCHW flows or [B,H,W] fields -> packed bytes [B,H,W,3]; mask [B,H,W] bytes or nullptr ------------
+int launch_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, hipStream_t st);
+int launch_flow_to_color(const float *flow, const float *norm, const unsigned char *mask, unsigned char *out, int B, int H, int W,
+                         int wheel, int order, hipStream_t st);
+int launch_field_absmax(const void *field, int is_f64, const unsigned char *mask, double *absmax, int B, int H, int W, hipStream_t st);
+int launch_scalar_to_color(const void *field, int is_f64, const unsigned char *mask, const unsigned char *lut, unsigned char *out, int B,
+                           int H, int W, double vmin, double vmax, int bad_rgb, hipStream_t st);
+int launch_flow_decimate(const float *flow, const unsigned char *mask, float *mean, int *count, int B, int H, int W, int cell,
+                         hipStream_t st);
+
 // ---- image pre-processing (preproc.hip): [n,H,W,3] uint8 frames -> background minimum [H,W,3], network input [n,3,H,W] fp32 --------
 int launch_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, hipStream_t st);
 int launch_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W, int k, int floor,

@@ -170,7 +170,8 @@ class PairLoader:
 def stream_pairs(net, loader: PairLoader, device: torch.device, sink: Callable[..., None],
                  estimate_fn: Optional[Callable] = None, in_flight: int = 3,
                  mods: Optional[Sequence[Tuple[float, float]]] = None, group: int = 1,
-                 prep: Optional[Callable[[torch.Tensor], torch.Tensor]] = None) -> int:
+                 prep: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
+                 extras: Optional[Callable[[], dict]] = None) -> int:
     """Drive `estimate` over a PairLoader.  `sink(flow_hw2, name)` is called once per pair, in order; the numpy view it gets
     owns a reference to its (pinned) batch buffer, so an asynchronous writer may keep it.  On a GPU the uploads and
     downloads run on a copy stream and overlap with compute; on the CPU (tests of the host logic, with a stand-in
@@ -181,27 +182,35 @@ def stream_pairs(net, loader: PairLoader, device: torch.device, sink: Callable[.
     then returns the outputs already in the file layout, [n / group, H, W, C], the sink gets the name of each group's first
     pair, and the count returned is the number of outputs.
     `prep`: a callable uint8 [n,H,W,3] -> float32 [n,3,H,W] (pivlfn.preproc.Preprocessor) that takes the place of `u8_to_input` for
-    both frames of every batch."""
+    both frames of every batch.
+    `extras`: called once per batch, right after `estimate_fn`, for further per-pair outputs of that batch that are already on the
+    device (pictures, pivlfn.viz): a dict name -> tensor [n,...].  They return with the flows, on the copy stream and behind the same
+    event, and the sink is called as `sink(flow_hw2, name, extras={name: array})`.  Not with `mods` or `group`."""
     if group < 1:
         raise ValueError("stream_pairs: group must be >= 1")
+    if extras is not None and (mods is not None or group != 1):
+        raise ValueError("stream_pairs: extras are per pair: not with mods or group")
     if estimate_fn is None:
         from .inference import estimate as estimate_fn      # noqa: N813
     from .imagemod import image_mod
     to_input = prep if prep is not None else u8_to_input
     on_gpu = device.type == "cuda"
     copy = torch.cuda.Stream(device) if on_gpu else None
-    pending: List[Tuple[Optional[torch.cuda.Event], torch.Tensor, Sequence[str], Optional[Tuple[float, float]]]] = []
+    pending: List[Tuple[Optional[torch.cuda.Event], torch.Tensor, Sequence[str], Optional[Tuple[float, float]], Optional[dict]]] = []
     done = 0
 
     def drain(keep: int) -> None:
         nonlocal done
         while len(pending) > keep:
-            ev, host, names, mod = pending.pop(0)
+            ev, host, names, mod, more = pending.pop(0)
             if ev is not None:
                 ev.synchronize()
             arr = host.numpy()
+            more = {key: t.numpy() for key, t in more.items()} if more is not None else None
             for k, name in enumerate(names):
-                if mod is None:
+                if more is not None:
+                    sink(arr[k], name, extras={key: a[k] for key, a in more.items()})
+                elif mod is None:
                     sink(arr[k], name)
                 else:
                     sink(arr[k], name, mod)
@@ -232,17 +241,24 @@ def stream_pairs(net, loader: PairLoader, device: torch.device, sink: Callable[.
                 if len(names) % group:
                     raise ValueError(f"stream_pairs: a batch of {len(names)} pairs does not split into groups of {group}")
                 out = flow.contiguous()                                                      # [n/group,H,W,C]
+            more = {key: t.contiguous() for key, t in extras().items()} if extras is not None else None
             if on_gpu:
                 host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
+                more_host = {key: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for key, t in more.items()} if more is not None \
+                    else None
                 copy.wait_stream(main)
                 with torch.cuda.stream(copy):
                     host.copy_(out, non_blocking=True)
+                    for key, t in (more or {}).items():
+                        more_host[key].copy_(t, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(copy)
                 out.record_stream(copy)
-                pending.append((ev, host, names[::group], mod))
+                for t in (more or {}).values():
+                    t.record_stream(copy)
+                pending.append((ev, host, names[::group], mod, more_host))
             else:
-                pending.append((None, out, names[::group], mod))
+                pending.append((None, out, names[::group], mod, more))
             drain(in_flight - 1)
     drain(0)
     return done

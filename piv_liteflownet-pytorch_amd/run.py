@@ -4,6 +4,7 @@
   python run.py --model piv -i DIR [-i DIR2 ...] -o OUT [-p] [-s N] [-n N] [-b F ...] [-c F ...] [-v 1|2]
                 [--weights FILE] [--batch B] [--stats] [--validate flag|mask|replace]
                 [--background min|FILE] [--minmax K] [--minmax-floor N] [--truth DIR [--truth-levels]]
+                [--color [--color-max X] [--color-wheel interp|original]] [--vort-image [--vort-max X]] [--quiver [CELL]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -27,6 +28,10 @@ Differences, all deliberate:
   * `--truth DIR` scores every flow against the known field DIR/<name>_flow.flo on the device before it is copied back
     (pivlfn.evaluate: AEE, RMSE, L1, bias and the largest error per pair in <save>/errors.json, per-pixel bias and random-error
     maps in <save>/error_maps.npz); `--truth-levels` adds the table of pyramid level x stage errors;
+  * `--color`, `--vort-image` and `--quiver` write pictures beside every .flo: <name>_out.png (the Middlebury colour coding of the
+    reference's motion_to_color, with color_wheel.png as the legend), <name>_vort.png (vorticity, blue - white - red) and
+    <name>_quiver.png (one arrow per cell).  They are coloured / averaged on the device before the copy back (pivlfn.viz) and written
+    on background threads; with --validate flag|mask the rejected vectors are black and left out of the normaliser and the arrows;
   * a trailing slash on an input directory is ignored (the reference would name the output directory '');
   * with -b/-c a frame whose file name has no '_' gets the tag appended (<stem>_<BBB>_<CCC>_out.flo) -- the reference splits
     the whole path at its last '_' and then either fails or lets the combinations overwrite each other.
@@ -103,7 +108,28 @@ parser.add_argument("--truth", type=str, default=None, metavar="DIR",
 parser.add_argument("--truth-levels", action="store_true",
                     help="with --truth: also the average end-point error of every pyramid level and stage (M, S, R) in errors.json; "
                          "the frame sizes must be multiples of 32")
+parser.add_argument("--color", action="store_true",
+                    help="also write <name>_out.png beside every .flo: the flow in the Middlebury colour coding (pivlfn.viz.flow_to_color; "
+                         "not a reference flag; not with -b/-c), coloured on the device after --validate (rejected vectors are black "
+                         "under flag and mask), and color_wheel.png, the legend, once per output directory")
+parser.add_argument("--color-max", type=float, default=None, metavar="X",
+                    help="with --color: the vector length in pixels that gets full saturation.  Without it every pair is normalised by "
+                         "its own longest vector, as the reference does for a single field, so the pictures of a sequence are only "
+                         "comparable with a fixed normaliser")
+parser.add_argument("--color-wheel", type=str, default=None, choices=["interp", "original"],
+                    help="with --color: the interpolated colour wheel (default, the reference's) or the original Middlebury one")
+parser.add_argument("--vort-image", action="store_true",
+                    help="also write <name>_vort.png beside every .flo: the vorticity (pivlfn.postpro.flow_fields) in blue - white - red, "
+                         "symmetric about 0 (pivlfn.viz.vorticity_image; not a reference flag; not with -b/-c)")
+parser.add_argument("--vort-max", type=float, default=None, metavar="X",
+                    help="with --vort-image: the vorticity magnitude at the ends of the colour map; without it every pair takes its own "
+                         "largest magnitude")
+parser.add_argument("--quiver", type=int, nargs="?", const=0, default=None, metavar="CELL",
+                    help="also write <name>_quiver.png beside every .flo: one arrow per CELL x CELL block of vectors, averaged on the "
+                         "device (pivlfn.viz.decimate_flow); without CELL the smallest block that leaves at most 64 arrows per axis.  "
+                         "Needs matplotlib (not a reference flag; not with -b/-c)")
 PREP_FLAGS = ("background", "minmax", "minmax_floor")
+VIZ_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -232,6 +258,39 @@ def write_validation_json(path, est, names):
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
+
+
+class _VizEstimate:
+    """An estimate_fn (plain estimate() when `inner` is None) that also makes the pictures of every batch on the device, right after
+    the flows and on the same stream: `extras()` hands them to stream_pairs, which copies them back with the flows.  `validator`: the
+    _ValidateEstimate inside, if any; under "flag" and "mask" the pictures show its raw flow with its flags as the mask (what is
+    rejected is black, stays out of the normalisers and out of the arrows), under "replace" the replaced flow."""
+
+    def __init__(self, inner, validator, color, color_max, color_wheel, vort_image, vort_max, quiver):
+        self.inner, self.validator = inner, validator
+        self.color, self.color_max, self.color_wheel = color, color_max, color_wheel or "interp"
+        self.vort_image, self.vort_max, self.quiver = vort_image, vort_max, quiver
+        self.last = {}
+
+    def __call__(self, net, img1, img2, tensor=True):
+        from pivlfn import viz
+        from pivlfn.inference import estimate
+        flow = estimate(net, img1, img2, tensor=True) if self.inner is None else self.inner(net, img1, img2, tensor=True)
+        shown, mask = flow, None
+        if getattr(self.validator, "mode", None) in ("flag", "mask"):
+            shown, mask = self.validator.last_raw, self.validator.last_flag
+        self.last = {}
+        if self.color:
+            self.last["color"] = viz.flow_to_color(shown, self.color_max, wheel=self.color_wheel, mask=mask)
+        if self.vort_image:
+            self.last["vort"] = viz.vorticity_image(shown, vmax=self.vort_max, mask=mask)
+        if self.quiver is not None:
+            cell = self.quiver or viz.quiver_cell(flow.size(2), flow.size(3))
+            self.last["quiver_mean"], self.last["quiver_count"] = viz.decimate_flow(shown, cell, mask)
+        return flow
+
+    def extras(self):
+        return self.last
 
 
 def truth_files(ds, truth_dir, levels=False):
@@ -483,13 +542,13 @@ def background_min(ds, device, batch):
 
 
 def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch, rank=0, world=1, stats_file=None,
-            validate=None, validation_file=None, prep=None, background_file=None, truth=None):
+            validate=None, validation_file=None, prep=None, background_file=None, truth=None, viz=None):
     """Every pair of the folder through `estimate` (reference main_dl, run.py:137-168); with `stats_file`, FlowStats over the
     pairs go there; with `validate` (the keyword arguments of _ValidateEstimate bar `stats`), every flow goes through
     validate_flow before it is copied back and the counts go to `validation_file`.  `prep` = (background, minmax, floor): the
     frames go through pivlfn.preproc.preprocess_frames; a background of "min" is computed from the folder first and written to
     `background_file`.  `truth` = (directory or the truth_files() list of it, levels, errors file, maps file): every flow is scored against its truth file
-    (_TruthEstimate)."""
+    (_TruthEstimate).  `viz`: the keyword arguments of _VizEstimate bar `inner` and `validator`: pictures beside the .flo files."""
     os.makedirs(savedir, exist_ok=True)
     ds = Run(root=inputdir, is_pair=is_pair, n_images=num_images, start_at=start_id)
     truth_paths = None
@@ -515,13 +574,31 @@ def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch
         scorer = _TruthEstimate(truth_paths[lo:hi], est, truth[1], 1.0 / (5.0 if net.starting_scale == 10 else 20.0),
                                 pin=device.type == "cuda")
     seen = []
+    run_est = scorer if scorer is not None else est
+    painter = None
+    if viz is not None:
+        from pivlfn import viz as vz
+        run_est = painter = _VizEstimate(run_est, est if validate is not None else None, **viz)
+        if viz["color"] and rank == 0:
+            vz.write_png(os.path.join(savedir, "color_wheel.png"),
+                         vz.color_wheel_image(wheel=viz["color_wheel"] or "interp", device=device).cpu().numpy())
 
-    def sink(flow, name):
+    def sink(flow, name, extras=None):
         seen.append(name)
         writer.submit(flow, flowname_modifier(name, savedir, pair=False))
+        for key, ext in (("color", "_out.png"), ("vort", "_vort.png")):
+            if extras and key in extras:
+                pictures.submit(extras[key], flowname_modifier(name, savedir, ext=ext, pair=False))
+        if extras and "quiver_mean" in extras:          # pyplot is not thread-safe: the arrows are drawn here
+            vz.draw_quiver(extras["quiver_mean"], extras["quiver_count"], viz["quiver"] or vz.quiver_cell(*flow.shape[:2]), *flow.shape[:2],
+                           flowname_modifier(name, savedir, ext="_quiver.png", pair=False))
     try:
         with FloWriter() as writer:
-            n = stream_pairs(net, loader, device, sink, estimate_fn=scorer if scorer is not None else est, prep=prep)
+            if painter is None:
+                n = stream_pairs(net, loader, device, sink, estimate_fn=run_est, prep=prep)
+            else:
+                with vz.PngWriter() as pictures:
+                    n = stream_pairs(net, loader, device, sink, estimate_fn=run_est, prep=prep, extras=painter.extras)
     finally:
         loader.close()
         if scorer is not None:
@@ -555,6 +632,14 @@ def main_mod(net, inputdir, savedir, start_id, num_images, device, mod_factors: 
         loader.close()
     assert n == (hi - lo) * len(mod_factors)
     return n
+
+
+def args_lines(args, validate, prep, viz) -> List[str]:
+    """The lines of args.txt.  The flags of validation, pre-processing, scoring and pictures appear only in runs that use them:
+    without them the file is what it was before they existed."""
+    return [f"{k}: {v}\n" for k, v in sorted(vars(args).items())
+            if not ((validate is None and k.startswith("validate")) or (prep is None and k in PREP_FLAGS) or
+                    (args.truth is None and k in TRUTH_FLAGS) or (viz is None and k in VIZ_FLAGS))]
 
 
 def load_weights(args) -> Tuple[dict, str]:
@@ -615,6 +700,29 @@ def main(argv: Optional[List[str]] = None) -> int:
         except ValueError as e:
             raise SystemExit(f"run.py: {e}")
         prep = (args.background, minmax, floor)
+    viz = None
+    if any(getattr(args, k) is not None and getattr(args, k) is not False for k in VIZ_FLAGS):
+        import math
+        if args.brightness is not None or args.contrast is not None:
+            raise SystemExit("run.py: --color / --vort-image / --quiver are not available with -b/-c (every combination is a different "
+                             "experiment)")
+        if (args.color_max is not None or args.color_wheel is not None) and not args.color:
+            raise SystemExit("run.py: --color-max and --color-wheel need --color")
+        if args.vort_max is not None and not args.vort_image:
+            raise SystemExit("run.py: --vort-max needs --vort-image")
+        for flag, x in (("--color-max", args.color_max), ("--vort-max", args.vort_max)):
+            if x is not None and not (math.isfinite(x) and x > 0):
+                raise SystemExit(f"run.py: {flag} {x} must be a finite positive number")
+        if args.quiver is not None:
+            if not 0 <= args.quiver <= 32768:
+                raise SystemExit(f"run.py: --quiver {args.quiver}: the cell must be 1..32768")
+            from pivlfn.viz import _pyplot
+            try:
+                _pyplot()                           # once, here, and not at the first pair
+            except ImportError as e:
+                raise SystemExit(f"run.py: --quiver: {e}")
+        viz = dict(color=args.color, color_max=args.color_max, color_wheel=args.color_wheel, vort_image=args.vort_image,
+                   vort_max=args.vort_max, quiver=args.quiver)
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run.py: this build has no CPU path (the reference's correlation has none either, "
                          "src/correlation.py:339-340); a GPU is required")
@@ -642,11 +750,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         os.makedirs(lay.save, exist_ok=True)
         if rank == 0:
             with open(lay.args_file, "w") as f:
-                for k, v in sorted(vars(args).items()):
-                    if (validate is None and k.startswith("validate")) or (prep is None and k in PREP_FLAGS) or \
-                            (args.truth is None and k in TRUTH_FLAGS):
-                        continue                 # without these flags the file is what it was before they existed
-                    f.write(f"{k}: {v}\n")
+                f.writelines(args_lines(args, validate, prep, viz))
         if mods is None:
             stats_file = os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "stats", 1)[:-4] + ".npz") \
                 if args.stats else None          # stats.npz (stats_left / stats_right.npz for the halves of a stereo set)
@@ -657,7 +761,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                              None if args.truth is None else
                              (truth_paths[imdir], args.truth_levels,
                               os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "errors", 1)[:-4] + ".json"),
-                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "error_maps", 1)[:-4] + ".npz")))
+                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "error_maps", 1)[:-4] + ".npz")),
+                             viz)
         else:
             total += main_mod(net, imdir, lay.flow, args.start, args.num_images, device, mods, args.batch, rank, world)
     if args.truth is not None and world > 1:

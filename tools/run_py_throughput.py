@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end rate of run.py on a folder of PNG frames (decode -> H2D -> estimate -> D2H -> .flo): N2/N1 of SURVEY section 8(f).
-  python tools/run_py_throughput.py [frames] [size] [--truth]
+  python tools/run_py_throughput.py [frames] [size] [--truth] [--color] [--vort-image]
+--color / --vort-image: every pair also gets its picture (main_dl's `viz`: coloured on the device, written as PNG on background
+threads); their cost is the difference to a run without them.
 --truth: every pair also has a truth file (<frame>_flow.flo, 8 bytes per pixel) that run.py reads and scores on the device
 (main_dl's `truth`): the cost of --truth is the difference to a run without it; the part of it spent after the last pair, on
 errors.json and error_maps.npz (run.py's finish_truth), is timed and printed beside the rate."""
@@ -18,7 +20,8 @@ import run as runpy
 from pivlfn import synth
 
 with_truth = "--truth" in sys.argv
-argv = [a for a in sys.argv[1:] if a != "--truth"]
+pictures = [a for a in ("--color", "--vort-image") if a in sys.argv]
+argv = [a for a in sys.argv[1:] if a not in ("--truth", "--color", "--vort-image")]
 n = int(argv[0]) if len(argv) > 0 else 33
 S = int(argv[1]) if len(argv) > 1 else 1024
 d = tempfile.mkdtemp(prefix="seq_")
@@ -35,6 +38,9 @@ if with_truth:
         write_flow(field, os.path.join(tdir, f"frame_{k:05d}_flow.flo"))
     truth = (tdir, False, os.path.join(out, "errors.json"), os.path.join(out, "error_maps.npz"))
 kw = dict(truth=truth) if with_truth else {}
+if pictures:
+    kw["viz"] = dict(color="--color" in pictures, color_max=None, color_wheel=None, vort_image="--vort-image" in pictures, vort_max=None,
+                     quiver=None)
 finish_s = [0.0]
 if with_truth:
     _finish = runpy.finish_truth
@@ -54,6 +60,6 @@ for precision in ("fp32", "fp16"):
         pairs = runpy.main_dl(net, d, out, False, 0, -1, dev, batch, **kw)      # run.py's per-directory loop (run.py:137-168)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print(f"run.py main_dl{' --truth' if with_truth else ''} {S}x{S} PNG sequence, {pairs} pairs, --batch {batch}, {precision}: {dt:.2f} s = {pairs / dt:.1f} pairs/s "
-              f"end to end (PNG decode -> H2D -> estimate -> D2H -> .flo files closed)"
+        print(f"run.py main_dl{' --truth' if with_truth else ''}{''.join(' ' + p for p in pictures)} {S}x{S} PNG sequence, {pairs} pairs, --batch {batch}, {precision}: {dt:.2f} s = {pairs / dt:.1f} pairs/s "
+              f"end to end (PNG decode -> H2D -> estimate -> D2H -> .flo{' and .png' if pictures else ''} files closed)"
               + (f"; of it {finish_s[0]:.3f} s after the last pair (errors.json, error_maps.npz)" if with_truth else ""), flush=True)
