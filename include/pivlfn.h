@@ -49,29 +49,40 @@ int         pivlfn_tune(int knob, int value);
 
 /* ---- custom op: replaces _FunctionCorrelation.forward, src/correlation.py:287-344 (+ kernels :9-104)
  * first, second: NCHW [B,C,H,W]; out: NCHW [B,49,ceil(H/stride),ceil(W/stride)];
- * out[b,7(dy+3)+(dx+3),y,x] = (1/C) sum_c first[b,c,s*y,s*x] * second[b,c,s*(y+dy),s*(x+dx)], zeros outside. */
+ * out[b,7(dy+3)+(dx+3),y,x] = (1/C) sum_c first[b,c,s*y,s*x] * second[b,c,s*(y+dy),s*(x+dx)], zeros outside.
+ * 1 <= stride <= 4, PIVLFN_ERR_ARG otherwise: one range for this entry point, pivlfn_corr_bwd and the two fused ones. */
 int pivlfn_corr_fwd(const float *first, const float *second, float *out,
                     int B, int C, int H, int W, int stride, void *stream);
 
 /* ---- backward of the custom op: replaces _FunctionCorrelation.backward, src/correlation.py:348-405 (+ kernels :106-234).
  * grad_out: NCHW [B,49,ceil(H/stride),ceil(W/stride)]; grad_first / grad_second: NCHW [B,C,H,W], every element written
- * (exact zeros off the stride grid); either may be NULL (needs_input_grad false, :353-356). */
+ * (exact zeros off the stride grid); either may be NULL (needs_input_grad false, :353-356).
+ * 1 <= stride <= 4 as for the forward, PIVLFN_ERR_ARG otherwise. */
 int pivlfn_corr_bwd(const float *first, const float *second, const float *grad_out, float *grad_first, float *grad_second,
                     int B, int C, int H, int W, int stride, void *stream);
 
+/* Channels per workgroup (16, 8 or 4) of the pivlfn_corr_bwd launch of this size: the launch policy, a function of the size
+ * alone, exported so that tests can tell which grouping a shape runs on (the gradients' bits do not depend on it).  No launch,
+ * no GPU needed; 0 for a shape or stride pivlfn_corr_bwd refuses.  Added without an ABI bump (additive). */
+int pivlfn_corr_bwd_channel_group(int B, int C, int H, int W, int stride);
+
 /* ---- replaces backwarp(), src/models.py:20-35.  in: NCHW [B,C,H,W]; flow: NCHW [B,2,H,W] (pixels);
- * out[b,c,y,x] = bilinear(in[b,c], x + flow[b,0,y,x], y + flow[b,1,y,x]), zeros outside. */
+ * out[b,c,y,x] = bilinear(in[b,c], x + flow[b,0,y,x], y + flow[b,1,y,x]), zeros outside.
+ * A flow of any finite size is in range (a sample far outside gives zero); a NaN flow component gives a zero output pixel:
+ * the tap positions are clamped with fmaxf / fminf, which drop a NaN, so no tap of that pixel lies inside the image. */
 int pivlfn_backwarp(const float *in, const float *flow, float *out,
                     int B, int C, int H, int W, void *stream);
 
 /* ---- fused Matching front end: backwarp(second, flow*flow_scale) then correlation, then optional
- * LeakyReLU(0.1): src/models.py:171-184.  NCHW in / NCHW out, flow may be NULL (level 6). */
+ * LeakyReLU(0.1): src/models.py:171-184.  NCHW in / NCHW out, flow may be NULL (level 6).
+ * 1 <= stride <= 4, PIVLFN_ERR_ARG otherwise. */
 int pivlfn_warp_corr_fwd(const float *first, const float *second, const float *flow, float flow_scale,
                          float *out, int B, int C, int H, int W, int stride, int leaky, void *stream);
 
 /* ---- the same kernel on the network's internal channels-last layout (what pivlfn_forward launches;
  * exported for benchmarks and roofline measurement).  first/second: [B,H,W,C]; flow: [B,H,W,4] (u,v,0,0)
- * or NULL; out: [B,Ho,Wo,56] (49 displacements + 7 zero lanes). C must be a multiple of 32. */
+ * or NULL; out: [B,Ho,Wo,56] (49 displacements + 7 zero lanes). C must be a multiple of 32.
+ * 1 <= stride <= 4, PIVLFN_ERR_ARG otherwise. */
 int pivlfn_warp_corr_nhwc(const float *first, const float *second, const float *flow, float flow_scale,
                           float *out, int B, int C, int H, int W, int stride, int leaky, void *stream);
 

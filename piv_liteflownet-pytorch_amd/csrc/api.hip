@@ -110,6 +110,12 @@ int pivlfn_corr_bwd(const float *first, const float *second, const float *grad_o
     return launch_corr_bwd(first, second, grad_out, grad_first, grad_second, B, C, H, W, stride, (hipStream_t)stream);
 }
 
+int pivlfn_corr_bwd_channel_group(int B, int C, int H, int W, int stride)
+{
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || stride < 1 || stride > 4) { set_error("corr_bwd_channel_group: bad shape or stride"); return 0; }
+    return corr_bwd_cgroup(B, C, H, W, stride);
+}
+
 int pivlfn_backwarp(const float *in, const float *flow, float *out, int B, int C, int H, int W, void *stream)
 {
     return launch_backwarp_nchw(in, flow, out, B, C, H, W, (hipStream_t)stream);

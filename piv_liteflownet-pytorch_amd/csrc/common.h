@@ -226,6 +226,7 @@ void warp_corr_time_next(hipEvent_t start, hipEvent_t stop);   // attach start/s
 int launch_backwarp_nchw(const float *in, const float *flow, float *out, int B, int C, int H, int W, hipStream_t st);
 int launch_corr_bwd(const float *first, const float *second, const float *gout, float *gfirst, float *gsecond,
                     int B, int C, int H, int W, int s, hipStream_t st);
+int corr_bwd_cgroup(int B, int C, int H, int W, int s);        // channels per workgroup of that launch (16, 8 or 4)
 
 // ---- small ops (ops.hip); NHWC unless noted ----------------------------------------------------------
 int launch_prep_images(const float *img1, const float *img2, float *out, int B, int H, int W,

@@ -66,17 +66,26 @@ __global__ __launch_bounds__(256) void corr_bwd_kernel(const float *__restrict__
     }
 }
 
+// Channels per workgroup: enough channel groups to fill the chip, but at least 4 channels per group so the 49 gout loads amortise.
+// A function of the launch's size only; the bits of a gradient do not depend on it (a thread sums its 49 terms per channel).
+int corr_bwd_cgroup(int B, int C, int H, int W, int s)
+{
+    const int tiles = cdiv(cdiv(W, s), 16) * cdiv(cdiv(H, s), 16);
+    int cgroup = 16;
+    while (cgroup > 4 && (long)tiles * cdiv(C, cgroup) * B < 2048) cgroup >>= 1;
+    return cgroup;
+}
+
 int launch_corr_bwd(const float *first, const float *second, const float *gout, float *gfirst, float *gsecond,
                     int B, int C, int H, int W, int s, hipStream_t st)
 {
     PIV_REQUIRE(first && second && gout, "corr_bwd: null input");
-    PIV_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && s >= 1, "corr_bwd: bad shape B=%d C=%d H=%d W=%d stride=%d", B, C, H, W, s);
+    PIV_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "corr_bwd: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+    PIV_REQUIRE(s >= 1 && s <= 4, "corr_bwd: stride=%d unsupported", s);      // the forward's range (launch_warp_corr)
     PIV_REQUIRE(B <= 65535, "corr_bwd: batch %d exceeds the grid limit", B);
     const int Ho = cdiv(H, s), Wo = cdiv(W, s);
     const int tiles_x = cdiv(Wo, 16), tiles = tiles_x * cdiv(Ho, 16);
-    // enough channel groups to fill the chip, but at least 4 channels per group so the 49 gout loads amortise
-    int cgroup = 16;
-    while (cgroup > 4 && (long)tiles * cdiv(C, cgroup) * B < 2048) cgroup >>= 1;
+    const int cgroup = corr_bwd_cgroup(B, C, H, W, s);
     const dim3 grid(tiles, cdiv(C, cgroup), B);
     if (gfirst) hipLaunchKernelGGL(corr_bwd_kernel<false>, grid, dim3(256), 0, st, second, gout, gfirst, C, H, W, Ho, Wo, s, cgroup, tiles_x);
     if (gsecond) hipLaunchKernelGGL(corr_bwd_kernel<true>, grid, dim3(256), 0, st, first, gout, gsecond, C, H, W, Ho, Wo, s, cgroup, tiles_x);

@@ -31,8 +31,10 @@ def _check(first: torch.Tensor, second: torch.Tensor) -> None:
 class _FunctionCorrelation(torch.autograd.Function):
     @staticmethod
     def forward(ctx, first, second, intStride):
-        _check(first, second)
         s = int(intStride)
+        if not 1 <= s <= 4:                   # the range of pivlfn_corr_fwd / pivlfn_corr_bwd; before any arithmetic with s
+            raise ValueError(f"FunctionCorrelation: intStride {s} outside 1..4")
+        _check(first, second)
         ctx.save_for_backward(first, second)
         ctx.intStride = s
         B, C, H, W = first.shape

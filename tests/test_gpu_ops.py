@@ -7,6 +7,7 @@ import torch
 
 import pivlfn
 import pivlfn_oracle as orc
+from corr_reference import fused_f64
 from pivlfn import _lib
 
 pytestmark = pytest.mark.gpu
@@ -129,45 +130,6 @@ def test_fused_warp_correlation_vs_oracle_composition(shape, nhwc, dev):
     assert rel(got, want) < 2e-5
 
 
-def fused_f64(f1, f2, fl, scale, s, leaky=True, device="cpu"):
-    """leaky_relu(corr(f1, backwarp(f2, flow * scale)))  (src/models.py:20-35, 171-184; src/correlation.py:36-104) in float64 and in
-    pixel units: the sample position is x + u * scale with the exact product of the two fp32 numbers, the blend weights and the
-    dot products are float64.  What the fp32 kernel and the fp32 oracle are both measured against.  Plain torch float64 tensor
-    operations (indexing, multiply, sum) on `device`: none of the library's kernels."""
-    B, C, H, W = f1.shape
-    t1 = torch.from_numpy(f1).to(device).double()
-    t2 = torch.from_numpy(f2).to(device).double()
-    if fl is not None:
-        tf = torch.from_numpy(fl).to(device).double()
-        yy, xx = torch.meshgrid(torch.arange(H, device=device, dtype=torch.float64), torch.arange(W, device=device, dtype=torch.float64), indexing="ij")
-        px = xx + tf[:, 0] * float(np.float32(scale))
-        py = yy + tf[:, 1] * float(np.float32(scale))
-        x0, y0 = torch.floor(px), torch.floor(py)
-        ax, ay = px - x0, py - y0
-        f2w = torch.zeros_like(t2)
-        flat = t2.reshape(B, C, H * W)
-        for dy, dx, w in ((0, 0, (1 - ax) * (1 - ay)), (0, 1, ax * (1 - ay)), (1, 0, (1 - ax) * ay), (1, 1, ax * ay)):
-            xi, yi = x0 + dx, y0 + dy
-            ok = ((xi >= 0) & (xi < W) & (yi >= 0) & (yi < H)).double()
-            idx = (yi.clamp(0, H - 1).long() * W + xi.clamp(0, W - 1).long()).reshape(B, 1, H * W).expand(B, C, H * W)
-            f2w += (torch.gather(flat, 2, idx) * (w * ok).reshape(B, 1, H * W)).reshape(B, C, H, W)
-    else:
-        f2w = t2
-    Ho, Wo = -(-H // s), -(-W // s)
-    pad = 3 * s
-    f2p = torch.zeros(B, C, H + 2 * pad, W + 2 * pad, device=device, dtype=torch.float64)
-    f2p[:, :, pad:pad + H, pad:pad + W] = f2w
-    a = t1[:, :, ::s, ::s]
-    out = torch.empty(B, 49, Ho, Wo, device=device, dtype=torch.float64)
-    for dy in range(-3, 4):
-        for dx in range(-3, 4):
-            sh = f2p[:, :, pad + s * dy:pad + s * dy + H:s, pad + s * dx:pad + s * dx + W:s]
-            out[:, 7 * (dy + 3) + (dx + 3)] = (a * sh).sum(dim=1) / C
-    if leaky:
-        out = torch.where(out >= 0, out, 0.1 * out)
-    return out.cpu().numpy()
-
-
 @pytest.mark.parametrize("shape", [
     (4, 64, 256, 256, 2, True),      # 1024 tiles: persistent kernel, sliding window over runs of 4 tiles (two items per lane)
     (3, 64, 200, 136, 2, True),      # 13 x 9 x 3 tiles: runs of 2 with a ragged last run, ragged tiles right and bottom, several runs per workgroup
@@ -184,7 +146,7 @@ def fused_f64(f1, f2, fl, scale, s, leaky=True, device="cpu"):
 def test_channels_last_kernels_vs_oracle_at_launch_sizes(shape, dev):
     """The channels-last kernels pivlfn_forward launches, at sizes where their launch policy takes each of its branches (latency
     kernel, persistent kernel with and without the sliding window), with large smooth-plus-noise flows so that taps leave the image
-    on every side.  The yardstick is the fused operation in FLOAT64 (fused_f64 above).  At x >= 512 a sample position has an fp32 ulp
+    on every side.  The yardstick is the fused operation in FLOAT64 (fused_f64 of corr_reference.py).  At x >= 512 a sample position has an fp32 ulp
     of 6e-5 px, so the fp32 kernel and the fp32 oracle -- both in pixel units, one contracting x + u * scale into an fma, the other
     rounding the product first -- each sit a few 1e-5 of max|out| from float64 on a 1024-pixel image without either being wrong; what
     is asserted is that the kernel is no further from float64 than twice the oracle is (plus 2e-6), and within 2e-5 of the oracle on
