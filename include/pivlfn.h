@@ -305,6 +305,54 @@ int pivlfn_scalar_to_color(const void *field, int is_f64, const unsigned char *m
 int pivlfn_flow_decimate(const float *flow, const unsigned char *mask, float *mean, int *count, int B, int H, int W, int cell,
                          void *stream);
 
+/* ---- match quality of an estimated flow: the normalised correlation between image 1 and image 2 warped back by the flow inside a
+ * (2*radius+1)^2 window around every pixel, at zero shift and at the four one-pixel shifts, and the sub-pixel position of its peak
+ * (three-point Gaussian fit) -- the correlation peak height of a classical PIV evaluation and what a window-deformation pass would
+ * still add to the vector.  Added without an ABI bump (additive).
+ * img1, img2: NCHW [B,C,H,W] fp32, C = 1 or 3;  flow: NCHW [B,2,H,W] fp32;  mask: [B,H,W] bytes or NULL, nonzero = leave the pixel
+ * out;  quality: NCHW [B,3,H,W] fp32, planes c, dx, dy;  flag: [B,H,W] bytes;  workspace: 8-byte aligned, at least
+ * pivlfn_match_quality_workspace_bytes(B,H,W,radius) bytes, needs no initial contents.  Launches only on `stream`, no allocation, no
+ * host synchronisation, no floating-point atomics; no output depends on what quality, flag or the workspace held before the call; a
+ * pair gives the same bits alone, inside any batch and from run to run.
+ * Arithmetic contract, all fp64 unless stated, every operation rounded on its own (no fma), divisions and square roots correctly
+ * rounded:
+ *   gray value:  C = 1: g(q) = (double)x;  C = 3: g(q) = (((double)r + (double)g) + (double)b) / 3.0 (three equal channels give the
+ *                bits of C = 1).  a = g of img1, g2 = g of img2.
+ *   warp:        xf = (float)x + u(p), yf = (float)y + v(p), one fp32 addition each;  m(p) = 1 iff 0 <= xf <= W-1 && 0 <= yf <= H-1
+ *                (NaN and inf compare false: the 1e10 of a masked flow is invalid by itself).  Where m = 1: x0 = (int)xf,
+ *                x1 = min(x0+1, W-1), fx = (double)xf - x0 (exact), the same in y;
+ *                top = (1.0-fx)*g2(y0,x0) + fx*g2(y0,x1), bot likewise on row y1;  b(p) = (1.0-fy)*top + fy*bot.
+ *                This is pivlfn_backwarp's sampling position (align_corners=True: pixel x + u).
+ *   exclusion:   k(q) = 1 iff mask is NULL or mask(q) == 0.
+ *   shifts:      s = (sx, sy) in {(0,0), (-1,0), (+1,0), (0,-1), (0,+1)}, in this order.  Pixel q takes part in shift s iff k(q) = 1,
+ *                q+s lies inside the image and m(q+s) = 1.  Its six terms are 1, a(q), a(q)^2, b(q+s), b(q+s)^2, a(q)*b(q+s); a pixel
+ *                that does not take part is +0.0 in all six.
+ *   window sums: over the (2*radius+1)^2 window centred at p, clipped to the image (no edge replication): per row the terms are added
+ *                left to right from +0.0, then the row sums top to bottom from +0.0.  The order is fixed by this contract and not by
+ *                the launch geometry.  Results per shift: n (an exact count), A, AA, Bs, BB, AB.
+ *   per shift:   few = n < min_count;  va = AA - A*A/n, vb = BB - Bs*Bs/n, cov = AB - A*Bs/n;
+ *                flat = va < floor*floor*n || vb < floor*floor*n;  c_s = cov / sqrt(va*vb) where neither few nor flat.
+ *   flag byte:   bit 0 (1) FEW: shift 0 is few;  bit 1 (2) FLAT: shift 0 is flat and not few;  bit 2 (4) NO_PEAK: FEW and FLAT are
+ *                clear and a fit condition fails;  bit 3 (8) CENTRE_OUT: k(p) = 0 or m(p) = 0 (informational: the values are still
+ *                formed).  Fit conditions, on the c values as computed: the four other shifts are neither few nor flat; c0 > 0; each
+ *                side value > 0; c0 >= each side value; (2*c0 - c_minus) - c_plus >= 1e-6 in x and in y.
+ *   outputs:     c = (float)c0, NaN where FEW or FLAT is set.  Where bits 0-2 are clear, with l = ln (the device library's fp64
+ *                logarithm, the one operation here that is not correctly rounded):
+ *                dx = 0.5*(l(c_minus) - l(c_plus)) / ((l(c_minus) - 2.0*l(c0)) + l(c_plus)) over the x shifts, dy over the y shifts,
+ *                each rounded once to fp32; the conditions keep the denominator below -1e-6 and |dx|, |dy| <= 0.5.  dx = dy = +0.0f
+ *                wherever one of bits 0-2 is set.  The peak sits at the error of the flow: flow + (dx, dy) is the corrected vector.
+ * Errors (PIVLFN_ERR_ARG, before any launch): null img1 / img2 / flow / quality / flag / workspace, quality or flag overlapping an
+ * input, the workspace or each other, C not 1 or 3, a non-positive size, H*W >= 2^31, B > 65535, radius outside 1..15, min_count < 2
+ * or > (2*radius+1)^2, floor negative or non-finite, a misaligned or too-small workspace. */
+#define PIVLFN_QUALITY_FEW        1
+#define PIVLFN_QUALITY_FLAT       2
+#define PIVLFN_QUALITY_NO_PEAK    4
+#define PIVLFN_QUALITY_CENTRE_OUT 8
+size_t pivlfn_match_quality_workspace_bytes(int B, int H, int W, int radius);
+int pivlfn_match_quality(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask, float *quality,
+                         unsigned char *flag, int B, int H, int W, int radius, int min_count, double floor, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

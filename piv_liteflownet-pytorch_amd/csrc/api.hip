@@ -200,6 +200,16 @@ int pivlfn_error_stats_accumulate(const float *flow, const float *truth, const u
     return launch_error_stats(flow, truth, mask, acc, B, H, W, (hipStream_t)stream);
 }
 
+size_t pivlfn_match_quality_workspace_bytes(int B, int H, int W, int radius) { return match_quality_workspace_bytes(B, H, W, radius); }
+
+int pivlfn_match_quality(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask, float *quality,
+                         unsigned char *flag, int B, int H, int W, int radius, int min_count, double floor, void *workspace,
+                         size_t workspace_bytes, void *stream)
+{
+    return launch_match_quality(img1, img2, C, flow, mask, quality, flag, B, H, W, radius, min_count, floor, workspace, workspace_bytes,
+                                (hipStream_t)stream);
+}
+
 int pivlfn_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, void *stream)
 {
     return launch_flow_maxrad(flow, mask, maxrad, B, H, W, (hipStream_t)stream);

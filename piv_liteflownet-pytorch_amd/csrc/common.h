@@ -279,6 +279,12 @@ int launch_scalar_to_color(const void *field, int is_f64, const unsigned char *m
 int launch_flow_decimate(const float *flow, const unsigned char *mask, float *mean, int *count, int B, int H, int W, int cell,
                          hipStream_t st);
 
+// ---- match quality (quality.hip): windowed correlation of img1 with img2 warped by the flow, and the sub-pixel residual of its peak ----
+size_t match_quality_workspace_bytes(int B, int H, int W, int radius);
+int launch_match_quality(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask, float *quality,
+                         unsigned char *flag, int B, int H, int W, int radius, int min_count, double floor, void *ws, size_t ws_bytes,
+                         hipStream_t st);
+
 // ---- image pre-processing (preproc.hip): [n,H,W,3] uint8 frames -> background minimum [H,W,3], network input [n,3,H,W] fp32 --------
 int launch_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, hipStream_t st);
 int launch_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W, int k, int floor,

@@ -55,6 +55,9 @@ SIGNATURES = {
     "pivlfn_scalar_to_color": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3
                                + [ctypes.c_double] * 2 + [ctypes.c_int, ctypes.c_void_p]),
     "pivlfn_flow_decimate": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    "pivlfn_match_quality_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "pivlfn_match_quality": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5
+                             + [ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "pivlfn_create": (ctypes.c_int, [ctypes.POINTER(Tensor), ctypes.c_int, ctypes.c_float, ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_void_p)]),
     "pivlfn_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "pivlfn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_void_p] + [ctypes.c_int] * 3),

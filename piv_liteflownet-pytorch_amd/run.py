@@ -5,6 +5,7 @@
                 [--weights FILE] [--batch B] [--stats] [--validate flag|mask|replace]
                 [--background min|FILE] [--minmax K] [--minmax-floor N] [--truth DIR [--truth-levels]]
                 [--color [--color-max X] [--color-wheel interp|original]] [--vort-image [--vort-max X]] [--quiver [CELL]]
+                [--quality [R] [--quality-image]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -32,6 +33,11 @@ Differences, all deliberate:
     reference's motion_to_color, with color_wheel.png as the legend), <name>_vort.png (vorticity, blue - white - red) and
     <name>_quiver.png (one arrow per cell).  They are coloured / averaged on the device before the copy back (pivlfn.viz) and written
     on background threads; with --validate flag|mask the rejected vectors are black and left out of the normaliser and the arrows;
+  * `--quality [R]` writes a per-vector quality measure beside every .flo, computed on the device from the two frames the network was
+    given and the flow that is written (pivlfn.quality.match_quality: the correlation of frame 1 with frame 2 warped back by the
+    flow inside (2R+1)^2 windows, and the sub-pixel residual of its peak): <name>_qual.flo with the three bands c, dx, dy, the
+    summaries in <save>/quality.json, and with `--quality-image` <name>_corr.png (c on 0..1 in gray, undefined pixels red); with
+    --validate flag|mask the rejected vectors are left out of the windows;
   * a trailing slash on an input directory is ignored (the reference would name the output directory '');
   * with -b/-c a frame whose file name has no '_' gets the tag appended (<stem>_<BBB>_<CCC>_out.flo) -- the reference splits
     the whole path at its last '_' and then either fails or lets the combinations overwrite each other.
@@ -128,8 +134,19 @@ parser.add_argument("--quiver", type=int, nargs="?", const=0, default=None, meta
                     help="also write <name>_quiver.png beside every .flo: one arrow per CELL x CELL block of vectors, averaged on the "
                          "device (pivlfn.viz.decimate_flow); without CELL the smallest block that leaves at most 64 arrows per axis.  "
                          "Needs matplotlib (not a reference flag; not with -b/-c)")
+parser.add_argument("--quality", type=int, nargs="?", const=8, default=None, metavar="R",
+                    help="also write <name>_qual.flo beside every .flo: the match quality of the written flow (pivlfn.quality."
+                         "match_quality; not a reference flag; not with -b/-c): bands c, the correlation of frame 1 with frame 2 warped "
+                         "back by the flow inside (2R+1) x (2R+1) windows (R = 1..15, default 8), and dx, dy, the sub-pixel residual of "
+                         "its peak; the summaries go to <save>/quality.json.  With --validate flag|mask the rejected vectors are left out "
+                         "of the windows, with --validate replace the replaced flow is rated")
+parser.add_argument("--quality-image", action="store_true",
+                    help="with --quality: also <name>_corr.png, c on 0..1 in gray, pixels without a value in red")
 PREP_FLAGS = ("background", "minmax", "minmax_floor")
-VIZ_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
+QUALITY_FLAGS = ("quality", "quality_image")
+QUALITY_BAD_RGB = (255, 0, 0)
+PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS      # every flag of a further per-pair output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -291,6 +308,74 @@ class _VizEstimate:
 
     def extras(self):
         return self.last
+
+
+class _QualityEstimate:
+    """An estimate_fn (plain estimate() when `inner` is None) that also rates every batch of flows on the device, right after them
+    and on the same stream: match_quality of the frames the network was given and the flow that is returned (what the .flo files
+    get), with the flags of `validator` (a _ValidateEstimate under "flag" or "mask") as the mask.  `extras()` hands the three
+    bands -- and the picture of c, with `image` -- to stream_pairs beside those of `painter` (a _VizEstimate, if any); the per-pair
+    sums stay on the device until sums() copies them once."""
+
+    def __init__(self, inner, validator, painter, radius, image):
+        from pivlfn.quality import check_params
+        self.inner, self.validator, self.painter, self.radius, self.image = inner, validator, painter, radius, image
+        self.floor = 1.0 / 255.0
+        self.min_count = check_params(radius, self.floor, None)
+        self.last, self._sums = {}, []
+
+    @property
+    def mode(self):
+        return getattr(self.validator, "mode", None)
+
+    def __call__(self, net, img1, img2, tensor=True):
+        from pivlfn import viz
+        from pivlfn.inference import estimate
+        from pivlfn.quality import match_quality
+        flow = estimate(net, img1, img2, tensor=True) if self.inner is None else self.inner(net, img1, img2, tensor=True)
+        mask = self.validator.last_flag if self.mode in ("flag", "mask") else None
+        q = match_quality(img1, img2, flow, self.radius, mask, self.floor, self.min_count)
+        self._sums.append(q.sums())
+        self.last = {"qual": torch.cat([q.c.unsqueeze(1), q.residual], dim=1).permute(0, 2, 3, 1)}      # the .flo layout
+        if self.image:
+            self.last["corr"] = viz.scalar_to_color(q.c.contiguous(), 0.0, 1.0, cmap="gray", bad=QUALITY_BAD_RGB)
+        return flow
+
+    def extras(self):
+        return {**(self.painter.extras() if self.painter is not None else {}), **self.last}
+
+    def sums(self):
+        """[pairs, 9] float64 on the host (pivlfn.quality.SUMS), in the order of the pairs."""
+        if not self._sums:
+            return torch.zeros([0, 9], dtype=torch.float64)
+        return torch.cat(self._sums).cpu()
+
+
+def write_quality_json(path, rater, names, rank, world):
+    """<save>/quality.json: the parameters, per pair name the summary of MatchQuality.summary(), and the same over the run, formed from
+    the per-pair sums in pair order.  Sharded runs (world > 1, a process group exists): the records of all ranks are gathered in rank
+    order -- the shards are contiguous, so that is pair order -- and rank 0 writes.  A value that is not finite is written as null."""
+    import json
+    import math
+    from pivlfn.quality import summarize
+    rows = rater.sums().tolist()
+    assert len(rows) == len(names)
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.all_gather_object(parts, (names, rows))
+        names, rows = [n for p in parts for n in p[0]], [r for p in parts for r in p[1]]
+    if rank != 0:
+        return
+    total = [0.0] * 9
+    for row in rows:
+        total = [a + b for a, b in zip(total, row)]
+    strict = lambda d: {k: (None if isinstance(v, float) and not math.isfinite(v) else v) for k, v in d.items()}      # noqa: E731
+    doc = {"radius": rater.radius, "floor": rater.floor, "min_count": rater.min_count, "mask": rater.mode if rater.mode in ("flag", "mask") else None,
+           "pairs": {name: strict(summarize(row)) for name, row in zip(names, rows)}, "total": strict(summarize(total))}
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1, allow_nan=False)
+        f.write("\n")
 
 
 def truth_files(ds, truth_dir, levels=False):
@@ -542,13 +627,14 @@ def background_min(ds, device, batch):
 
 
 def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch, rank=0, world=1, stats_file=None,
-            validate=None, validation_file=None, prep=None, background_file=None, truth=None, viz=None):
+            validate=None, validation_file=None, prep=None, background_file=None, truth=None, viz=None, quality=None):
     """Every pair of the folder through `estimate` (reference main_dl, run.py:137-168); with `stats_file`, FlowStats over the
     pairs go there; with `validate` (the keyword arguments of _ValidateEstimate bar `stats`), every flow goes through
     validate_flow before it is copied back and the counts go to `validation_file`.  `prep` = (background, minmax, floor): the
     frames go through pivlfn.preproc.preprocess_frames; a background of "min" is computed from the folder first and written to
     `background_file`.  `truth` = (directory or the truth_files() list of it, levels, errors file, maps file): every flow is scored against its truth file
-    (_TruthEstimate).  `viz`: the keyword arguments of _VizEstimate bar `inner` and `validator`: pictures beside the .flo files."""
+    (_TruthEstimate).  `viz`: the keyword arguments of _VizEstimate bar `inner` and `validator`: pictures beside the .flo files.
+    `quality` = (radius, image, quality file): every written flow is rated by _QualityEstimate."""
     os.makedirs(savedir, exist_ok=True)
     ds = Run(root=inputdir, is_pair=is_pair, n_images=num_images, start_at=start_id)
     truth_paths = None
@@ -583,10 +669,17 @@ def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch
             vz.write_png(os.path.join(savedir, "color_wheel.png"),
                          vz.color_wheel_image(wheel=viz["color_wheel"] or "interp", device=device).cpu().numpy())
 
+    rater = None
+    if quality is not None:
+        from pivlfn import viz as vz
+        run_est = rater = _QualityEstimate(run_est, est if validate is not None else None, painter, quality[0], quality[1])
+
     def sink(flow, name, extras=None):
         seen.append(name)
         writer.submit(flow, flowname_modifier(name, savedir, pair=False))
-        for key, ext in (("color", "_out.png"), ("vort", "_vort.png")):
+        if extras and "qual" in extras:
+            writer.submit(extras["qual"], flowname_modifier(name, savedir, ext="_qual.flo", pair=False))
+        for key, ext in (("color", "_out.png"), ("vort", "_vort.png"), ("corr", "_corr.png")):
             if extras and key in extras:
                 pictures.submit(extras[key], flowname_modifier(name, savedir, ext=ext, pair=False))
         if extras and "quiver_mean" in extras:          # pyplot is not thread-safe: the arrows are drawn here
@@ -594,11 +687,12 @@ def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch
                            flowname_modifier(name, savedir, ext="_quiver.png", pair=False))
     try:
         with FloWriter() as writer:
-            if painter is None:
+            if painter is None and rater is None:
                 n = stream_pairs(net, loader, device, sink, estimate_fn=run_est, prep=prep)
             else:
                 with vz.PngWriter() as pictures:
-                    n = stream_pairs(net, loader, device, sink, estimate_fn=run_est, prep=prep, extras=painter.extras)
+                    n = stream_pairs(net, loader, device, sink, estimate_fn=run_est, prep=prep,
+                                     extras=(rater if rater is not None else painter).extras)
     finally:
         loader.close()
         if scorer is not None:
@@ -606,6 +700,8 @@ def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch
     assert n == hi - lo
     if scorer is not None:
         finish_truth(scorer, seen, truth[2], truth[3], rank, world, device)
+    if rater is not None:
+        write_quality_json(quality[2], rater, seen, rank, world)
     if validate is not None:
         write_validation_json(validation_file, est, seen)
         if est.stats is not None:
@@ -635,11 +731,12 @@ def main_mod(net, inputdir, savedir, start_id, num_images, device, mod_factors: 
 
 
 def args_lines(args, validate, prep, viz) -> List[str]:
-    """The lines of args.txt.  The flags of validation, pre-processing, scoring and pictures appear only in runs that use them:
+    """The lines of args.txt.  The flags of validation, pre-processing, scoring, pictures and quality appear only in runs that use them:
     without them the file is what it was before they existed."""
     return [f"{k}: {v}\n" for k, v in sorted(vars(args).items())
             if not ((validate is None and k.startswith("validate")) or (prep is None and k in PREP_FLAGS) or
-                    (args.truth is None and k in TRUTH_FLAGS) or (viz is None and k in VIZ_FLAGS))]
+                    (args.truth is None and k in TRUTH_FLAGS) or (viz is None and k in PICTURE_FLAGS) or
+                    (args.quality is None and k in QUALITY_FLAGS))]
 
 
 def load_weights(args) -> Tuple[dict, str]:
@@ -701,7 +798,7 @@ def main(argv: Optional[List[str]] = None) -> int:
             raise SystemExit(f"run.py: {e}")
         prep = (args.background, minmax, floor)
     viz = None
-    if any(getattr(args, k) is not None and getattr(args, k) is not False for k in VIZ_FLAGS):
+    if any(getattr(args, k) is not None and getattr(args, k) is not False for k in PICTURE_FLAGS):
         import math
         if args.brightness is not None or args.contrast is not None:
             raise SystemExit("run.py: --color / --vort-image / --quiver are not available with -b/-c (every combination is a different "
@@ -723,13 +820,23 @@ def main(argv: Optional[List[str]] = None) -> int:
                 raise SystemExit(f"run.py: --quiver: {e}")
         viz = dict(color=args.color, color_max=args.color_max, color_wheel=args.color_wheel, vort_image=args.vort_image,
                    vort_max=args.vort_max, quiver=args.quiver)
+    if args.quality_image and args.quality is None:
+        raise SystemExit("run.py: --quality-image needs --quality")
+    if args.quality is not None:
+        if args.brightness is not None or args.contrast is not None:
+            raise SystemExit("run.py: --quality is not available with -b/-c (every combination is a different experiment)")
+        from pivlfn.quality import check_params as check_quality
+        try:
+            check_quality(args.quality, 1.0 / 255.0, None)
+        except ValueError as e:
+            raise SystemExit(f"run.py: --quality: {e}")
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run.py: this build has no CPU path (the reference's correlation has none either, "
                          "src/correlation.py:339-340); a GPU is required")
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())   # ranks may share a card
     torch.cuda.set_device(device)
-    if args.truth is not None and world > 1:        # the ranks' records and maps meet on rank 0: a small host-side exchange
+    if (args.truth is not None or args.quality is not None) and world > 1:        # the ranks' records and maps meet on rank 0: a small host-side exchange
         import torch.distributed as dist
         if not dist.is_initialized():
             dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -762,10 +869,13 @@ def main(argv: Optional[List[str]] = None) -> int:
                              (truth_paths[imdir], args.truth_levels,
                               os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "errors", 1)[:-4] + ".json"),
                               os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "error_maps", 1)[:-4] + ".npz")),
-                             viz)
+                             viz,
+                             None if args.quality is None else
+                             (args.quality, args.quality_image,
+                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "quality", 1)[:-4] + ".json")))
         else:
             total += main_mod(net, imdir, lay.flow, args.start, args.num_images, device, mods, args.batch, rank, world)
-    if args.truth is not None and world > 1:
+    if (args.truth is not None or args.quality is not None) and world > 1:
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
