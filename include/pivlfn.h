@@ -353,6 +353,36 @@ int pivlfn_match_quality(const float *img1, const float *img2, int C, const floa
                          unsigned char *flag, int B, int H, int W, int radius, int min_count, double floor, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* ---- snapshot POD of a flow sequence: the two device steps of proper orthogonal decomposition by the method of snapshots.  The
+ * eigenproblem of the n x n matrix stays a host job.  Added without an ABI bump (additive).
+ * X: n rows (snapshots) of P fp32 values, row stride ldx >= P floats.  Nothing beyond column P of a row and nothing beyond row n is
+ * read.  Both entry points launch only on `stream`, allocate nothing, never synchronise the host and can be captured into a graph; no
+ * output depends on what G, out or the workspace held before the call.
+ *
+ * pivlfn_snapshot_gram: G ([n,n] fp64, row-major, written completely) with G[i][j] = sum over p of (double)X[i][p] * (double)X[j][p].
+ *   Every product of two fp32 values is exact in fp64, so the only rounding is the summation, done in fp64 by the matrix instruction
+ *   v_mfma_f64_16x16x4_f64 in an order that depends on P alone: P is cut into slabs of PIVLFN_GRAM_SLAB floats; a slab is summed in
+ *   ascending p by one chain of matrix instructions (four consecutive p per instruction) into an accumulator that starts at +0.0;
+ *   G[i][j] = ((+0.0 + S_0) + S_1) + ... over the slab sums in slab order, plain fp64 additions.  Tile padding (rows past n, columns
+ *   past P) is +0.0 in both operands.  Consequences: G[i][j] has the same bits whatever n is, wherever rows i and j sit in X, whatever
+ *   the other rows hold and from run to run;  G[j][i] is G[i][j] bit for bit (the upper triangle is computed and mirrored);  a NaN or
+ *   inf in row i reaches row i and column i of G and nothing else.
+ *   workspace: 8-byte aligned, at least pivlfn_snapshot_gram_workspace_bytes(n, P) bytes (0 for arguments out of range), needs no
+ *   initial contents.  Where G has few 64 x 64 blocks, the slab sums of a block are formed by different workgroups and pass through
+ *   it; the values do not depend on that choice.
+ *   Errors (PIVLFN_ERR_ARG, before any launch): null X / G / workspace, n outside 1..PIVLFN_POD_MAX_SNAPSHOTS, P < 1, P >= 2^31,
+ *   ldx < P, a misaligned or too-small workspace.
+ *
+ * pivlfn_snapshot_project: Wt: [n,K] fp64 row-major on the device;  out: [K,P] fp64;  out[k][p] = the fold over i = 0 .. n-1,
+ *   ascending, of acc = acc + Wt[i][k] * (double)X[i][p] from +0.0, the multiplication and the addition each rounded on its own (no
+ *   fma): a sequential fp64 loop gives the same bits.  X is read once.
+ *   Errors (PIVLFN_ERR_ARG, before any launch): null X / Wt / out, n, P and ldx as above, K outside 1..64. */
+#define PIVLFN_GRAM_SLAB         2048
+#define PIVLFN_POD_MAX_SNAPSHOTS 4096
+size_t pivlfn_snapshot_gram_workspace_bytes(int n, long P);
+int pivlfn_snapshot_gram(const float *X, int n, long P, long ldx, double *G, void *ws, size_t ws_bytes, void *stream);
+int pivlfn_snapshot_project(const float *X, int n, long P, long ldx, const double *Wt, int K, double *out, void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

@@ -238,6 +238,18 @@ int pivlfn_flow_decimate(const float *flow, const unsigned char *mask, float *me
     return launch_flow_decimate(flow, mask, mean, count, B, H, W, cell, (hipStream_t)stream);
 }
 
+size_t pivlfn_snapshot_gram_workspace_bytes(int n, long P) { return snapshot_gram_workspace_bytes(n, P); }
+
+int pivlfn_snapshot_gram(const float *X, int n, long P, long ldx, double *G, void *ws, size_t ws_bytes, void *stream)
+{
+    return launch_snapshot_gram(X, n, P, ldx, G, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int pivlfn_snapshot_project(const float *X, int n, long P, long ldx, const double *Wt, int K, double *out, void *stream)
+{
+    return launch_snapshot_project(X, n, P, ldx, Wt, K, out, (hipStream_t)stream);
+}
+
 int pivlfn_create(const pivlfn_tensor *tensors, int n_tensors, float starting_scale, int lowest_level,
                   const float rgb_mean[6], pivlfn_net **out)
 {

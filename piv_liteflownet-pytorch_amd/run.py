@@ -5,7 +5,7 @@
                 [--weights FILE] [--batch B] [--stats] [--validate flag|mask|replace]
                 [--background min|FILE] [--minmax K] [--minmax-floor N] [--truth DIR [--truth-levels]]
                 [--color [--color-max X] [--color-wheel interp|original]] [--vort-image [--vort-max X]] [--quiver [CELL]]
-                [--quality [R] [--quality-image]]
+                [--quality [R] [--quality-image]] [--pod K [--pod-cell C]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -38,6 +38,11 @@ Differences, all deliberate:
     flow inside (2R+1)^2 windows, and the sub-pixel residual of its peak): <name>_qual.flo with the three bands c, dx, dy, the
     summaries in <save>/quality.json, and with `--quality-image` <name>_corr.png (c on 0..1 in gray, undefined pixels red); with
     --validate flag|mask the rejected vectors are left out of the windows;
+  * `--pod K` decomposes the flows of every input directory after it has been processed (pivlfn.pod.FlowPOD, snapshot POD: the
+    Gram matrix of the flows in float64 on the device, its eigenvectors on the host): the first K modes, the mean, the coefficients
+    and the energy fractions go to <save>/pod.npz, one line per mode is printed, and with --color the modes are drawn as
+    <save>/pod_mode<k>.png; `--pod-cell C` decomposes the means over C x C blocks of vectors.  2..4096 pairs per directory, a
+    single process, not with -b/-c; a rejected vector that leaves a cell empty is refused (use --validate replace or a larger cell);
   * a trailing slash on an input directory is ignored (the reference would name the output directory '');
   * with -b/-c a frame whose file name has no '_' gets the tag appended (<stem>_<BBB>_<CCC>_out.flo) -- the reference splits
     the whole path at its last '_' and then either fails or lets the combinations overwrite each other.
@@ -142,11 +147,18 @@ parser.add_argument("--quality", type=int, nargs="?", const=8, default=None, met
                          "of the windows, with --validate replace the replaced flow is rated")
 parser.add_argument("--quality-image", action="store_true",
                     help="with --quality: also <name>_corr.png, c on 0..1 in gray, pixels without a value in red")
+parser.add_argument("--pod", type=int, default=None, metavar="K",
+                    help="after each input directory, write the first K POD modes of its flows (method of snapshots, pivlfn.pod.FlowPOD: "
+                         "mean, modes, coefficients, energies) to <save>/pod.npz and print their energy fractions; with --color also "
+                         "<save>/pod_mode<k>.png (not a reference flag; not with -b/-c, single process only, at most 4096 pairs)")
+parser.add_argument("--pod-cell", type=int, default=None, metavar="C",
+                    help="with --pod: decompose the means over C x C blocks of vectors (default 1: every vector)")
 PREP_FLAGS = ("background", "minmax", "minmax_floor")
+POD_FLAGS = ("pod", "pod_cell")
 QUALITY_FLAGS = ("quality", "quality_image")
 QUALITY_BAD_RGB = (255, 0, 0)
 PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
-VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS      # every flag of a further per-pair output beside the .flo: absent from args.txt unless used
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + POD_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -261,6 +273,50 @@ class _ValidateEstimate:
             np.savez(path, acc=st.acc.cpu().numpy(), calib=np.float64(st.calib), validation=self.mode, **st.result())
         else:
             self.stats.save(path, validation=self.mode)
+
+
+class _PodEstimate:
+    """An estimate_fn (plain estimate() when `inner` is None) that also stores every batch of flows in a FlowPOD, created at the
+    first batch's size: what the .flo files get after "replace", the raw flow with the flags of `validator` (a _ValidateEstimate) as
+    the mask under "flag" and "mask"."""
+
+    def __init__(self, inner, validator, capacity, cell):
+        self.inner, self.validator, self.capacity, self.cell = inner, validator, capacity, cell
+        self.pod = None
+
+    def __call__(self, net, img1, img2, tensor=True):
+        from pivlfn.inference import estimate
+        from pivlfn.pod import FlowPOD
+        flow = estimate(net, img1, img2, tensor=True) if self.inner is None else self.inner(net, img1, img2, tensor=True)
+        if self.pod is None:
+            H, W = flow.size(2), flow.size(3)
+            need, free = FlowPOD.store_bytes(H, W, self.capacity, self.cell), torch.cuda.mem_get_info(flow.device)[0]
+            if need > free // 2:
+                raise SystemExit(f"run.py: --pod: the store of {self.capacity} snapshots of {H} x {W} takes {need / 2**30:.1f} GiB, more "
+                                 f"than half of the {free / 2**30:.1f} GiB free on the device; decompose block means with --pod-cell C")
+            self.pod = FlowPOD(H, W, self.capacity, self.cell, device=flow.device)
+        if getattr(self.validator, "mode", None) in ("flag", "mask"):
+            self.pod.update(self.validator.last_raw, self.validator.last_flag)
+        else:
+            self.pod.update(flow)
+        return flow
+
+
+def finish_pod(pod, K, pod_file, color):
+    """<save>/pod.npz, one line per mode, and with `color` (the wheel's name) the modes as pod_mode<k>.png beside it."""
+    try:
+        res = pod.solve(K)
+    except ValueError as e:
+        raise SystemExit(f"run.py: --pod: {e}")
+    print(f"POD of {pod.n} flows -> '{res.save(pod_file)}'")
+    for k in range(K):
+        print(f"  mode {k + 1}: {100.0 * res.fraction[k]:6.2f} % of the fluctuation energy")
+    if color is not None:
+        from pivlfn import viz as vz
+        pics = vz.flow_to_color(torch.from_numpy(res.modes.astype("float32")).to(pod.device), None, wheel=color).cpu().numpy()
+        with vz.PngWriter() as pictures:
+            for k in range(K):
+                pictures.submit(pics[k], pod_file[:-4] + f"_mode{k + 1}.png")
 
 
 def write_validation_json(path, est, names):
@@ -627,16 +683,22 @@ def background_min(ds, device, batch):
 
 
 def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch, rank=0, world=1, stats_file=None,
-            validate=None, validation_file=None, prep=None, background_file=None, truth=None, viz=None, quality=None):
+            validate=None, validation_file=None, prep=None, background_file=None, truth=None, viz=None, quality=None, pod=None):
     """Every pair of the folder through `estimate` (reference main_dl, run.py:137-168); with `stats_file`, FlowStats over the
     pairs go there; with `validate` (the keyword arguments of _ValidateEstimate bar `stats`), every flow goes through
     validate_flow before it is copied back and the counts go to `validation_file`.  `prep` = (background, minmax, floor): the
     frames go through pivlfn.preproc.preprocess_frames; a background of "min" is computed from the folder first and written to
     `background_file`.  `truth` = (directory or the truth_files() list of it, levels, errors file, maps file): every flow is scored against its truth file
     (_TruthEstimate).  `viz`: the keyword arguments of _VizEstimate bar `inner` and `validator`: pictures beside the .flo files.
-    `quality` = (radius, image, quality file): every written flow is rated by _QualityEstimate."""
+    `quality` = (radius, image, quality file): every written flow is rated by _QualityEstimate.  `pod` = (modes, cell, pod file,
+    wheel name or None): every written flow is stored by _PodEstimate and decomposed after the folder."""
     os.makedirs(savedir, exist_ok=True)
     ds = Run(root=inputdir, is_pair=is_pair, n_images=num_images, start_at=start_id)
+    if pod is not None and not 2 <= len(ds) <= 4096:
+        raise SystemExit(f"run.py: --pod: '{inputdir}' has {len(ds)} pairs; the method of snapshots here takes 2..4096 (decompose a "
+                         "part of the recording with --start / --num_images)")
+    if pod is not None and pod[0] > len(ds) - 1:
+        raise SystemExit(f"run.py: --pod {pod[0]}: '{inputdir}' has {len(ds)} pairs, which carry at most {len(ds) - 1} modes")
     truth_paths = None
     if truth is not None:          # a list: main() has checked these files already; a directory: check them now
         truth_paths = truth_files(ds, truth[0], truth[1]) if isinstance(truth[0], str) else list(truth[0])
@@ -674,6 +736,10 @@ def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch
         from pivlfn import viz as vz
         run_est = rater = _QualityEstimate(run_est, est if validate is not None else None, painter, quality[0], quality[1])
 
+    podder = None
+    if pod is not None:
+        run_est = podder = _PodEstimate(run_est, est if validate is not None else None, hi - lo, pod[1])
+
     def sink(flow, name, extras=None):
         seen.append(name)
         writer.submit(flow, flowname_modifier(name, savedir, pair=False))
@@ -708,6 +774,8 @@ def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch
             est.save_stats(stats_file)
     elif est is not None and est.stats is not None:
         est.stats.save(stats_file)
+    if podder is not None:
+        finish_pod(podder.pod, pod[0], pod[2], pod[3])
     return hi - lo
 
 
@@ -736,7 +804,7 @@ def args_lines(args, validate, prep, viz) -> List[str]:
     return [f"{k}: {v}\n" for k, v in sorted(vars(args).items())
             if not ((validate is None and k.startswith("validate")) or (prep is None and k in PREP_FLAGS) or
                     (args.truth is None and k in TRUTH_FLAGS) or (viz is None and k in PICTURE_FLAGS) or
-                    (args.quality is None and k in QUALITY_FLAGS))]
+                    (args.quality is None and k in QUALITY_FLAGS) or (args.pod is None and k in POD_FLAGS))]
 
 
 def load_weights(args) -> Tuple[dict, str]:
@@ -755,6 +823,17 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.stats and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("run.py: --stats needs a single process (run.py has no process group to merge the statistics; "
                          "the sharded path for statistics is pivlfn.sequence.run_sequence)")
+    if args.pod_cell is not None and args.pod is None:
+        raise SystemExit("run.py: --pod-cell needs --pod")
+    if args.pod is not None:
+        if args.brightness is not None or args.contrast is not None:
+            raise SystemExit("run.py: --pod is not available with -b/-c (every combination is a different experiment)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("run.py: --pod needs a single process (the snapshots of one decomposition live on one device)")
+        if not 1 <= args.pod <= 64:
+            raise SystemExit(f"run.py: --pod {args.pod}: the number of modes must be 1..64")
+        if args.pod_cell is not None and not 1 <= args.pod_cell <= 32768:
+            raise SystemExit(f"run.py: --pod-cell {args.pod_cell}: the cell must be 1..32768")
     validate = None
     if args.validate is not None:
         if args.brightness is not None or args.contrast is not None:
@@ -872,7 +951,11 @@ def main(argv: Optional[List[str]] = None) -> int:
                              viz,
                              None if args.quality is None else
                              (args.quality, args.quality_image,
-                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "quality", 1)[:-4] + ".json")))
+                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "quality", 1)[:-4] + ".json")),
+                             None if args.pod is None else
+                             (args.pod, args.pod_cell or 1,
+                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "pod", 1)[:-4] + ".npz"),
+                              (args.color_wheel or "interp") if args.color else None))
         else:
             total += main_mod(net, imdir, lay.flow, args.start, args.num_images, device, mods, args.batch, rank, world)
     if (args.truth is not None or args.quality is not None) and world > 1:
