@@ -162,10 +162,10 @@ class FlowStats:
         """finalize() of the current sums: count, mean_u, mean_v, rms_u, rms_v, cov_uv, mean_vort, rms_vort."""
         return finalize(self.acc.cpu().numpy(), self.count)
 
-    def save(self, path: str) -> str:
-        """An .npz with result()'s arrays, the raw accumulators (`acc`, SUMS order) and `calib`; returns the path written."""
+    def save(self, path: str, **extra) -> str:
+        """An .npz with result()'s arrays, the raw accumulators (`acc`, SUMS order), `calib` and `extra`; returns the path written."""
         res = self.result()
         if not path.endswith(".npz"):
             path += ".npz"
-        np.savez(path, acc=self.acc.cpu().numpy(), calib=np.float64(self.calib), **res)
+        np.savez(path, acc=self.acc.cpu().numpy(), calib=np.float64(self.calib), **extra, **res)
         return path

@@ -48,25 +48,39 @@ Differences, all deliberate:
     the whole path at its last '_' and then either fails or lets the combinations overwrite each other.
 """
 import argparse
+import json
+import math
 import os
+import struct
 import sys
-from dataclasses import dataclass
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass, field
 from types import SimpleNamespace
 from itertools import product
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.realpath(__file__))
 sys.path.insert(0, HERE)
 
 from pivlfn import Network                               # noqa: E402
-from pivlfn import synth                                 # noqa: E402
+from pivlfn import quality, synth, viz                   # noqa: E402
 from pivlfn.datasets import Run, image_files_from_folder, pair_files     # noqa: E402
 from pivlfn.dist import shard_bounds                     # noqa: E402
+from pivlfn.evaluate import ErrorStats, flow_errors, level_errors        # noqa: E402
 from pivlfn.flo import FloWriter, flowname_modifier      # noqa: E402
 from pivlfn.imagemod import mod_name                     # noqa: E402
+from pivlfn.inference import estimate                    # noqa: E402
 from pivlfn.pipeline import PairLoader, stream_pairs     # noqa: E402
+from pivlfn.pod import FlowPOD                           # noqa: E402
+from pivlfn.postpro import FlowStats                     # noqa: E402
+from pivlfn.preproc import FrameBackground, Preprocessor                 # noqa: E402
+from pivlfn.preproc import check_params as check_prep    # noqa: E402
+from pivlfn.validate import NOT_REPLACED, OUTLIER, UNKNOWN, MaskedFlowStats, validate_flow      # noqa: E402
+from pivlfn.validate import check_params as check_validate               # noqa: E402
 
 parser = argparse.ArgumentParser(description="Inferencing script for LiteFlowNet (MI355X-native path)")
 parser.add_argument("--start", "-s", type=int, default=0, help="Input image starting index.")
@@ -162,6 +176,11 @@ VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + POD_FLAGS      # every flag of a fur
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
+def _used(args, flags) -> bool:
+    """Whether the command line sets any flag of the group."""
+    return any(getattr(args, k) is not None and getattr(args, k) is not False for k in flags)
+
+
 @dataclass(frozen=True)
 class OutputLayout:
     """Where the results of one input directory go."""
@@ -181,11 +200,11 @@ class OutputLayout:
                             flow=os.path.join(save, "flow", side) if side else os.path.join(save, "flow"),
                             args_file=os.path.join(save, f"args_{side}.txt" if side else "args.txt"))
 
-
-def output_dirs(args, imdir, netname):
-    """(save, flow dir, args file name) for one input directory."""
-    lay = OutputLayout.of(args.output, netname, imdir, args.start, args.num_images)
-    return lay.save, lay.flow, os.path.basename(lay.args_file)
+    def sibling(self, name: str) -> str:
+        """A file beside args[_left|_right].txt: "stats.npz" -> <save>/stats.npz (stats_left / stats_right.npz for the halves of a
+        stereo set)."""
+        stem, ext = os.path.splitext(name)
+        return os.path.join(self.save, stem + os.path.basename(self.args_file)[len("args"):-len(".txt")] + ext)
 
 
 class _FrameSequence:
@@ -214,231 +233,169 @@ def mod_flow_name(first_frame: str, savedir: str, mod: Tuple[float, float]) -> s
     return flowname_modifier(tagged, savedir, pair=False)
 
 
-class _StatsEstimate:
-    """estimate() that also adds every batch of flows to a FlowStats, created at the first batch's size (stream_pairs' estimate_fn)."""
+def checked(prefix, check, *params):
+    """check(*params), its ValueError turned into the SystemExit of a refused command line."""
+    try:
+        return check(*params)
+    except ValueError as e:
+        raise SystemExit(f"run.py: {prefix}{e}")
 
-    def __init__(self):
-        self.stats = None
+
+def json_strict(x):
+    """JSON has no NaN or Infinity: null stands for every value that is not finite."""
+    if isinstance(x, dict):
+        return {k: json_strict(v) for k, v in x.items()}
+    if isinstance(x, list):
+        return [json_strict(v) for v in x]
+    return None if isinstance(x, float) and not math.isfinite(x) else x
+
+
+def write_json(path, doc, **kw):
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1, **kw)
+        f.write("\n")
+
+
+def gather_rows(names, rows, world):
+    """(the names of all ranks, [every rank's `rows`]), both in rank order -- the shards are contiguous, so that is pair order.
+    Sharded runs (world > 1) need a process group."""
+    if world == 1:
+        return names, [rows]
+    import torch.distributed as dist
+    parts = [None] * world
+    dist.all_gather_object(parts, (names, rows))
+    return [n for p in parts for n in p[0]], [p[1] for p in parts]
+
+
+def _cat(parts):
+    """The per-batch records of a stage, kept on the device until now, as one host tensor in pair order (None without a batch)."""
+    return torch.cat(parts).cpu() if parts else None
+
+
+# ---- one forward, then the stages ----------------------------------------------------------------------------------------------------
+@dataclass
+class Batch:
+    """What one forward produced, all on the device."""
+    img1: torch.Tensor                      # the tensors the network was given
+    img2: torch.Tensor
+    raw: torch.Tensor                       # the network's flow
+    flow: torch.Tensor                      # what the .flo files get: `raw` unless validation masks or replaces
+    flag: Optional[torch.Tensor] = None     # the validator's flags
+    mode: Optional[str] = None              # the validation mode
+    levels: Optional[list] = None           # the per-level flows of the same forward, if a stage asked for them
+    extras: dict = field(default_factory=dict)      # name -> tensor [n, ...] that returns to the host with the flows
+
+    def masked(self):
+        """(flow, mask) for what looks at the vectors that passed: under "flag" and "mask" the raw flow with the flags as the mask,
+        otherwise (no validation, or "replace") the written flow and no mask."""
+        return (self.raw, self.flag) if self.mode in ("flag", "mask") else (self.flow, None)
+
+
+class Stage:
+    """One further output of run.py.  The Estimator calls begin() before every forward and the stage itself after it, in the order of
+    its list; the stage enqueues on the current stream and never synchronises the host.  main_dl calls finish() after the directory
+    (`names`: the pairs of this rank in order; `ctx`: rank, world, device) and close() whatever happened."""
+    levels = False          # wants Batch.levels
+    extras = False          # puts per-pair outputs into Batch.extras
+
+    def begin(self, n, device):
+        pass
+
+    def __call__(self, batch):
+        pass
+
+    def finish(self, names, ctx):
+        pass
+
+    def close(self):
+        pass
+
+
+class _LevelsNet:
+    """Stands in for the network inside estimate(): the same forward, with the per-level flows of the last call kept."""
+
+    def __init__(self, net):
+        self.net, self.training, self.levels = net, False, None
+
+    def eval(self):
+        return self
+
+    def __call__(self, a, b):
+        out, self.levels = self.net.forward_levels(a, b)
+        return out
+
+
+class Estimator:
+    """stream_pairs' estimate_fn: one forward per batch, then every stage on its Batch; extras() is stream_pairs' hook of that name."""
+
+    def __init__(self, stages, estimate=estimate):
+        self.stages, self.estimate = list(stages), estimate
+        self.levels = any(s.levels for s in self.stages)
+        self.batch = None
 
     def __call__(self, net, img1, img2, tensor=True):
-        from pivlfn.inference import estimate
-        from pivlfn.postpro import FlowStats
-        flow = estimate(net, img1, img2, tensor=True)
-        if self.stats is None:
-            self.stats = FlowStats(flow.size(2), flow.size(3), device=flow.device)
-        self.stats.update(flow)
-        return flow
+        for stage in self.stages:
+            stage.begin(img1.size(0), img1.device)
+        run_net = _LevelsNet(net) if self.levels else net          # estimate()'s resize logic stays the single code path
+        raw = self.estimate(run_net, img1, img2, tensor=True)
+        self.batch = Batch(img1, img2, raw, raw, levels=run_net.levels if self.levels else None)
+        for stage in self.stages:
+            stage(self.batch)
+        return self.batch.flow
+
+    def extras(self):
+        return self.batch.extras
 
 
-class _ValidateEstimate:
-    """estimate() followed by validate_flow on the device (stream_pairs' estimate_fn): returns what the .flo files get -- the flow
-    itself for "flag", the masked / replaced flow otherwise.  The per-pair counts of the three flag bits are reduced on the device
-    and stay there until counts() copies them once; with `stats`, "flag" and "mask" feed (raw flow, flag) to a MaskedFlowStats and
-    "replace" feeds the replaced flow to a FlowStats."""
+class Validate(Stage):
+    """validate_flow on the device: sets what the .flo files get -- the flow itself for "flag", the masked / replaced flow otherwise.
+    The per-pair counts of the three flag bits are reduced on the device and stay there until finish() copies them once."""
 
-    def __init__(self, mode, radius, spacing, eps, thresh, stats):
-        self.mode, self.params, self.want_stats = mode, dict(radius=radius, spacing=spacing, eps=eps, thresh=thresh), stats
-        self.stats = None
+    def __init__(self, mode, radius, spacing, eps, thresh, file):
+        self.mode, self.params, self.file = mode, dict(radius=radius, spacing=spacing, eps=eps, thresh=thresh), file
         self._counts = []
 
-    def __call__(self, net, img1, img2, tensor=True):
-        from pivlfn.inference import estimate
-        from pivlfn.postpro import FlowStats
-        from pivlfn.validate import NOT_REPLACED, OUTLIER, UNKNOWN, MaskedFlowStats, validate_flow
-        flow = estimate(net, img1, img2, tensor=True)
-        res = validate_flow(flow, mode=self.mode, **self.params)
-        self.last_raw, self.last_flag = flow, res.flag          # what --truth scores for "flag" and "mask"
+    def __call__(self, batch):
+        res = validate_flow(batch.raw, mode=self.mode, **self.params)
+        batch.flow, batch.flag, batch.mode = res.flow, res.flag, self.mode
         flat = res.flag.flatten(1)
         self._counts.append(torch.stack([(flat & bit).ne(0).sum(1) for bit in (OUTLIER, UNKNOWN, NOT_REPLACED)], dim=1))
-        if self.want_stats:
-            if self.stats is None:
-                kind = FlowStats if self.mode == "replace" else MaskedFlowStats
-                self.stats = kind(flow.size(2), flow.size(3), device=flow.device)
-            if self.mode == "replace":
-                self.stats.update(res.flow)
-            else:
-                self.stats.update(flow, res.flag)
-        return res.flow
 
-    def counts(self):
-        """[pairs, 3] int64 on the host: outlier, unknown, not-replaced vectors of each pair, in the order of the pairs."""
-        if not self._counts:
-            return torch.zeros([0, 3], dtype=torch.int64)
-        return torch.cat(self._counts).cpu()
-
-    def save_stats(self, path):
-        import numpy as np
-        if self.mode == "replace":            # FlowStats.save's fields, and which validation the flows went through
-            st = self.stats
-            np.savez(path, acc=st.acc.cpu().numpy(), calib=np.float64(st.calib), validation=self.mode, **st.result())
-        else:
-            self.stats.save(path, validation=self.mode)
+    def finish(self, names, ctx):
+        """<save>/validation.json: the parameters, per pair name the counts of outlier / unknown / not-replaced vectors, the totals."""
+        rows = _cat(self._counts).tolist() if self._counts else []
+        assert len(rows) == len(names)
+        keys = ("outlier", "unknown", "not_replaced")
+        write_json(self.file, {"mode": self.mode, **self.params,
+                               "pairs": {name: dict(zip(keys, row)) for name, row in zip(names, rows)},
+                               "total": {k: sum(row[i] for row in rows) for i, k in enumerate(keys)}})
 
 
-class _PodEstimate:
-    """An estimate_fn (plain estimate() when `inner` is None) that also stores every batch of flows in a FlowPOD, created at the
-    first batch's size: what the .flo files get after "replace", the raw flow with the flags of `validator` (a _ValidateEstimate) as
-    the mask under "flag" and "mask"."""
+class Stats(Stage):
+    """Adds every batch of flows to a FlowStats, created at the first batch's size; after "flag" and "mask" (raw flow, flag) go to a
+    MaskedFlowStats instead, after "replace" the FlowStats gets the replaced flow.  The file says which validation the flows went
+    through."""
 
-    def __init__(self, inner, validator, capacity, cell):
-        self.inner, self.validator, self.capacity, self.cell = inner, validator, capacity, cell
-        self.pod = None
+    def __init__(self, file):
+        self.file, self.stats, self.extra = file, None, {}
 
-    def __call__(self, net, img1, img2, tensor=True):
-        from pivlfn.inference import estimate
-        from pivlfn.pod import FlowPOD
-        flow = estimate(net, img1, img2, tensor=True) if self.inner is None else self.inner(net, img1, img2, tensor=True)
-        if self.pod is None:
-            H, W = flow.size(2), flow.size(3)
-            need, free = FlowPOD.store_bytes(H, W, self.capacity, self.cell), torch.cuda.mem_get_info(flow.device)[0]
-            if need > free // 2:
-                raise SystemExit(f"run.py: --pod: the store of {self.capacity} snapshots of {H} x {W} takes {need / 2**30:.1f} GiB, more "
-                                 f"than half of the {free / 2**30:.1f} GiB free on the device; decompose block means with --pod-cell C")
-            self.pod = FlowPOD(H, W, self.capacity, self.cell, device=flow.device)
-        if getattr(self.validator, "mode", None) in ("flag", "mask"):
-            self.pod.update(self.validator.last_raw, self.validator.last_flag)
-        else:
-            self.pod.update(flow)
-        return flow
+    def __call__(self, batch):
+        flow, flag = batch.masked()
+        if self.stats is None:
+            kind = FlowStats if flag is None else MaskedFlowStats
+            self.stats = kind(flow.size(2), flow.size(3), device=flow.device)
+            self.extra = {} if batch.mode is None else {"validation": batch.mode}
+        self.stats.update(*((flow,) if flag is None else (flow, flag)))
 
-
-def finish_pod(pod, K, pod_file, color):
-    """<save>/pod.npz, one line per mode, and with `color` (the wheel's name) the modes as pod_mode<k>.png beside it."""
-    try:
-        res = pod.solve(K)
-    except ValueError as e:
-        raise SystemExit(f"run.py: --pod: {e}")
-    print(f"POD of {pod.n} flows -> '{res.save(pod_file)}'")
-    for k in range(K):
-        print(f"  mode {k + 1}: {100.0 * res.fraction[k]:6.2f} % of the fluctuation energy")
-    if color is not None:
-        from pivlfn import viz as vz
-        pics = vz.flow_to_color(torch.from_numpy(res.modes.astype("float32")).to(pod.device), None, wheel=color).cpu().numpy()
-        with vz.PngWriter() as pictures:
-            for k in range(K):
-                pictures.submit(pics[k], pod_file[:-4] + f"_mode{k + 1}.png")
-
-
-def write_validation_json(path, est, names):
-    """<save>/validation.json: the parameters, per pair name the counts of outlier / unknown / not-replaced vectors, the totals."""
-    import json
-    rows = est.counts().tolist()
-    assert len(rows) == len(names)
-    keys = ("outlier", "unknown", "not_replaced")
-    doc = {"mode": est.mode, **est.params,
-           "pairs": {name: dict(zip(keys, row)) for name, row in zip(names, rows)},
-           "total": {k: sum(row[i] for row in rows) for i, k in enumerate(keys)}}
-    with open(path, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-
-
-class _VizEstimate:
-    """An estimate_fn (plain estimate() when `inner` is None) that also makes the pictures of every batch on the device, right after
-    the flows and on the same stream: `extras()` hands them to stream_pairs, which copies them back with the flows.  `validator`: the
-    _ValidateEstimate inside, if any; under "flag" and "mask" the pictures show its raw flow with its flags as the mask (what is
-    rejected is black, stays out of the normalisers and out of the arrows), under "replace" the replaced flow."""
-
-    def __init__(self, inner, validator, color, color_max, color_wheel, vort_image, vort_max, quiver):
-        self.inner, self.validator = inner, validator
-        self.color, self.color_max, self.color_wheel = color, color_max, color_wheel or "interp"
-        self.vort_image, self.vort_max, self.quiver = vort_image, vort_max, quiver
-        self.last = {}
-
-    def __call__(self, net, img1, img2, tensor=True):
-        from pivlfn import viz
-        from pivlfn.inference import estimate
-        flow = estimate(net, img1, img2, tensor=True) if self.inner is None else self.inner(net, img1, img2, tensor=True)
-        shown, mask = flow, None
-        if getattr(self.validator, "mode", None) in ("flag", "mask"):
-            shown, mask = self.validator.last_raw, self.validator.last_flag
-        self.last = {}
-        if self.color:
-            self.last["color"] = viz.flow_to_color(shown, self.color_max, wheel=self.color_wheel, mask=mask)
-        if self.vort_image:
-            self.last["vort"] = viz.vorticity_image(shown, vmax=self.vort_max, mask=mask)
-        if self.quiver is not None:
-            cell = self.quiver or viz.quiver_cell(flow.size(2), flow.size(3))
-            self.last["quiver_mean"], self.last["quiver_count"] = viz.decimate_flow(shown, cell, mask)
-        return flow
-
-    def extras(self):
-        return self.last
-
-
-class _QualityEstimate:
-    """An estimate_fn (plain estimate() when `inner` is None) that also rates every batch of flows on the device, right after them
-    and on the same stream: match_quality of the frames the network was given and the flow that is returned (what the .flo files
-    get), with the flags of `validator` (a _ValidateEstimate under "flag" or "mask") as the mask.  `extras()` hands the three
-    bands -- and the picture of c, with `image` -- to stream_pairs beside those of `painter` (a _VizEstimate, if any); the per-pair
-    sums stay on the device until sums() copies them once."""
-
-    def __init__(self, inner, validator, painter, radius, image):
-        from pivlfn.quality import check_params
-        self.inner, self.validator, self.painter, self.radius, self.image = inner, validator, painter, radius, image
-        self.floor = 1.0 / 255.0
-        self.min_count = check_params(radius, self.floor, None)
-        self.last, self._sums = {}, []
-
-    @property
-    def mode(self):
-        return getattr(self.validator, "mode", None)
-
-    def __call__(self, net, img1, img2, tensor=True):
-        from pivlfn import viz
-        from pivlfn.inference import estimate
-        from pivlfn.quality import match_quality
-        flow = estimate(net, img1, img2, tensor=True) if self.inner is None else self.inner(net, img1, img2, tensor=True)
-        mask = self.validator.last_flag if self.mode in ("flag", "mask") else None
-        q = match_quality(img1, img2, flow, self.radius, mask, self.floor, self.min_count)
-        self._sums.append(q.sums())
-        self.last = {"qual": torch.cat([q.c.unsqueeze(1), q.residual], dim=1).permute(0, 2, 3, 1)}      # the .flo layout
-        if self.image:
-            self.last["corr"] = viz.scalar_to_color(q.c.contiguous(), 0.0, 1.0, cmap="gray", bad=QUALITY_BAD_RGB)
-        return flow
-
-    def extras(self):
-        return {**(self.painter.extras() if self.painter is not None else {}), **self.last}
-
-    def sums(self):
-        """[pairs, 9] float64 on the host (pivlfn.quality.SUMS), in the order of the pairs."""
-        if not self._sums:
-            return torch.zeros([0, 9], dtype=torch.float64)
-        return torch.cat(self._sums).cpu()
-
-
-def write_quality_json(path, rater, names, rank, world):
-    """<save>/quality.json: the parameters, per pair name the summary of MatchQuality.summary(), and the same over the run, formed from
-    the per-pair sums in pair order.  Sharded runs (world > 1, a process group exists): the records of all ranks are gathered in rank
-    order -- the shards are contiguous, so that is pair order -- and rank 0 writes.  A value that is not finite is written as null."""
-    import json
-    import math
-    from pivlfn.quality import summarize
-    rows = rater.sums().tolist()
-    assert len(rows) == len(names)
-    if world > 1:
-        import torch.distributed as dist
-        parts = [None] * world
-        dist.all_gather_object(parts, (names, rows))
-        names, rows = [n for p in parts for n in p[0]], [r for p in parts for r in p[1]]
-    if rank != 0:
-        return
-    total = [0.0] * 9
-    for row in rows:
-        total = [a + b for a, b in zip(total, row)]
-    strict = lambda d: {k: (None if isinstance(v, float) and not math.isfinite(v) else v) for k, v in d.items()}      # noqa: E731
-    doc = {"radius": rater.radius, "floor": rater.floor, "min_count": rater.min_count, "mask": rater.mode if rater.mode in ("flag", "mask") else None,
-           "pairs": {name: strict(summarize(row)) for name, row in zip(names, rows)}, "total": strict(summarize(total))}
-    with open(path, "w") as f:
-        json.dump(doc, f, indent=1, allow_nan=False)
-        f.write("\n")
+    def finish(self, names, ctx):
+        if self.stats is not None:
+            self.stats.save(self.file, **self.extra)
 
 
 def truth_files(ds, truth_dir, levels=False):
     """The truth file of every pair of `ds` (a Run), DIR/<stem>_flow.flo with the stem flowname_modifier gives the flow file.  Every
     file must exist and have the size of the pair's first frame (a multiple of 32 both ways for `levels`): checked here, from the
     headers alone, before anything is launched."""
-    import struct
     import PIL.Image
     paths = []
     for name, pair in zip(ds.name_list, ds.image_list):
@@ -466,16 +423,12 @@ class _TruthPrefetch:
     thread going through read_flow, a host transpose and pin_memory() -- four passes over it -- held the fp16 loop back."""
 
     def __init__(self, paths, pin, depth=8, workers=4):
-        from collections import deque
-        from concurrent.futures import ThreadPoolExecutor
         self.paths, self.pin, self.depth, self.at = list(paths), pin, depth, 0
         self.pool = ThreadPoolExecutor(max_workers=workers)
         self.pending = deque()
         self._fill()
 
     def _read(self, path):
-        import struct
-        import numpy as np
         with open(path, "rb") as f:
             w, h = struct.unpack("<ii", f.read(12)[4:])
             buf = torch.empty([h, w, 2], dtype=torch.float32, pin_memory=self.pin)
@@ -502,78 +455,70 @@ class _TruthPrefetch:
         self.pool.shutdown(wait=True)
 
 
-class _LevelsNet:
-    """Stands in for the network inside estimate(): the same forward, with the per-level flows of the last call kept."""
+class Truth(Stage):
+    """Scores every flow against the next truth field (`paths`: the truth_files() of this rank's pairs) on the device: per-pair sums
+    (pivlfn.evaluate.flow_errors) stay there until finish() copies them once, and an ErrorStats collects the per-pixel maps.  After
+    "flag" and "mask" the raw flow is scored with the flags as the mask, after "replace" the replaced flow.  `levels`: also
+    level_errors on the per-level flows of the same forward; as Stage.levels it is also what makes the Estimator keep them."""
 
-    def __init__(self, net):
-        self.net, self.training, self.levels = net, False, None
-
-    def eval(self):
-        return self
-
-    def __call__(self, a, b):
-        out, self.levels = self.net.forward_levels(a, b)
-        return out
-
-
-class _TruthEstimate:
-    """An estimate_fn (plain estimate() when `inner` is None) whose flows are scored against the next truth fields on the device before
-    they are returned: per-pair sums (pivlfn.evaluate.flow_errors) stay on the device until records() copies them once, and an
-    ErrorStats collects the per-pixel maps.  With a _ValidateEstimate inside, "flag" and "mask" score the raw flow with the flags
-    as the mask, "replace" scores the replaced flow.  `levels`: also level_errors on the per-level flows of the same forward."""
-
-    def __init__(self, paths, inner, levels, div_flow, pin):
-        self.inner, self.levels, self.div_flow = inner, levels, div_flow
+    def __init__(self, net, paths, levels, errors_file, maps_file, pin):
+        self.net, self.levels, self.errors_file, self.maps_file = net, levels, errors_file, maps_file
+        self.div_flow = 1.0 / (5.0 if net.starting_scale == 10 else 20.0)
         self.prefetch = _TruthPrefetch(paths, pin)
         self.copy = None                                        # the truth goes up on its own stream, under the forward
-        self.stats = None
+        self.stats, self.mode = None, None
         self._sums, self._excluded, self._level_sums = [], [], []
 
-    def __call__(self, net, img1, img2, tensor=True):
-        from pivlfn.evaluate import ErrorStats, flow_errors, level_errors
-        from pivlfn.inference import estimate
-        dev = img1.device
-        main = torch.cuda.current_stream(dev)
+    def begin(self, n, device):
         if self.copy is None:
-            self.copy = torch.cuda.Stream(dev)
+            self.copy = torch.cuda.Stream(device)
         with torch.cuda.stream(self.copy):
-            raw = torch.stack([t.to(dev, non_blocking=True) for t in self.prefetch.take(img1.size(0))])        # [n,H,W,2]
-        run_net = _LevelsNet(net) if self.levels else net
-        flow = estimate(run_net, img1, img2, tensor=True) if self.inner is None else self.inner(run_net, img1, img2, tensor=True)
+            self.raw = torch.stack([t.to(device, non_blocking=True) for t in self.prefetch.take(n)])        # [n,H,W,2]
+
+    def __call__(self, batch):
+        main = torch.cuda.current_stream(batch.raw.device)
         main.wait_stream(self.copy)
-        raw.record_stream(main)
-        truth = raw.permute(0, 3, 1, 2).contiguous()
-        scored, mask = flow, None
-        mode = getattr(self.inner, "mode", None)
-        if mode in ("flag", "mask"):
-            scored, mask = self.inner.last_raw, self.inner.last_flag
+        self.raw.record_stream(main)
+        truth = self.raw.permute(0, 3, 1, 2).contiguous()
+        scored, mask = batch.masked()
+        self.mode = batch.mode
+        if mask is not None:
             self._excluded.append(mask.flatten(1).ne(0).sum(1))
         err = flow_errors(scored, truth, mask)
         self._sums.append(torch.stack(list(err[:7]), dim=1))
         if self.stats is None:
-            self.stats = ErrorStats(flow.size(2), flow.size(3), device=dev)
+            self.stats = ErrorStats(scored.size(2), scored.size(3), device=scored.device)
         self.stats.update(scored, truth, mask)
         if self.levels:
-            table = level_errors(net, run_net.levels, truth, self.div_flow, mask)
+            table = level_errors(self.net, batch.levels, truth, self.div_flow, mask)
             self._level_sums.append(torch.stack([torch.stack([torch.stack(list(e[:7]), dim=1) for e in row], dim=1) for row in table],
                                                 dim=1))
-        return flow
 
     def close(self):
         self.prefetch.close()
 
-    def records(self):
-        """([pairs,7] float64 sums, [pairs] excluded counts or None, [pairs,nlev,3,7] level sums or None), on the host."""
-        cat = lambda parts: torch.cat(parts).cpu() if parts else None      # noqa: E731
-        return cat(self._sums), cat(self._excluded), cat(self._level_sums)
+    def finish(self, names, ctx):
+        """Writes errors.json and error_maps.npz.  Sharded runs: the per-pair records of all ranks are gathered (gather_rows), the
+        maps are merged (ErrorStats.merge), and rank 0 writes."""
+        size = None if self.stats is None else (self.stats.H, self.stats.W)
+        names, parts = gather_rows(names, (_cat(self._sums), _cat(self._excluded), _cat(self._level_sums), size), ctx.world)
+        sums, excluded, levels = (torch.cat([p[i] for p in parts if p[i] is not None]) if any(p[i] is not None for p in parts) else None
+                                  for i in (0, 1, 2))
+        size = next((p[3] for p in parts if p[3] is not None), None)
+        if ctx.world > 1 and size is not None:
+            if self.stats is None:                              # a rank without pairs still takes part in the merge
+                self.stats = ErrorStats(size[0], size[1], device=ctx.device)
+            self.stats.merge()
+        if ctx.rank == 0:
+            write_errors_json(self.errors_file, names, sums, excluded, levels, self.mode, self.div_flow)      # validation: one process
+            if self.stats is not None and self.stats.count > 0:
+                self.stats.save(self.maps_file)
 
 
 def write_errors_json(path, names, sums, excluded, levels, mode, div_flow):
     """<save>/errors.json: per pair name n, aee, rmse, l1, bias_u, bias_v, max (pixels; null where the value is not finite: nothing
     scored, or a non-finite estimated flow); the totals over the run, formed from the per-pair sums in pair order; with --validate flag|mask the vectors left out; with --truth-levels the level x stage AEE tables.
-    sums [pairs,7], excluded [pairs] or None, levels [pairs,nlev,3,7] or None: host tensors (_TruthEstimate.records)."""
-    import json
-    import math
+    sums [pairs,7], excluded [pairs] or None, levels [pairs,nlev,3,7] or None: host tensors (Truth.finish)."""
     rows = sums.tolist() if sums is not None else []
     assert len(rows) == len(names)
 
@@ -597,48 +542,148 @@ def write_errors_json(path, names, sums, excluded, levels, mode, div_flow):
         aee = (tot[:, :, 2] / tot[:, :, 0]).tolist()            # [nlev][3] in level units (flow * div_flow at that level's resolution)
         doc["levels"] = {"div_flow": div_flow, "stages": ["M", "S", "R"], "levels": [6 - i for i in range(len(aee))],
                          "aee_level_units": aee, "aee_px": [[v / div_flow for v in row] for row in aee]}
-    def strict(x):                  # JSON has no NaN or Infinity: null stands for every value that is not finite
-        if isinstance(x, dict):
-            return {k: strict(v) for k, v in x.items()}
-        if isinstance(x, list):
-            return [strict(v) for v in x]
-        return None if isinstance(x, float) and not math.isfinite(x) else x
-    with open(path, "w") as f:
-        json.dump(strict(doc), f, indent=1, allow_nan=False)
-        f.write("\n")
+    write_json(path, json_strict(doc), allow_nan=False)
 
 
-def finish_truth(scorer, names, errors_file, maps_file, rank, world, device):
-    """Writes errors.json and error_maps.npz.  Sharded runs (world > 1, a process group exists): the per-pair records of all ranks
-    are gathered in rank order -- the shards are contiguous, so that is pair order -- the maps are merged (ErrorStats.merge), and
-    rank 0 writes."""
-    sums, excluded, levels = scorer.records()
-    mode = getattr(scorer.inner, "mode", None)
-    size = None if scorer.stats is None else (scorer.stats.H, scorer.stats.W)
-    if world > 1:
-        import torch.distributed as dist
-        from pivlfn.evaluate import ErrorStats
-        parts = [None] * world
-        dist.all_gather_object(parts, (names, sums, excluded, levels, size))
-        names = [n for p in parts for n in p[0]]
-        sums, excluded, levels = (torch.cat([p[i] for p in parts if p[i] is not None]) if any(p[i] is not None for p in parts) else None
-                                  for i in (1, 2, 3))
-        size = next((p[4] for p in parts if p[4] is not None), None)
-        if size is not None:
-            if scorer.stats is None:                            # a rank without pairs still takes part in the merge
-                scorer.stats = ErrorStats(size[0], size[1], device=device)
-            scorer.stats.merge()
-    if rank == 0:
-        write_errors_json(errors_file, names, sums, excluded, levels, mode, scorer.div_flow)
-        if scorer.stats is not None and scorer.stats.count > 0:
-            scorer.stats.save(maps_file)
+class Pictures(Stage):
+    """Makes the pictures of every batch on the device, right after the flows and on the same stream; they go back to the host with
+    the flows.  After "flag" and "mask" the pictures show the raw flow with the flags as the mask (what is rejected is black, stays
+    out of the normalisers and out of the arrows), after "replace" the replaced flow."""
+    extras = True
+
+    def __init__(self, color, color_max, color_wheel, vort_image, vort_max, quiver):
+        self.color, self.color_max, self.color_wheel = color, color_max, color_wheel or "interp"
+        self.vort_image, self.vort_max, self.quiver = vort_image, vort_max, quiver
+
+    def cell(self, H, W):
+        return self.quiver or viz.quiver_cell(H, W)
+
+    def __call__(self, batch):
+        shown, mask = batch.masked()
+        if self.color:
+            batch.extras["color"] = viz.flow_to_color(shown, self.color_max, wheel=self.color_wheel, mask=mask)
+        if self.vort_image:
+            batch.extras["vort"] = viz.vorticity_image(shown, vmax=self.vort_max, mask=mask)
+        if self.quiver is not None:
+            batch.extras["quiver_mean"], batch.extras["quiver_count"] = viz.decimate_flow(shown, self.cell(*shown.shape[2:]), mask)
+
+
+class Quality(Stage):
+    """Rates every batch of flows on the device, right after them and on the same stream: match_quality of the frames the network
+    was given and the flow that is written, with the flags of "flag" or "mask" as the mask.  The three bands -- and the picture of
+    c, with `image` -- go back to the host with the flows; the per-pair sums (pivlfn.quality.SUMS) stay on the device until finish()
+    copies them once."""
+    extras = True
+
+    def __init__(self, radius, image, file, mask=None):
+        self.radius, self.image, self.file, self.mask = radius, image, file, mask      # mask: "flag", "mask" or None, for quality.json
+        self.floor = 1.0 / 255.0
+        self.min_count = quality.check_params(radius, self.floor, None)
+        self._sums = []
+
+    def __call__(self, batch):
+        q = quality.match_quality(batch.img1, batch.img2, batch.flow, self.radius, batch.masked()[1], self.floor, self.min_count)
+        self._sums.append(q.sums())
+        batch.extras["qual"] = torch.cat([q.c.unsqueeze(1), q.residual], dim=1).permute(0, 2, 3, 1)      # the .flo layout
+        if self.image:
+            batch.extras["corr"] = viz.scalar_to_color(q.c.contiguous(), 0.0, 1.0, cmap="gray", bad=QUALITY_BAD_RGB)
+
+    def finish(self, names, ctx):
+        """<save>/quality.json: the parameters, per pair name the summary of MatchQuality.summary(), and the same over the run, formed
+        from the per-pair sums in pair order.  Sharded runs: the records of all ranks are gathered (gather_rows) and rank 0 writes.
+        A value that is not finite is written as null."""
+        rows = _cat(self._sums).tolist() if self._sums else []
+        assert len(rows) == len(names)
+        names, parts = gather_rows(names, rows, ctx.world)
+        if ctx.rank != 0:
+            return
+        rows = [row for part in parts for row in part]
+        total = [0.0] * 9
+        for row in rows:
+            total = [a + b for a, b in zip(total, row)]
+        doc = {"radius": self.radius, "floor": self.floor, "min_count": self.min_count, "mask": self.mask,
+               "pairs": {name: quality.summarize(row) for name, row in zip(names, rows)}, "total": quality.summarize(total)}
+        write_json(self.file, json_strict(doc), allow_nan=False)
+
+
+class Pod(Stage):
+    """Stores every batch of flows in a FlowPOD, created at the first batch's size -- what the .flo files get after "replace", the raw
+    flow with the flags as the mask after "flag" and "mask" -- and decomposes them after the directory.  `pairs`: how many pairs
+the directory has (check_pod_pairs); `wheel`: the name of the colour wheel the modes are drawn with, or None for no pictures."""
+
+    def __init__(self, modes, cell, pairs, file, wheel):
+        self.modes, self.cell, self.capacity, self.file, self.wheel = modes, cell, pairs, file, wheel
+        self.pod = None
+
+    def __call__(self, batch):
+        if self.pod is None:
+            H, W = batch.flow.size(2), batch.flow.size(3)
+            need, free = FlowPOD.store_bytes(H, W, self.capacity, self.cell), torch.cuda.mem_get_info(batch.flow.device)[0]
+            if need > free // 2:
+                raise SystemExit(f"run.py: --pod: the store of {self.capacity} snapshots of {H} x {W} takes {need / 2**30:.1f} GiB, more "
+                                 f"than half of the {free / 2**30:.1f} GiB free on the device; decompose block means with --pod-cell C")
+            self.pod = FlowPOD(H, W, self.capacity, self.cell, device=batch.flow.device)
+        self.pod.update(*batch.masked())
+
+    def finish(self, names, ctx):
+        """<save>/pod.npz, one line per mode, and with a wheel the modes as pod_mode<k>.png beside it."""
+        res = checked("--pod: ", self.pod.solve, self.modes)
+        print(f"POD of {self.pod.n} flows -> '{res.save(self.file)}'")
+        for k in range(self.modes):
+            print(f"  mode {k + 1}: {100.0 * res.fraction[k]:6.2f} % of the fluctuation energy")
+        if self.wheel is not None:
+            pics = viz.flow_to_color(torch.from_numpy(res.modes.astype("float32")).to(self.pod.device), None, wheel=self.wheel).cpu().numpy()
+            with viz.PngWriter() as pictures:
+                for k in range(self.modes):
+                    pictures.submit(pics[k], self.file[:-4] + f"_mode{k + 1}.png")
+
+
+def check_pod_pairs(pairs, modes, inputdir):
+    if not 2 <= pairs <= 4096:
+        raise SystemExit(f"run.py: --pod: '{inputdir}' has {pairs} pairs; the method of snapshots here takes 2..4096 (decompose a "
+                         "part of the recording with --start / --num_images)")
+    if modes > pairs - 1:
+        raise SystemExit(f"run.py: --pod {modes}: '{inputdir}' has {pairs} pairs, which carry at most {pairs - 1} modes")
+
+
+def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=None):
+    """The stages the command line asks for, for one input directory, in their fixed order: what validation sets is what every later
+    stage sees.  `truth_paths`: the truth_files() of the whole directory."""
+    stages = []
+    if args.pod is not None:                # refused before anything is launched
+        pairs = len(Run(root=inputdir, is_pair=args.is_pair, n_images=args.num_images, start_at=args.start))
+        check_pod_pairs(pairs, args.pod, inputdir)
+    if args.validate is not None:
+        stages.append(Validate(args.validate, args.validate_radius, args.validate_spacing, args.validate_eps, args.validate_thresh,
+                               layout.sibling("validation.json")))
+    if args.stats:
+        stages.append(Stats(layout.sibling("stats.npz")))
+    if args.truth is not None:
+        lo, hi = shard_bounds(len(truth_paths), rank, world)
+        stages.append(Truth(net, truth_paths[lo:hi], args.truth_levels, layout.sibling("errors.json"), layout.sibling("error_maps.npz"),
+                            pin=device.type == "cuda"))
+    if _used(args, PICTURE_FLAGS):
+        stages.append(Pictures(args.color, args.color_max, args.color_wheel, args.vort_image, args.vort_max, args.quiver))
+    if args.quality is not None:
+        stages.append(Quality(args.quality, args.quality_image, layout.sibling("quality.json"),
+                              args.validate if args.validate in ("flag", "mask") else None))
+    if args.pod is not None:
+        stages.append(Pod(args.pod, args.pod_cell or 1, pairs, layout.sibling("pod.npz"), (args.color_wheel or "interp") if args.color else None))
+    return stages
+
+
+@dataclass(frozen=True)
+class Prep:
+    """--background / --minmax / --minmax-floor, checked."""
+    background: object      # None, "min" (main_dl takes the minimum over the folder first) or the image, uint8 [H,W,3] on the device
+    minmax: int
+    floor: int
 
 
 class _SizedPrep:
     """pivlfn.preproc.Preprocessor that checks the background's size against the first batch and names both sizes if they differ."""
 
     def __init__(self, background, minmax, floor):
-        from pivlfn.preproc import Preprocessor
         self.prep, self.checked = Preprocessor(background, minmax, floor), background is None
 
     def __call__(self, frames):
@@ -653,7 +698,6 @@ class _SizedPrep:
 def background_min(ds, device, batch):
     """The per-pixel minimum over every distinct frame of `ds` (a Run), each decoded once on PairLoader's threads: a
     pivlfn.preproc.FrameBackground.  All frames must have one size."""
-    from pivlfn.preproc import FrameBackground
     paths = list(dict.fromkeys(p for pair in ds.image_list for p in pair))
     odd = len(paths) % 2
     twos = SimpleNamespace(image_list=[[paths[i], paths[min(i + 1, len(paths) - 1)]] for i in range(0, len(paths), 2)])
@@ -682,101 +726,58 @@ def background_min(ds, device, batch):
     return bg
 
 
-def main_dl(net, inputdir, savedir, is_pair, start_id, num_images, device, batch, rank=0, world=1, stats_file=None,
-            validate=None, validation_file=None, prep=None, background_file=None, truth=None, viz=None, quality=None, pod=None):
-    """Every pair of the folder through `estimate` (reference main_dl, run.py:137-168); with `stats_file`, FlowStats over the
-    pairs go there; with `validate` (the keyword arguments of _ValidateEstimate bar `stats`), every flow goes through
-    validate_flow before it is copied back and the counts go to `validation_file`.  `prep` = (background, minmax, floor): the
-    frames go through pivlfn.preproc.preprocess_frames; a background of "min" is computed from the folder first and written to
-    `background_file`.  `truth` = (directory or the truth_files() list of it, levels, errors file, maps file): every flow is scored against its truth file
-    (_TruthEstimate).  `viz`: the keyword arguments of _VizEstimate bar `inner` and `validator`: pictures beside the .flo files.
-    `quality` = (radius, image, quality file): every written flow is rated by _QualityEstimate.  `pod` = (modes, cell, pod file,
-    wheel name or None): every written flow is stored by _PodEstimate and decomposed after the folder."""
-    os.makedirs(savedir, exist_ok=True)
-    ds = Run(root=inputdir, is_pair=is_pair, n_images=num_images, start_at=start_id)
-    if pod is not None and not 2 <= len(ds) <= 4096:
-        raise SystemExit(f"run.py: --pod: '{inputdir}' has {len(ds)} pairs; the method of snapshots here takes 2..4096 (decompose a "
-                         "part of the recording with --start / --num_images)")
-    if pod is not None and pod[0] > len(ds) - 1:
-        raise SystemExit(f"run.py: --pod {pod[0]}: '{inputdir}' has {len(ds)} pairs, which carry at most {len(ds) - 1} modes")
-    truth_paths = None
-    if truth is not None:          # a list: main() has checked these files already; a directory: check them now
-        truth_paths = truth_files(ds, truth[0], truth[1]) if isinstance(truth[0], str) else list(truth[0])
-        assert len(truth_paths) == len(ds)
-    if prep is not None:
-        background, minmax, floor = prep
-        if isinstance(background, str):
-            bg = background_min(ds, device, batch)
-            print(f"Background: minimum over {bg.count} frames -> '{bg.save(background_file)}'")
-            background = bg.image()
-        prep = _SizedPrep(background, minmax, floor)
-    lo, hi = shard_bounds(len(ds), rank, world)
-    print(f"Processing {hi - lo} of {len(ds)} pairs of images (rank {rank}/{world})...")
-    loader = PairLoader(ds, lo, hi, batch, depth=2, pin=device.type == "cuda")
-    if validate is not None:
-        est = _ValidateEstimate(stats=stats_file is not None, **validate)
-    else:
-        est = _StatsEstimate() if stats_file is not None else None
-    scorer = None
-    if truth is not None:
-        scorer = _TruthEstimate(truth_paths[lo:hi], est, truth[1], 1.0 / (5.0 if net.starting_scale == 10 else 20.0),
-                                pin=device.type == "cuda")
-    seen = []
-    run_est = scorer if scorer is not None else est
-    painter = None
-    if viz is not None:
-        from pivlfn import viz as vz
-        run_est = painter = _VizEstimate(run_est, est if validate is not None else None, **viz)
-        if viz["color"] and rank == 0:
-            vz.write_png(os.path.join(savedir, "color_wheel.png"),
-                         vz.color_wheel_image(wheel=viz["color_wheel"] or "interp", device=device).cpu().numpy())
-
-    rater = None
-    if quality is not None:
-        from pivlfn import viz as vz
-        run_est = rater = _QualityEstimate(run_est, est if validate is not None else None, painter, quality[0], quality[1])
-
-    podder = None
-    if pod is not None:
-        run_est = podder = _PodEstimate(run_est, est if validate is not None else None, hi - lo, pod[1])
-
-    def sink(flow, name, extras=None):
-        seen.append(name)
-        writer.submit(flow, flowname_modifier(name, savedir, pair=False))
-        if extras and "qual" in extras:
-            writer.submit(extras["qual"], flowname_modifier(name, savedir, ext="_qual.flo", pair=False))
-        for key, ext in (("color", "_out.png"), ("vort", "_vort.png"), ("corr", "_corr.png")):
-            if extras and key in extras:
-                pictures.submit(extras[key], flowname_modifier(name, savedir, ext=ext, pair=False))
-        if extras and "quiver_mean" in extras:          # pyplot is not thread-safe: the arrows are drawn here
-            vz.draw_quiver(extras["quiver_mean"], extras["quiver_count"], viz["quiver"] or vz.quiver_cell(*flow.shape[:2]), *flow.shape[:2],
-                           flowname_modifier(name, savedir, ext="_quiver.png", pair=False))
+def main_dl(net, inputdir, layout, is_pair, start_id, num_images, device, batch, rank=0, world=1, stages=(), prep=None):
+    """Every pair of the folder through `estimate` (reference main_dl, run.py:137-168) and then through `stages` (make_stages), whose
+    files are written after the last pair.  `prep` (a Prep): the frames go through pivlfn.preproc.preprocess_frames; a background of
+    "min" is computed from the folder first and written beside args.txt."""
     try:
-        with FloWriter() as writer:
-            if painter is None and rater is None:
-                n = stream_pairs(net, loader, device, sink, estimate_fn=run_est, prep=prep)
-            else:
-                with vz.PngWriter() as pictures:
-                    n = stream_pairs(net, loader, device, sink, estimate_fn=run_est, prep=prep,
-                                     extras=(rater if rater is not None else painter).extras)
-    finally:
-        loader.close()
-        if scorer is not None:
-            scorer.close()
-    assert n == hi - lo
-    if scorer is not None:
-        finish_truth(scorer, seen, truth[2], truth[3], rank, world, device)
-    if rater is not None:
-        write_quality_json(quality[2], rater, seen, rank, world)
-    if validate is not None:
-        write_validation_json(validation_file, est, seen)
-        if est.stats is not None:
-            est.save_stats(stats_file)
-    elif est is not None and est.stats is not None:
-        est.stats.save(stats_file)
-    if podder is not None:
-        finish_pod(podder.pod, pod[0], pod[2], pod[3])
-    return hi - lo
+        savedir = layout.flow
+        os.makedirs(savedir, exist_ok=True)
+        ds = Run(root=inputdir, is_pair=is_pair, n_images=num_images, start_at=start_id)
+        if prep is not None:
+            background = prep.background
+            if isinstance(background, str):
+                bg = background_min(ds, device, batch)
+                print(f"Background: minimum over {bg.count} frames -> '{bg.save(layout.sibling('background.png'))}'")
+                background = bg.image()
+            prep = _SizedPrep(background, prep.minmax, prep.floor)
+        lo, hi = shard_bounds(len(ds), rank, world)
+        print(f"Processing {hi - lo} of {len(ds)} pairs of images (rank {rank}/{world})...")
+        loader = PairLoader(ds, lo, hi, batch, depth=2, pin=device.type == "cuda")
+        est = Estimator(stages)
+        painter = next((s for s in stages if isinstance(s, Pictures)), None)
+        if painter is not None and painter.color and rank == 0:
+            viz.write_png(os.path.join(savedir, "color_wheel.png"), viz.color_wheel_image(wheel=painter.color_wheel, device=device).cpu().numpy())
+        seen = []
+
+        def sink(flow, name, extras=None):
+            seen.append(name)
+            writer.submit(flow, flowname_modifier(name, savedir, pair=False))
+            if extras and "qual" in extras:
+                writer.submit(extras["qual"], flowname_modifier(name, savedir, ext="_qual.flo", pair=False))
+            for key, ext in (("color", "_out.png"), ("vort", "_vort.png"), ("corr", "_corr.png")):
+                if extras and key in extras:
+                    pictures.submit(extras[key], flowname_modifier(name, savedir, ext=ext, pair=False))
+            if extras and "quiver_mean" in extras:          # pyplot is not thread-safe: the arrows are drawn here
+                viz.draw_quiver(extras["quiver_mean"], extras["quiver_count"], painter.cell(*flow.shape[:2]), *flow.shape[:2],
+                                flowname_modifier(name, savedir, ext="_quiver.png", pair=False))
+        try:
+            with FloWriter() as writer:
+                if not any(s.extras for s in stages):
+                    n = stream_pairs(net, loader, device, sink, estimate_fn=est, prep=prep)
+                else:
+                    with viz.PngWriter() as pictures:
+                        n = stream_pairs(net, loader, device, sink, estimate_fn=est, prep=prep, extras=est.extras)
+        finally:
+            loader.close()
+        assert n == hi - lo
+        ctx = SimpleNamespace(rank=rank, world=world, device=device)
+        for stage in stages:
+            stage.finish(seen, ctx)
+        return hi - lo
+    finally:                                # whatever failed, and where: a stage may hold threads
+        for stage in stages:
+            stage.close()
 
 
 def main_mod(net, inputdir, savedir, start_id, num_images, device, mod_factors: Sequence[Tuple[float, float]], batch,
@@ -798,12 +799,13 @@ def main_mod(net, inputdir, savedir, start_id, num_images, device, mod_factors: 
     return n
 
 
-def args_lines(args, validate, prep, viz) -> List[str]:
+def args_lines(args) -> List[str]:
     """The lines of args.txt.  The flags of validation, pre-processing, scoring, pictures and quality appear only in runs that use them:
     without them the file is what it was before they existed."""
+    prep, pictures = _used(args, PREP_FLAGS), _used(args, PICTURE_FLAGS)
     return [f"{k}: {v}\n" for k, v in sorted(vars(args).items())
-            if not ((validate is None and k.startswith("validate")) or (prep is None and k in PREP_FLAGS) or
-                    (args.truth is None and k in TRUTH_FLAGS) or (viz is None and k in PICTURE_FLAGS) or
+            if not ((args.validate is None and k.startswith("validate")) or (not prep and k in PREP_FLAGS) or
+                    (args.truth is None and k in TRUTH_FLAGS) or (not pictures and k in PICTURE_FLAGS) or
                     (args.quality is None and k in QUALITY_FLAGS) or (args.pod is None and k in POD_FLAGS))]
 
 
@@ -816,72 +818,60 @@ def load_weights(args) -> Tuple[dict, str]:
     return synth.generate_weights(tag, 0), f"{tag}-synthetic"
 
 
+def refuse_mods(args, what):
+    """`what`: the flags and their verb, "--stats is"."""
+    if args.brightness is not None or args.contrast is not None:
+        raise SystemExit(f"run.py: {what} not available with -b/-c (every combination is a different experiment)")
+
+
+def refuse_sharded(flag, reason):
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(f"run.py: {flag} needs a single process ({reason})")
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     args = parser.parse_args(argv)
-    if args.stats and (args.brightness is not None or args.contrast is not None):
-        raise SystemExit("run.py: --stats is not available with -b/-c (every combination is a different experiment)")
-    if args.stats and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("run.py: --stats needs a single process (run.py has no process group to merge the statistics; "
-                         "the sharded path for statistics is pivlfn.sequence.run_sequence)")
+    if args.stats:
+        refuse_mods(args, "--stats is")
+        refuse_sharded("--stats", "run.py has no process group to merge the statistics; the sharded path for statistics is "
+                                  "pivlfn.sequence.run_sequence")
     if args.pod_cell is not None and args.pod is None:
         raise SystemExit("run.py: --pod-cell needs --pod")
     if args.pod is not None:
-        if args.brightness is not None or args.contrast is not None:
-            raise SystemExit("run.py: --pod is not available with -b/-c (every combination is a different experiment)")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise SystemExit("run.py: --pod needs a single process (the snapshots of one decomposition live on one device)")
+        refuse_mods(args, "--pod is")
+        refuse_sharded("--pod", "the snapshots of one decomposition live on one device")
         if not 1 <= args.pod <= 64:
             raise SystemExit(f"run.py: --pod {args.pod}: the number of modes must be 1..64")
         if args.pod_cell is not None and not 1 <= args.pod_cell <= 32768:
             raise SystemExit(f"run.py: --pod-cell {args.pod_cell}: the cell must be 1..32768")
-    validate = None
     if args.validate is not None:
-        if args.brightness is not None or args.contrast is not None:
-            raise SystemExit("run.py: --validate is not available with -b/-c (every combination is a different experiment)")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise SystemExit("run.py: --validate needs a single process (validation.json lists the pairs of one process)")
-        from pivlfn.validate import check_params
-        validate = dict(mode=args.validate, radius=args.validate_radius, spacing=args.validate_spacing, eps=args.validate_eps,
-                        thresh=args.validate_thresh)
-        try:
-            check_params(validate["radius"], validate["spacing"], validate["eps"], validate["thresh"], validate["mode"])
-        except ValueError as e:
-            raise SystemExit(f"run.py: {e}")
+        refuse_mods(args, "--validate is")
+        refuse_sharded("--validate", "validation.json lists the pairs of one process")
+        checked("", check_validate, args.validate_radius, args.validate_spacing, args.validate_eps, args.validate_thresh, args.validate)
     if args.truth_levels and args.truth is None:
         raise SystemExit("run.py: --truth-levels needs --truth")
+    truth_paths = {}
     if args.truth is not None:
-        if args.brightness is not None or args.contrast is not None:
-            raise SystemExit("run.py: --truth is not available with -b/-c (every combination is a different experiment)")
+        refuse_mods(args, "--truth is")
         if not os.path.isdir(args.truth):
             raise SystemExit(f"run.py: --truth '{args.truth}' is not a directory")
         # every truth file of every directory, before the first forward
         truth_paths = {imdir: truth_files(Run(root=imdir, is_pair=args.is_pair, n_images=args.num_images, start_at=args.start),
                                           args.truth, args.truth_levels) for imdir in args.input}
     prep = None
-    if any(getattr(args, k) is not None for k in PREP_FLAGS):
-        if args.brightness is not None or args.contrast is not None:
-            raise SystemExit("run.py: --background / --minmax are not available with -b/-c (every combination is a different "
-                             "experiment)")
-        if args.background == "min" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise SystemExit("run.py: --background min needs a single process (run.py has no process group to merge the minima of "
-                             "the ranks; compute the background once and pass --background FILE)")
+    if _used(args, PREP_FLAGS):
+        refuse_mods(args, "--background / --minmax are")
+        if args.background == "min":
+            refuse_sharded("--background min", "run.py has no process group to merge the minima of the ranks; compute the background "
+                                               "once and pass --background FILE")
         if args.minmax_floor is not None and args.minmax is None:
             raise SystemExit("run.py: --minmax-floor needs --minmax")
         if args.background not in (None, "min") and not os.path.isfile(args.background):
             raise SystemExit(f"run.py: --background '{args.background}' is neither 'min' nor an image file")
-        from pivlfn.preproc import check_params as check_prep
-        minmax, floor = (0 if args.minmax is None else args.minmax), (16 if args.minmax_floor is None else args.minmax_floor)
-        try:
-            check_prep(minmax, floor)
-        except ValueError as e:
-            raise SystemExit(f"run.py: {e}")
-        prep = (args.background, minmax, floor)
-    viz = None
-    if any(getattr(args, k) is not None and getattr(args, k) is not False for k in PICTURE_FLAGS):
-        import math
-        if args.brightness is not None or args.contrast is not None:
-            raise SystemExit("run.py: --color / --vort-image / --quiver are not available with -b/-c (every combination is a different "
-                             "experiment)")
+        prep = Prep(args.background, 0 if args.minmax is None else args.minmax, 16 if args.minmax_floor is None else args.minmax_floor)
+        checked("", check_prep, prep.minmax, prep.floor)
+    if _used(args, PICTURE_FLAGS):
+        refuse_mods(args, "--color / --vort-image / --quiver are")
         if (args.color_max is not None or args.color_wheel is not None) and not args.color:
             raise SystemExit("run.py: --color-max and --color-wheel need --color")
         if args.vort_max is not None and not args.vort_image:
@@ -892,23 +882,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         if args.quiver is not None:
             if not 0 <= args.quiver <= 32768:
                 raise SystemExit(f"run.py: --quiver {args.quiver}: the cell must be 1..32768")
-            from pivlfn.viz import _pyplot
             try:
-                _pyplot()                           # once, here, and not at the first pair
+                viz._pyplot()                       # once, here, and not at the first pair
             except ImportError as e:
                 raise SystemExit(f"run.py: --quiver: {e}")
-        viz = dict(color=args.color, color_max=args.color_max, color_wheel=args.color_wheel, vort_image=args.vort_image,
-                   vort_max=args.vort_max, quiver=args.quiver)
     if args.quality_image and args.quality is None:
         raise SystemExit("run.py: --quality-image needs --quality")
     if args.quality is not None:
-        if args.brightness is not None or args.contrast is not None:
-            raise SystemExit("run.py: --quality is not available with -b/-c (every combination is a different experiment)")
-        from pivlfn.quality import check_params as check_quality
-        try:
-            check_quality(args.quality, 1.0 / 255.0, None)
-        except ValueError as e:
-            raise SystemExit(f"run.py: --quality: {e}")
+        refuse_mods(args, "--quality is")
+        checked("--quality: ", quality.check_params, args.quality, 1.0 / 255.0, None)
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run.py: this build has no CPU path (the reference's correlation has none either, "
                          "src/correlation.py:339-340); a GPU is required")
@@ -923,9 +905,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     net = Network(model=args.model, params=weights, version=args.version).to(device).eval()
     if args.precision is not None:
         net.precision = args.precision
-    if prep is not None and prep[0] not in (None, "min"):
-        from pivlfn.preproc import FrameBackground
-        prep = (FrameBackground.load(prep[0], device).image(),) + prep[1:]
+    if prep is not None and prep.background not in (None, "min"):
+        prep = Prep(FrameBackground.load(prep.background, device).image(), prep.minmax, prep.floor)
     mods = None
     if args.brightness is not None or args.contrast is not None:
         mods = list(product(tuple(args.brightness or (1.0,)), tuple(args.contrast or (1.0,))))
@@ -936,26 +917,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         os.makedirs(lay.save, exist_ok=True)
         if rank == 0:
             with open(lay.args_file, "w") as f:
-                f.writelines(args_lines(args, validate, prep, viz))
+                f.writelines(args_lines(args))
         if mods is None:
-            stats_file = os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "stats", 1)[:-4] + ".npz") \
-                if args.stats else None          # stats.npz (stats_left / stats_right.npz for the halves of a stereo set)
-            validation_file = os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "validation", 1)[:-4] + ".json")
-            total += main_dl(net, imdir, lay.flow, args.is_pair, args.start, args.num_images, device, args.batch, rank, world,
-                             stats_file, validate, validation_file, prep,
-                             os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "background", 1)[:-4] + ".png"),
-                             None if args.truth is None else
-                             (truth_paths[imdir], args.truth_levels,
-                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "errors", 1)[:-4] + ".json"),
-                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "error_maps", 1)[:-4] + ".npz")),
-                             viz,
-                             None if args.quality is None else
-                             (args.quality, args.quality_image,
-                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "quality", 1)[:-4] + ".json")),
-                             None if args.pod is None else
-                             (args.pod, args.pod_cell or 1,
-                              os.path.join(lay.save, os.path.basename(lay.args_file).replace("args", "pod", 1)[:-4] + ".npz"),
-                              (args.color_wheel or "interp") if args.color else None))
+            total += main_dl(net, imdir, lay, args.is_pair, args.start, args.num_images, device, args.batch, rank, world,
+                             make_stages(args, lay, imdir, net, device, rank, world, truth_paths.get(imdir)), prep)
         else:
             total += main_mod(net, imdir, lay.flow, args.start, args.num_images, device, mods, args.batch, rank, world)
     if (args.truth is not None or args.quality is not None) and world > 1:

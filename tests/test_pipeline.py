@@ -145,3 +145,80 @@ def test_stream_pairs_with_brightness_contrast_mods(tmp_path):
         want = _fake_estimate(None, u8_to_input(image_mod(a, *mod)), u8_to_input(image_mod(b, *mod)))[0].permute(1, 2, 0).numpy()
         assert np.array_equal(flow, want), (name, mod)
     assert sorted({m for _, m, _ in got}) == sorted(mods)
+
+
+def test_run_py_estimator_runs_its_stages_in_list_order_on_one_batch(tmp_path):
+    """run.py's Estimator as stream_pairs' estimate_fn, with a stand-in estimate and recording stages: every begin() precedes the
+    forward, the stages run in list order on the same Batch, extras() returns what they put there, Batch.masked() follows the
+    mode rule, and a stage that asks for levels makes the forward go through forward_levels once."""
+    import run as runpy
+    log = []
+
+    def fake(net, a, b, tensor=True):
+        log.append("forward")
+        return net(a, b) if net is not None else _fake_estimate(net, a, b)
+
+    class Rec(runpy.Stage):
+        extras = True
+
+        def __init__(self, tag):
+            self.tag, self.batches = tag, []
+
+        def begin(self, n, device):
+            log.append(("begin", self.tag, n, device.type))
+
+        def __call__(self, batch):
+            log.append(("call", self.tag))
+            self.batches.append(batch)
+            batch.extras[self.tag] = batch.flow[:, 0] + len(batch.extras)
+
+    _write_frames(str(tmp_path), 4)
+    ds = Run(str(tmp_path), is_pair=False)
+    one, two = Rec("one"), Rec("two")
+    est = runpy.Estimator([one, two], estimate=fake)
+    loader = PairLoader(ds, 0, len(ds), 2)
+    got = []
+    n = stream_pairs(None, loader, torch.device("cpu"), lambda flow, name, extras: got.append((name, flow.copy(), extras)),
+                     estimate_fn=est, extras=est.extras)
+    loader.close()
+    assert n == 3 and [g[0] for g in got] == ds.name_list
+    assert log == [e for k in (2, 1)                               # a batch of two pairs, then one of one
+                   for e in (("begin", "one", k, "cpu"), ("begin", "two", k, "cpu"), "forward", ("call", "one"), ("call", "two"))]
+    assert len(one.batches) == 2 and all(x is y for x, y in zip(one.batches, two.batches))
+    last = one.batches[-1]
+    assert est.extras() is last.extras and list(last.extras) == ["one", "two"]
+    assert last.flow is last.raw and last.flag is None and last.mode is None and last.levels is None
+    for i, (name, flow, extras) in enumerate(got):
+        (a, b), _ = ds[i]
+        want = _fake_estimate(None, a[None], b[None])[0]
+        np.testing.assert_array_equal(flow, want.permute(1, 2, 0).numpy())
+        np.testing.assert_array_equal(extras["one"], want[0].numpy())
+        np.testing.assert_array_equal(extras["two"], want[0].numpy() + 1)
+
+    # masked(): (raw, flag) under "flag" and "mask", the written flow and no mask otherwise
+    raw, flow, flag = torch.zeros(1, 2, 4, 4), torch.ones(1, 2, 4, 4), torch.ones(1, 4, 4, dtype=torch.uint8)
+    for mode in ("flag", "mask"):
+        shown, mask = runpy.Batch(raw, raw, raw, flow, flag, mode).masked()
+        assert shown is raw and mask is flag
+    for batch in (runpy.Batch(raw, raw, raw, flow, flag, "replace"), runpy.Batch(raw, raw, raw, flow)):
+        shown, mask = batch.masked()
+        assert shown is flow and mask is None
+
+    # a stage that wants the levels: one forward_levels per batch, its second result in batch.levels
+    class Net:
+        calls = 0
+
+        def forward_levels(self, a, b):
+            Net.calls += 1
+            return _fake_estimate(None, a, b), ["levels", Net.calls]
+
+    class Wants(Rec):
+        levels = True
+
+    del log[:]
+    wants = Wants("w")
+    est = runpy.Estimator([Rec("plain"), wants], estimate=fake)
+    a = torch.rand(2, 3, 8, 8)
+    out = est(Net(), a, 1 - a)
+    assert Net.calls == 1 and log.count("forward") == 1 and wants.batches[0].levels == ["levels", 1]
+    assert out is wants.batches[0].flow and torch.equal(out, _fake_estimate(None, a, 1 - a))

@@ -185,7 +185,7 @@ def test_run_py_refusals(tmp_path, monkeypatch):
 def test_args_txt_lists_the_pod_flags_only_when_used():
     import run as runpy
     a = runpy.parser.parse_args(["--model", "piv", "-i", "x"])
-    assert not any(line.startswith("pod") for line in runpy.args_lines(a, None, None, None))
+    assert not any(line.startswith("pod") for line in runpy.args_lines(a))
     a = runpy.parser.parse_args(["--model", "piv", "-i", "x", "--pod", "2", "--pod-cell", "8"])
-    lines = runpy.args_lines(a, None, None, None)
+    lines = runpy.args_lines(a)
     assert "pod: 2\n" in lines and "pod_cell: 8\n" in lines

@@ -292,11 +292,11 @@ def test_run_py_quality_flags_parse_and_are_checked_before_a_gpu_is_needed(tmp_p
     import run as runpy
     plain = runpy.parser.parse_args(["-i", "x"])
     assert plain.quality is None and plain.quality_image is False
-    assert not [ln for ln in runpy.args_lines(plain, None, None, None) if ln.split(":")[0] in runpy.QUALITY_FLAGS]
+    assert not [ln for ln in runpy.args_lines(plain) if ln.split(":")[0] in runpy.QUALITY_FLAGS]
     assert runpy.parser.parse_args(["--quality"]).quality == 8
     full = runpy.parser.parse_args(["--quality", "4", "--quality-image"])
     assert (full.quality, full.quality_image) == (4, True)
-    lines = runpy.args_lines(full, None, None, None)
+    lines = runpy.args_lines(full)
     assert "quality: 4\n" in lines and "quality_image: True\n" in lines and not [ln for ln in lines if ln.startswith("color")]
     base = ["--model", "piv", "-i", str(tmp_path), "-o", str(tmp_path / "out")]
     for extra, word in ((["--quality-image"], "needs --quality"), (["--quality", "16"], "radius=16"), (["--quality", "0"], "radius=0"),

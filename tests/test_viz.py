@@ -283,7 +283,7 @@ def test_run_py_picture_flags_parse_and_stay_out_of_args_txt(tmp_path, monkeypat
     plain = runpy.parser.parse_args(["-i", "x", "-o", "y"])
     assert (plain.color, plain.color_max, plain.color_wheel, plain.vort_image, plain.vort_max, plain.quiver) == \
         (False, None, None, False, None, None)
-    keys = [ln.split(":")[0] for ln in runpy.args_lines(plain, None, None, None)]
+    keys = [ln.split(":")[0] for ln in runpy.args_lines(plain)]
     assert not set(keys) & set(runpy.VIZ_FLAGS)
     assert keys == sorted(k for k in vars(plain) if not k.startswith("validate") and
                           k not in runpy.PREP_FLAGS + runpy.TRUTH_FLAGS + runpy.VIZ_FLAGS)
@@ -292,7 +292,7 @@ def test_run_py_picture_flags_parse_and_stay_out_of_args_txt(tmp_path, monkeypat
     assert (full.color, full.color_max, full.color_wheel, full.vort_image, full.vort_max, full.quiver) == \
         (True, 4.0, "original", True, 0.5, 8)
     assert runpy.parser.parse_args(["--quiver"]).quiver == 0
-    lines = runpy.args_lines(full, None, None, dict(color=True))
+    lines = runpy.args_lines(full)
     assert "color: True\n" in lines and "color_max: 4.0\n" in lines and "quiver: 8\n" in lines
     assert "comparable" in runpy.parser.format_help()
     base = ["--model", "piv", "-i", str(tmp_path), "-o", str(tmp_path / "out")]
