@@ -353,6 +353,46 @@ int pivlfn_match_quality(const float *img1, const float *img2, int C, const floa
                          unsigned char *flag, int B, int H, int W, int radius, int min_count, double floor, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* ---- vortex identification: the functions Gamma1 and Gamma2 of Graftieaux, Michard and Grosjean (2001) of a flow field over the
+ * (2*radius+1)^2 - 1 neighbours at distance `spacing` pixels around every vector.  Gamma1 peaks at a vortex centre but is not Galilean
+ * invariant; Gamma2 is formed about the window's own mean velocity, is Galilean invariant, and |Gamma2| > 2/pi marks the region where
+ * rotation dominates shear (the vortex core).  Added without an ABI bump (additive).
+ * flow: NCHW [B,2,H,W] fp32;  mask: [B,H,W] bytes or NULL, nonzero = leave the vector out;  gamma: NCHW [B,2,H,W] fp32, planes Gamma1
+ * and Gamma2;  flag: [B,H,W] bytes;  workspace: 8-byte aligned, at least pivlfn_vortex_gamma_workspace_bytes(B,H,W,radius,spacing)
+ * bytes (0 for arguments out of range), needs no initial contents.  Launches only on `stream`, no allocation, no host
+ * synchronisation, no floating-point atomics; no output depends on what gamma, flag or the workspace held before the call; a pair
+ * gives the same bits alone, inside any batch and from run to run.
+ * Arithmetic contract, all fp64, every operation rounded on its own (no fma), divisions and square roots correctly rounded; x is the
+ * column index, y the row index, r = radius, s = spacing:
+ *   validity:    k(q) = 1 iff (mask is NULL or mask(q) == 0) and |u(q)| <= 1e9 && |v(q)| <= 1e9 (NaN compares false; the 1e10 of a
+ *                masked flow is invalid by itself).
+ *   vectors:     U = (double)u, V = (double)v where k = 1, else +0.0 for both;  m = sqrt(U*U + V*V);  ux = U/m, uy = V/m where m > 0,
+ *                else +0.0.
+ *   neighbours:  of P = (x, y): M = (x + i*s, y + j*s) with |i|, |j| <= r, (i, j) != (0, 0), M inside the image (no edge
+ *                replication).  M takes part iff k(M) = 1.
+ *   directions:  d = sqrt((double)(i*i + j*j)), px = i/d, py = j/d.  The table does not depend on s.
+ *   window sums: per row j the terms are added from i = -r to +r starting at +0.0, then the row sums from j = -r to +r starting at
+ *                +0.0.  A neighbour that does not take part is +0.0, and the centre is +0.0 where it is excluded.  The order is fixed
+ *                by this contract and not by the launch geometry.
+ *   counts:      N = the number of neighbours taking part (exact);  n_all = N + k(P).
+ *   Gamma1:      the sum of px*uy(M) - py*ux(M), divided by N.
+ *   window mean: SU, SV = the sums of U and V over the window, centre included, in the same order;  Mx = SU / n_all, My = SV / n_all.
+ *   Gamma2:      du = U(M) - Mx, dv = V(M) - My, m2 = sqrt(du*du + dv*dv);  the term is (px*dv - py*du) / m2 where m2 > 0, else +0.0;
+ *                Gamma2 = the sum divided by N.
+ *   outputs:     both values rounded once to fp32.  Flag bit 0 (PIVLFN_VORTEX_FEW): N < min_count; both planes are NaN there.  Bit 1
+ *                (PIVLFN_VORTEX_CENTRE_OUT): k(P) = 0 (informational: the values are still formed).
+ *   sign:        Gamma is positive where dv/dx - du/dy > 0 with x the column index and y the row index: a rotation that turns the x
+ *                axis towards the y axis, which is clockwise in a picture drawn with the row index growing downwards.  It does not
+ *                follow the mixed convention of the de_vort kind of pivlfn_flow_fields.
+ * Errors (PIVLFN_ERR_ARG, before any launch): null flow / gamma / flag / workspace, gamma or flag overlapping an input, the workspace
+ * or each other, a non-positive size, H*W >= 2^31, B > 65535, radius outside 1..15, spacing outside 1..16, min_count outside
+ * 1..(2*radius+1)^2 - 1, a misaligned or too-small workspace. */
+#define PIVLFN_VORTEX_FEW        1
+#define PIVLFN_VORTEX_CENTRE_OUT 2
+size_t pivlfn_vortex_gamma_workspace_bytes(int B, int H, int W, int radius, int spacing);
+int pivlfn_vortex_gamma(const float *flow, const unsigned char *mask, float *gamma, unsigned char *flag, int B, int H, int W, int radius,
+                        int spacing, int min_count, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- snapshot POD of a flow sequence: the two device steps of proper orthogonal decomposition by the method of snapshots.  The
  * eigenproblem of the n x n matrix stays a host job.  Added without an ABI bump (additive).
  * X: n rows (snapshots) of P fp32 values, row stride ldx >= P floats.  Nothing beyond column P of a row and nothing beyond row n is

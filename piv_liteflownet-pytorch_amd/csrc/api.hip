@@ -210,6 +210,18 @@ int pivlfn_match_quality(const float *img1, const float *img2, int C, const floa
                                 (hipStream_t)stream);
 }
 
+size_t pivlfn_vortex_gamma_workspace_bytes(int B, int H, int W, int radius, int spacing)
+{
+    return vortex_gamma_workspace_bytes(B, H, W, radius, spacing);
+}
+
+int pivlfn_vortex_gamma(const float *flow, const unsigned char *mask, float *gamma, unsigned char *flag, int B, int H, int W, int radius,
+                        int spacing, int min_count, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return launch_vortex_gamma(flow, mask, gamma, flag, B, H, W, radius, spacing, min_count, workspace, workspace_bytes,
+                               (hipStream_t)stream);
+}
+
 int pivlfn_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, void *stream)
 {
     return launch_flow_maxrad(flow, mask, maxrad, B, H, W, (hipStream_t)stream);

@@ -285,6 +285,11 @@ int launch_match_quality(const float *img1, const float *img2, int C, const floa
                          unsigned char *flag, int B, int H, int W, int radius, int min_count, double floor, void *ws, size_t ws_bytes,
                          hipStream_t st);
 
+// ---- vortex identification (vortex.hip): Gamma1 and Gamma2 of a flow over the (2r+1)^2 neighbours at spacing s -----------------------
+size_t vortex_gamma_workspace_bytes(int B, int H, int W, int radius, int spacing);
+int launch_vortex_gamma(const float *flow, const unsigned char *mask, float *gamma, unsigned char *flag, int B, int H, int W, int radius,
+                        int spacing, int min_count, void *ws, size_t ws_bytes, hipStream_t st);
+
 // ---- snapshot POD (pod.hip): fp64 Gram matrix of n fp32 snapshots on the fp64 matrix instruction, fp64 weighted sums of snapshots -----
 size_t snapshot_gram_workspace_bytes(int n, long P);
 int launch_snapshot_gram(const float *X, int n, long P, long ldx, double *G, void *ws, size_t ws_bytes, hipStream_t st);

@@ -5,7 +5,7 @@
                 [--weights FILE] [--batch B] [--stats] [--validate flag|mask|replace]
                 [--background min|FILE] [--minmax K] [--minmax-floor N] [--truth DIR [--truth-levels]]
                 [--color [--color-max X] [--color-wheel interp|original]] [--vort-image [--vort-max X]] [--quiver [CELL]]
-                [--quality [R] [--quality-image]] [--pod K [--pod-cell C]]
+                [--quality [R] [--quality-image]] [--vortex [R] [--vortex-spacing S] [--vortex-image]] [--pod K [--pod-cell C]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -38,6 +38,11 @@ Differences, all deliberate:
     flow inside (2R+1)^2 windows, and the sub-pixel residual of its peak): <name>_qual.flo with the three bands c, dx, dy, the
     summaries in <save>/quality.json, and with `--quality-image` <name>_corr.png (c on 0..1 in gray, undefined pixels red); with
     --validate flag|mask the rejected vectors are left out of the windows;
+  * `--vortex [R]` writes the vortex identification functions of the flow that is written beside every .flo, computed on the device
+    (pivlfn.vortex.vortex_gamma: Gamma1 and Gamma2 over the (2R+1)^2 vectors at `--vortex-spacing S` pixels around each one):
+    <name>_gamma.flo with the two bands, the vortex centres and core areas of every pair and the summary of the run in
+    <save>/vortices.json, and with `--vortex-image` <name>_gamma2.png (Gamma2 on -1..1 in blue - white - red, undefined pixels
+    black); with --validate flag|mask the rejected vectors are left out;
   * `--pod K` decomposes the flows of every input directory after it has been processed (pivlfn.pod.FlowPOD, snapshot POD: the
     Gram matrix of the flows in float64 on the device, its eigenvectors on the host): the first K modes, the mean, the coefficients
     and the energy fractions go to <save>/pod.npz, one line per mode is printed, and with --color the modes are drawn as
@@ -67,7 +72,7 @@ HERE = os.path.dirname(os.path.realpath(__file__))
 sys.path.insert(0, HERE)
 
 from pivlfn import Network                               # noqa: E402
-from pivlfn import quality, synth, viz                   # noqa: E402
+from pivlfn import quality, synth, viz, vortex           # noqa: E402
 from pivlfn.datasets import Run, image_files_from_folder, pair_files     # noqa: E402
 from pivlfn.dist import shard_bounds                     # noqa: E402
 from pivlfn.evaluate import ErrorStats, flow_errors, level_errors        # noqa: E402
@@ -161,6 +166,17 @@ parser.add_argument("--quality", type=int, nargs="?", const=8, default=None, met
                          "of the windows, with --validate replace the replaced flow is rated")
 parser.add_argument("--quality-image", action="store_true",
                     help="with --quality: also <name>_corr.png, c on 0..1 in gray, pixels without a value in red")
+parser.add_argument("--vortex", type=int, nargs="?", const=4, default=None, metavar="R",
+                    help="also write <name>_gamma.flo beside every .flo: the vortex identification functions Gamma1 and Gamma2 of the "
+                         "written flow (pivlfn.vortex.vortex_gamma; not a reference flag; not with -b/-c) over the (2R+1) x (2R+1) "
+                         "vectors around each one (R = 1..15, default 4); the vortex centres (peaks of |Gamma2|) and the core areas "
+                         "(|Gamma2| > 2/pi) go to <save>/vortices.json.  With --validate flag|mask the rejected vectors are left out, "
+                         "with --validate replace the replaced flow is rated")
+parser.add_argument("--vortex-spacing", type=int, default=None, metavar="S",
+                    help="with --vortex: the distance in pixels between the neighbours, 1..16 (default 1)")
+parser.add_argument("--vortex-image", action="store_true",
+                    help="with --vortex: also <name>_gamma2.png, Gamma2 in blue - white - red on the fixed range -1..1 (the pictures of a "
+                         "sequence are comparable), pixels without a value in black")
 parser.add_argument("--pod", type=int, default=None, metavar="K",
                     help="after each input directory, write the first K POD modes of its flows (method of snapshots, pivlfn.pod.FlowPOD: "
                          "mean, modes, coefficients, energies) to <save>/pod.npz and print their energy fractions; with --color also "
@@ -171,8 +187,9 @@ PREP_FLAGS = ("background", "minmax", "minmax_floor")
 POD_FLAGS = ("pod", "pod_cell")
 QUALITY_FLAGS = ("quality", "quality_image")
 QUALITY_BAD_RGB = (255, 0, 0)
+VORTEX_FLAGS = ("vortex", "vortex_spacing", "vortex_image")
 PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
-VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + POD_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + VORTEX_FLAGS + POD_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -606,6 +623,50 @@ class Quality(Stage):
         write_json(self.file, json_strict(doc), allow_nan=False)
 
 
+class Vortex(Stage):
+    """Rates every batch of flows on the device, right after them and on the same stream: vortex_gamma of the flow that is written,
+    with the flags of "flag" or "mask" as the mask.  The two bands -- and the picture of Gamma2, with `image` -- go back to the host
+    with the flows, where pair() finds the peaks of each pair from its bands; the per-pair sums (pivlfn.vortex.SUMS) stay on the device
+    until finish() copies them once."""
+    extras = True
+
+    def __init__(self, radius, spacing, image, file, mask=None):
+        self.radius, self.spacing, self.image, self.file, self.mask = radius, spacing, image, file, mask      # mask: for vortices.json
+        self.min_count = vortex.check_params(radius, spacing, None)
+        self._sums, self._peaks = [], []
+
+    def __call__(self, batch):
+        v = vortex.vortex_gamma(batch.flow, self.radius, self.spacing, batch.masked()[1], self.min_count)
+        self._sums.append(v.sums())
+        batch.extras["gamma"] = torch.stack([v.gamma1, v.gamma2], dim=3)      # the .flo layout
+        if self.image:          # red is the colour of Gamma2 = 1 in this map: what has no value is black, as in the vorticity pictures
+            batch.extras["gamma2"] = viz.scalar_to_color(v.gamma2.contiguous(), -1.0, 1.0, cmap="bwr")
+
+    def pair(self, gamma):
+        """The peaks of one pair from its bands on the host ([H,W,2]): VortexField.peaks is plain torch."""
+        g = torch.from_numpy(np.ascontiguousarray(gamma)).permute(2, 0, 1).unsqueeze(1)
+        flag = torch.zeros(g.shape[1:], dtype=torch.uint8)
+        self._peaks.append(vortex.VortexField(g[0], g[1], flag, self.radius, self.spacing).peaks()[0])
+
+    def finish(self, names, ctx):
+        """<save>/vortices.json: the parameters, per pair name the peaks of |Gamma2| (VortexField.peaks) and the summary
+        (VortexField.summary), and the summary over the run, formed from the per-pair sums in pair order.  Sharded runs: the records of
+        all ranks are gathered (gather_rows) and rank 0 writes.  A value that is not finite is written as null."""
+        rows = _cat(self._sums).tolist() if self._sums else []
+        assert len(rows) == len(names) == len(self._peaks)
+        names, parts = gather_rows(names, (rows, self._peaks), ctx.world)
+        if ctx.rank != 0:
+            return
+        rows, peaks = [row for part in parts for row in part[0]], [p for part in parts for p in part[1]]
+        total = [0.0] * len(vortex.SUMS)
+        for row in rows:
+            total = [a + b for a, b in zip(total, row)]
+        doc = {"radius": self.radius, "spacing": self.spacing, "min_count": self.min_count, "mask": self.mask, "threshold": vortex.CORE,
+               "pairs": {name: {"peaks": p, "summary": vortex.summarize(row)} for name, p, row in zip(names, peaks, rows)},
+               "total": vortex.summarize(total)}
+        write_json(self.file, json_strict(doc), allow_nan=False)
+
+
 class Pod(Stage):
     """Stores every batch of flows in a FlowPOD, created at the first batch's size -- what the .flo files get after "replace", the raw
     flow with the flags as the mask after "flag" and "mask" -- and decomposes them after the directory.  `pairs`: how many pairs
@@ -667,6 +728,9 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
     if args.quality is not None:
         stages.append(Quality(args.quality, args.quality_image, layout.sibling("quality.json"),
                               args.validate if args.validate in ("flag", "mask") else None))
+    if args.vortex is not None:
+        stages.append(Vortex(args.vortex, args.vortex_spacing or 1, args.vortex_image, layout.sibling("vortices.json"),
+                             args.validate if args.validate in ("flag", "mask") else None))
     if args.pod is not None:
         stages.append(Pod(args.pod, args.pod_cell or 1, pairs, layout.sibling("pod.npz"), (args.color_wheel or "interp") if args.color else None))
     return stages
@@ -746,6 +810,7 @@ def main_dl(net, inputdir, layout, is_pair, start_id, num_images, device, batch,
         loader = PairLoader(ds, lo, hi, batch, depth=2, pin=device.type == "cuda")
         est = Estimator(stages)
         painter = next((s for s in stages if isinstance(s, Pictures)), None)
+        vortices = next((s for s in stages if isinstance(s, Vortex)), None)
         if painter is not None and painter.color and rank == 0:
             viz.write_png(os.path.join(savedir, "color_wheel.png"), viz.color_wheel_image(wheel=painter.color_wheel, device=device).cpu().numpy())
         seen = []
@@ -755,7 +820,10 @@ def main_dl(net, inputdir, layout, is_pair, start_id, num_images, device, batch,
             writer.submit(flow, flowname_modifier(name, savedir, pair=False))
             if extras and "qual" in extras:
                 writer.submit(extras["qual"], flowname_modifier(name, savedir, ext="_qual.flo", pair=False))
-            for key, ext in (("color", "_out.png"), ("vort", "_vort.png"), ("corr", "_corr.png")):
+            if extras and "gamma" in extras:
+                writer.submit(extras["gamma"], flowname_modifier(name, savedir, ext="_gamma.flo", pair=False))
+                vortices.pair(extras["gamma"])
+            for key, ext in (("color", "_out.png"), ("vort", "_vort.png"), ("corr", "_corr.png"), ("gamma2", "_gamma2.png")):
                 if extras and key in extras:
                     pictures.submit(extras[key], flowname_modifier(name, savedir, ext=ext, pair=False))
             if extras and "quiver_mean" in extras:          # pyplot is not thread-safe: the arrows are drawn here
@@ -800,13 +868,14 @@ def main_mod(net, inputdir, savedir, start_id, num_images, device, mod_factors: 
 
 
 def args_lines(args) -> List[str]:
-    """The lines of args.txt.  The flags of validation, pre-processing, scoring, pictures and quality appear only in runs that use them:
+    """The lines of args.txt.  The flags of validation, pre-processing, scoring, pictures, quality and vortices appear only in runs that use them:
     without them the file is what it was before they existed."""
     prep, pictures = _used(args, PREP_FLAGS), _used(args, PICTURE_FLAGS)
     return [f"{k}: {v}\n" for k, v in sorted(vars(args).items())
             if not ((args.validate is None and k.startswith("validate")) or (not prep and k in PREP_FLAGS) or
                     (args.truth is None and k in TRUTH_FLAGS) or (not pictures and k in PICTURE_FLAGS) or
-                    (args.quality is None and k in QUALITY_FLAGS) or (args.pod is None and k in POD_FLAGS))]
+                    (args.quality is None and k in QUALITY_FLAGS) or (args.vortex is None and k in VORTEX_FLAGS) or
+                    (args.pod is None and k in POD_FLAGS))]
 
 
 def load_weights(args) -> Tuple[dict, str]:
@@ -891,13 +960,18 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.quality is not None:
         refuse_mods(args, "--quality is")
         checked("--quality: ", quality.check_params, args.quality, 1.0 / 255.0, None)
+    if (args.vortex_image or args.vortex_spacing is not None) and args.vortex is None:
+        raise SystemExit("run.py: --vortex-spacing and --vortex-image need --vortex")
+    if args.vortex is not None:
+        refuse_mods(args, "--vortex is")
+        checked("--vortex: ", vortex.check_params, args.vortex, 1 if args.vortex_spacing is None else args.vortex_spacing, None)
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run.py: this build has no CPU path (the reference's correlation has none either, "
                          "src/correlation.py:339-340); a GPU is required")
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())   # ranks may share a card
     torch.cuda.set_device(device)
-    if (args.truth is not None or args.quality is not None) and world > 1:        # the ranks' records and maps meet on rank 0: a small host-side exchange
+    if (args.truth is not None or args.quality is not None or args.vortex is not None) and world > 1:        # the ranks' records and maps meet on rank 0: a small host-side exchange
         import torch.distributed as dist
         if not dist.is_initialized():
             dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -923,7 +997,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                              make_stages(args, lay, imdir, net, device, rank, world, truth_paths.get(imdir)), prep)
         else:
             total += main_mod(net, imdir, lay.flow, args.start, args.num_images, device, mods, args.batch, rank, world)
-    if (args.truth is not None or args.quality is not None) and world > 1:
+    if (args.truth is not None or args.quality is not None or args.vortex is not None) and world > 1:
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
