@@ -496,13 +496,34 @@ size_t pivlfn_levels_floats(const pivlfn_net *net, int B, int H, int W);
  * them are not read; leaky: LeakyReLU(0.1) on the result.
  * Dispatch = the PIVLFN_PRECISION_F32 network's for the shape, except Winograd (own entry point below): the direct kernel
  * everywhere, but a 7 x 1 layer (pad 3, 0; no residual, no activation) on an image of >= 256 x 256 pixels runs on the streaming
- * matrix-core kernel pivlfn_forward uses for conv_dist_R.0 there -- not bit-comparable with the F32_DIRECT network's layer. */
+ * matrix-core kernel pivlfn_forward uses for conv_dist_R.0 there -- not bit-comparable with the F32_DIRECT network's layer.
+ * The handle's split-K scratch holds one image's shares: a batch it is too small for runs image by image, so a sample's split factor
+ * -- pivlfn_forward's for that image -- and its bits do not depend on B. */
 typedef struct pivlfn_conv pivlfn_conv;
 int pivlfn_conv_create(const float *weight, const float *bias, int cout, int cin, int kh, int kw, pivlfn_conv **out);
 int pivlfn_conv_destroy(pivlfn_conv *conv);
 int pivlfn_conv2d_nhwc(const pivlfn_conv *conv, const float *x, int x_stride, float *y, int y_stride,
                        const float *res, int res_stride, int B, int H, int W, int stride, int pad_y, int pad_x,
                        int leaky, void *stream);
+/* Which kernel pivlfn_conv2d_nhwc runs for a layer of this shape (as pivlfn_conv_create packs it) and a call of this geometry: the
+ * launcher's own decision, made on the host -- nothing is launched, no handle and no GPU is needed.  has_res: a residual is passed.
+ * plan[0] the kernel family, plan[1] / plan[2] the output rows / output channels of one workgroup's tile, plan[3] the v2 kernel's
+ * staging class as 100 * PMAX + WMAX (309, 505 or 913; 0 for the other families), plan[4] the split-K shares (1 = not split).
+ * A batch whose split-K shares exceed the handle's scratch runs image by image: the plan is then one image's.
+ * Returns PIVLFN_ERR_ARG, with a message, for everything pivlfn_conv2d_nhwc refuses for that geometry (its pointers apart).
+ * Whether a geometry is accepted, and the split-K shares, never depend on B; family and tile do, the bits of a sample do not
+ * (tests/test_conv_plan.py, tests/test_gpu_conv_tiles.py). */
+#define PIVLFN_CONV_PLAN_V2   1   /* conv_mfma2_kernel<rows / 4, channels / 32, PMAX, WMAX>, register-prefetched */
+#define PIVLFN_CONV_PLAN_V1   2   /* conv_mfma_kernel<rows / 4, channels / 32>: what v2's staging classes do not cover */
+#define PIVLFN_CONV_PLAN_K1   3   /* one 4-channel K chunk, >= 16 taps: weights resident, persistent workgroups (from 1024 tiles; at any
+                                   * count where no other kernel takes the layer) */
+#define PIVLFN_CONV_PLAN_C3K7 4   /* 7 x 7 from 3 channels to 32, taps packed into K */
+#define PIVLFN_CONV_PLAN_S2   5   /* 3 x 3 stride 2 from 32 channels, whole lines */
+#define PIVLFN_CONV_PLAN_COL7 6   /* streaming 7 x 1 */
+#define PIVLFN_CONV_PLAN_ROW7 7   /* streaming 1 x 7 */
+int pivlfn_conv2d_nhwc_plan(int cout, int cin, int kh, int kw, int B, int H, int W, int stride, int pad_y, int pad_x,
+                            int has_res, int leaky, int x_stride, int y_stride, int plan[5]);
+
 /* The same layer in the optional reduced-precision mode (BASELINE config #5: fp16 multiplicands, fp32 accumulation, on
  * v_mfma_f32_32x32x16_f16): x is fp32 or fp16 elements (x_is_f16; stride granularity 4 / 8 elements), y is stored as fp32
  * or fp16 (y_is_f16); with fp16 x, lanes cin..roundup(cin,8) must be finite and lanes past them are not read.  No residual input. */

@@ -116,6 +116,21 @@ int pivlfn_corr_bwd_channel_group(int B, int C, int H, int W, int stride)
     return corr_bwd_cgroup(B, C, H, W, stride);
 }
 
+int pivlfn_conv2d_nhwc_plan(int cout, int cin, int kh, int kw, int B, int H, int W, int stride, int pad_y, int pad_x,
+                            int has_res, int leaky, int x_stride, int y_stride, int plan[5])
+{
+    PIV_REQUIRE(plan && cout > 0 && cin > 0 && kh > 0 && kw > 0, "conv2d_plan: bad arguments");
+    static const float some_residual = 0.f;      // never read: the choice only asks whether there is one
+    ConvParams p;
+    ConvPlan pl;
+    bool per_image;
+    if (int rc = conv_forward_choose(conv_shape(cout, cin, kh, kw), x_stride, y_stride, has_res ? &some_residual : nullptr, B, H, W, stride,
+                                     pad_y, pad_x, leaky, p, pl, per_image))
+        return rc;
+    plan[0] = pl.family; plan[1] = pl.rows; plan[2] = pl.chans; plan[3] = pl.staging; plan[4] = pl.ksplit;
+    return PIVLFN_OK;
+}
+
 int pivlfn_backwarp(const float *in, const float *flow, float *out, int B, int C, int H, int W, void *stream)
 {
     return launch_backwarp_nchw(in, flow, out, B, C, H, W, (hipStream_t)stream);

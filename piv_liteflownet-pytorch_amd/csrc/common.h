@@ -123,7 +123,17 @@ struct ConvParams {
 #endif
 };
 
+// What launch_conv runs for a call (pivlfn_conv2d_nhwc_plan): kernel family (PIVLFN_CONV_PLAN_*), output rows and channels of a
+// workgroup's tile, v2's staging class as 100 * PMAX + WMAX (0 elsewhere), split-K shares.
+struct ConvPlan { int family, rows, chans, staging, ksplit; };
+// The launcher's decision from the geometry alone (no pointer read, no device call); scratch_floats == 0 stands for "no scratch".
+int choose_conv(const ConvParams &p, ConvPlan &pl);
 int launch_conv(const ConvParams &p, hipStream_t st);
+// A single-source layer's shape as pivlfn_conv_create packs it, and pivlfn_conv2d_nhwc's kernel choice for a call of it (net.hip)
+struct ConvShape { int cout, cout_pad, cin, KH, KW, nchunk, tail; bool col7, row7; };
+ConvShape conv_shape(int cout, int cin, int kh, int kw);
+int conv_forward_choose(const ConvShape &c, int x_stride, int y_stride, const float *res, int B, int H, int W, int stride, int pad_y,
+                        int pad_x, int leaky, ConvParams &p, ConvPlan &pl, bool &per_image);
 // NetC.conv1 with the two 1 x 1 layers that read its output at level 1 -- NetC_ext (32 -> 64, both frames) and Regularization's
 // moduleFeat (32 -> 128, first frame) -- computed from the activated accumulators in the same kernel (conv_mfma.hip).
 struct Conv1Fuse {
@@ -216,6 +226,8 @@ int launch_conv_col7(const float *x, int x_stride, const float *wf, const float 
 // (1 x 7) convolution 49 -> 49 channels (52 stored lanes), the same way along x (conv_head.hip)
 int launch_conv_row7(const float *x, int x_stride, const float *wf, const float *wf12, const float *bias, float *out, int out_stride,
                      int B, int H, int W, hipStream_t st);
+int check_conv_col7(int x_stride, int out_stride, int cout_store, int single48, int B, int H, int W);   // their argument checks,
+int check_conv_row7(int x_stride, int out_stride, int B, int H, int W);                                  // pointers apart
 int launch_conv_head(const float *x, const float *w, float b0, float b1, const float *res4, float *out4, int B, int H, int W,
                      int k, hipStream_t st);
 

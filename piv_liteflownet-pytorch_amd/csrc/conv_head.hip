@@ -392,14 +392,22 @@ __global__ __launch_bounds__(256, 2) void conv_col7_kernel(const float *__restri
 
 // wf: [4 blocks][7][2][64][4] fragments (net.hip pack_conv), bias: [64]; single48: the layer has 49 output channels and block 3 of
 // wf holds channel 48's weights replicated over the slots (vector path of the fourth wave)
-int launch_conv_col7(const float *x, int x_stride, const float *wf, const float *bias, float *out, int out_stride, int cout_store,
-                     int single48, int B, int H, int W, hipStream_t st)
+// What launch_conv_col7 accepts, apart from its pointers (also behind pivlfn_conv2d_nhwc_plan)
+int check_conv_col7(int x_stride, int out_stride, int cout_store, int single48, int B, int H, int W)
 {
-    PIV_REQUIRE(x && wf && bias && out && B > 0 && H > 0 && W > 0, "conv_col7: bad arguments");
+    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "conv_col7: bad arguments");
     PIV_REQUIRE(x_stride % 4 == 0 && out_stride % 4 == 0 && cout_store % 4 == 0 && cout_store <= 64 && cout_store <= out_stride, "conv_col7: bad strides");
     // the 49-channel path leaves channel 48's value in all four lane groups of block 3 and relies on only lane group 0 being stored
     PIV_REQUIRE(!single48 || cout_store == 52, "conv_col7: the 49-channel layer stores 52 lanes (got %d)", cout_store);
     PIV_REQUIRE((long)H * W * std::max(x_stride, out_stride) * 4 < (1L << 31), "conv_col7: image exceeds 2 GiB (32-bit buffer offsets for the loads and the stores)");
+    return PIVLFN_OK;
+}
+
+int launch_conv_col7(const float *x, int x_stride, const float *wf, const float *bias, float *out, int out_stride, int cout_store,
+                     int single48, int B, int H, int W, hipStream_t st)
+{
+    PIV_REQUIRE(x && wf && bias && out, "conv_col7: bad arguments");
+    if (int rc = check_conv_col7(x_stride, out_stride, cout_store, single48, B, H, W)) return rc;
     constexpr int TH = 16;
     hipLaunchKernelGGL((conv_col7_kernel<TH>), dim3(cdiv(cdiv(W, 16) * cdiv(H, TH) * B, 4)), dim3(256), 0, st, x, x_stride, wf, bias, out, out_stride, cout_store, single48, B, H, W);
     PIV_CHECK_HIP(hipGetLastError());
@@ -554,12 +562,20 @@ __global__ __launch_bounds__(256, 2) void conv_row7_kernel(const float *__restri
 
 // wf: [4 blocks][7][3][64][4] fragments of channel quads kq + 4 g, wf12: [4][7][64] = channel 48 in lane group 0 (net.hip pack_conv);
 // block 3 of both holds output channel 48's weights replicated over the slots; bias: [64]
+// What launch_conv_row7 accepts, apart from its pointers (also behind pivlfn_conv2d_nhwc_plan)
+int check_conv_row7(int x_stride, int out_stride, int B, int H, int W)
+{
+    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "conv_row7: bad arguments");
+    PIV_REQUIRE(x_stride % 4 == 0 && x_stride >= 52 && out_stride % 4 == 0 && out_stride >= 52, "conv_row7: 52 stored lanes in and out (strides %d, %d)", x_stride, out_stride);
+    PIV_REQUIRE((long)H * W * std::max(x_stride, out_stride) * 4 < (1L << 31), "conv_row7: image exceeds 2 GiB (32-bit buffer offsets for the loads and the stores)");
+    return PIVLFN_OK;
+}
+
 int launch_conv_row7(const float *x, int x_stride, const float *wf, const float *wf12, const float *bias, float *out, int out_stride,
                      int B, int H, int W, hipStream_t st)
 {
-    PIV_REQUIRE(x && wf && wf12 && bias && out && B > 0 && H > 0 && W > 0, "conv_row7: bad arguments");
-    PIV_REQUIRE(x_stride % 4 == 0 && x_stride >= 52 && out_stride % 4 == 0 && out_stride >= 52, "conv_row7: 52 stored lanes in and out (strides %d, %d)", x_stride, out_stride);
-    PIV_REQUIRE((long)H * W * std::max(x_stride, out_stride) * 4 < (1L << 31), "conv_row7: image exceeds 2 GiB (32-bit buffer offsets for the loads and the stores)");
+    PIV_REQUIRE(x && wf && wf12 && bias && out, "conv_row7: bad arguments");
+    if (int rc = check_conv_row7(x_stride, out_stride, B, H, W)) return rc;
     constexpr int TW = 16;
     hipLaunchKernelGGL((conv_row7_kernel<TW>), dim3(cdiv(cdiv(W, TW) * cdiv(H, 16) * B, 4)), dim3(256), 0, st, x, x_stride, wf, wf12, bias, out, out_stride, B, H, W,
                        reinterpret_cast<unsigned long long *>(((unsigned long long)(unsigned)PIV_KNOB(6) << 32) | (unsigned)PIV_KNOB(5)));   // tools build only

@@ -457,14 +457,18 @@ int launch_splitk_reduce(const ConvParams &p, int nz, hipStream_t st)
     return PIVLFN_OK;
 }
 
+// LDS of one v1 / v2 workgroup: the input patch of a th x 32 tile and one K chunk's weight slab for bn channels
+static size_t tile_lds_bytes(const ConvParams &p, int th, int bn)
+{
+    const int PH = (th - 1) * p.S + p.KH, PW = 31 * p.S + p.KW;
+    return ((size_t)PH * PW * PIXP + (size_t)p.KH * p.KW * 2 * bn * 4) * sizeof(float);
+}
+
 template <int MT, int NT, int PMAX, int WMAX>
 static int launch_t2(const ConvParams &p, hipStream_t st)
 {
     constexpr int TH = 4 * MT, BN = NT * 32;
-    const int PH = (TH - 1) * p.S + p.KH, PW = 31 * p.S + p.KW;
-    const size_t lds = ((size_t)PH * PW * PIXP + (size_t)p.KH * p.KW * 2 * BN * 4) * sizeof(float);
-    PIV_REQUIRE(lds <= 160 * 1024, "conv: LDS tile of %zu bytes exceeds 160 KiB (k=%dx%d s=%d)", lds, p.KH, p.KW, p.S);
-    PIV_REQUIRE(PH * PW * 2 <= 256 * PMAX && p.KH * p.KW * 2 * BN <= 256 * WMAX, "conv: internal staging bound exceeded");
+    const size_t lds = tile_lds_bytes(p, TH, BN);            // bounds: choose_conv2
     static LdsAttr attr;
     if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_mfma2_kernel<MT, NT, PMAX, WMAX>), 160 * 1024)) return rc;
     const int tiles = cdiv(p.Wo, 32) * cdiv(p.Ho, TH) * p.B;
@@ -598,15 +602,25 @@ __global__ __launch_bounds__(256, 2) void conv_k1_kernel(const ConvParams p)
 }
 
 // Applies to: one K chunk that is a 4-channel tail, >= 16 taps, no residual, 32-channel output blocks, enough tiles.
+// any_tiles: without the tile count, the one condition that holds the batch (choose_conv's last resort; the persistent kernel walks
+// any number of tiles, workgroups past the last one return at once).
+static bool choose_conv_k1(const ConvParams &p, ConvPlan &pl, bool any_tiles = false)
+{
+    if (p.nchunk != 1 || !p.tail || p.res || p.KH * p.KW < 16 || p.nseg != 1 || (PIV_KNOB(1) & 256)) return false;
+    const int PH = 7 * p.S + p.KH, PW = 31 * p.S + p.KW;
+    if (PH * PW * 2 > 256 * 5) return false;
+    const size_t lds = ((size_t)PH * PW * PIXP + (size_t)p.KH * p.KW * 2 * 32 * 4) * sizeof(float);
+    if (lds > 80 * 1024) return false;
+    const int tiles = cdiv(p.Wo, 32) * cdiv(p.Ho, 8) * p.B;
+    if (tiles < 1024 && !any_tiles) return false;
+    pl = ConvPlan{PIVLFN_CONV_PLAN_K1, 8, 32, 0, 1};
+    return true;
+}
+
 static int launch_conv_k1(const ConvParams &p, hipStream_t st)
 {
-    if (p.nchunk != 1 || !p.tail || p.res || p.KH * p.KW < 16 || p.nseg != 1 || (PIV_KNOB(1) & 256)) return -1;
     const int PH = 7 * p.S + p.KH, PW = 31 * p.S + p.KW;
-    if (PH * PW * 2 > 256 * 5) return -1;
     const size_t lds = ((size_t)PH * PW * PIXP + (size_t)p.KH * p.KW * 2 * 32 * 4) * sizeof(float);
-    if (lds > 80 * 1024) return -1;
-    const int tiles = cdiv(p.Wo, 32) * cdiv(p.Ho, 8) * p.B;
-    if (tiles < 1024) return -1;
     static LdsAttr attr;
     if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_k1_kernel<5>), 80 * 1024)) return rc;
     const int nby = p.cout_pad / 32;
@@ -784,13 +798,19 @@ __global__ __launch_bounds__(256, FUSE ? 2 : 3) void conv_c3k7_kernel(const Conv
 }
 
 // Applies to: 7 x 7, stride 1, pad 3, one source of 3 real channels on 4 lanes, 32 output channels, no residual, >= 1024 tiles
-static int launch_conv_c3k7(const ConvParams &p, hipStream_t st)
+static bool choose_conv_c3k7(const ConvParams &p, ConvPlan &pl)
 {
     if (p.KH != 7 || p.KW != 7 || p.S != 1 || p.padY != 3 || p.padX != 3 || p.nseg != 1 || p.seg[0].cload != 4 || p.nchunk != 1 || !p.tail ||
         p.res || p.cout_pad != 32 || p.cin_real != 3 || (PIV_KNOB(1) & 134217728))
-        return -1;
+        return false;
+    if ((long)cdiv(p.Wo, 32) * cdiv(p.Ho, 8) < 512) return false;             // per image: never a function of the batch
+    pl = ConvPlan{PIVLFN_CONV_PLAN_C3K7, 8, 32, 0, 1};
+    return true;
+}
+
+static int launch_conv_c3k7(const ConvParams &p, hipStream_t st)
+{
     const long tiles = (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 8) * p.B;
-    if ((long)cdiv(p.Wo, 32) * cdiv(p.Ho, 8) < 512) return -1;             // per image: never a function of the batch
     const int cus = device_cus();
     hipLaunchKernelGGL((conv_c3k7_kernel<false>), dim3((unsigned)std::min<long>(tiles, 3L * cus)), dim3(256), 0, st, p, Conv1Fuse{});
     PIV_CHECK_HIP(hipGetLastError());
@@ -969,14 +989,19 @@ __global__ __launch_bounds__(256) void conv_s2c32_kernel(const ConvParams p)
 
 // Applies to: 3 x 3, stride 2, pad 1, one source of exactly 32 channels, 32 or 64 output channels, no residual, and (per image, never
 // a function of the batch) at least 256 tiles of 8 x 16 outputs.
-static int launch_conv_s2(const ConvParams &p_in, hipStream_t st)
+static bool choose_conv_s2(const ConvParams &p, ConvPlan &pl)
 {
-    const ConvParams &p = p_in;
     if (p.KH != 3 || p.KW != 3 || p.S != 2 || p.padY != 1 || p.padX != 1 || p.nseg != 1 || p.seg[0].cload != 32 || p.nchunk != 4 || p.tail ||
         p.res || (p.cout_pad != 32 && p.cout_pad != 64) || (PIV_KNOB(1) & 4194304))
-        return -1;
-    if ((long)cdiv(p.Wo, 16) * cdiv(p.Ho, 8) < 256) return -1;
-    if ((size_t)17 * p.W * p.seg[0].stride * 4 >= 0x7fffffffull) return -1;       // one patch inside a descriptor's 2 GiB
+        return false;
+    if ((long)cdiv(p.Wo, 16) * cdiv(p.Ho, 8) < 256) return false;
+    if ((size_t)17 * p.W * p.seg[0].stride * 4 >= 0x7fffffffull) return false;       // one patch inside a descriptor's 2 GiB
+    pl = ConvPlan{PIVLFN_CONV_PLAN_S2, 8, p.cout_pad, 0, 1};
+    return true;
+}
+
+static int launch_conv_s2(const ConvParams &p, hipStream_t st)
+{
     const int nt = p.cout_pad / 32;
     const size_t lds = ((size_t)S2_NPIX * S2_PIXP + (size_t)4 * 9 * 2 * 32 * nt * 4) * sizeof(float);
     const int cus = device_cus();
@@ -1000,48 +1025,64 @@ static int launch_conv_s2(const ConvParams &p_in, hipStream_t st)
 // change of the step time.  Both run at ~3.5 TB/s of a 4:1 write-heavy stream; tools/bench_ops.py conv --filter 1x1.)
 
 // Tile choice for v2.  Staging loads per thread: patch = PH*PW*2/256, slab = taps*2*BN/256 (16-byte each).
-static int launch_conv2(const ConvParams &p_in, hipStream_t st)
+// nt_cap / mt_cap bound the tile (4 / 4: the shipped policy).  Returns PIVLFN_OK with the plan, -1 when v2 does not cover the layer
+// with that tile (the caller falls back to v1), or PIVLFN_ERR_ARG.
+// say: leave the refusal's message as the last error (false for choose_conv's speculative attempts).
+#define CHOOSE_REQUIRE(cond, ...)                                                            \
+    do {                                                                                     \
+        if (!(cond)) {                                                                       \
+            if (say) pivlfn::set_error(__VA_ARGS__);                                         \
+            return PIVLFN_ERR_ARG;                                                           \
+        }                                                                                    \
+    } while (0)
+static int choose_conv2(const ConvParams &p, int nt_cap, int mt_cap, ConvPlan &pl, bool say)
 {
-    ConvParams p = p_in;
-    p.stamps = reinterpret_cast<unsigned long long *>(((unsigned long long)(unsigned)PIV_KNOB(6) << 32) | (unsigned)PIV_KNOB(5));   // tools only
-    PIV_SET_DBG(p, PIV_KNOB(7));
     const int taps = p.KH * p.KW;
     for (int s = 0; s < p.nseg; ++s)      // 32-bit byte offsets inside the rows of one patch (the descriptors are rebased per workgroup)
-        PIV_REQUIRE((size_t)(15 * p.S + p.KH) * p.W * p.seg[s].stride * 4 < 0x7fffffffull, "conv: one patch (%d rows x %d x %d floats) of source %d exceeds the 2 GiB buffer-descriptor range", 15 * p.S + p.KH, p.W, p.seg[s].stride, s);
+        CHOOSE_REQUIRE((size_t)(15 * p.S + p.KH) * p.W * p.seg[s].stride * 4 < 0x7fffffffull, "conv: one patch (%d rows x %d x %d floats) of source %d exceeds the 2 GiB buffer-descriptor range", 15 * p.S + p.KH, p.W, p.seg[s].stride, s);
     // Split-K when one image has too few tiles for the chip and the K loop is long enough to be worth sharing.  Decided from
     // the per-image count of canonical (4 rows x 32 px x 32 channels) tiles only -- never from the batch size or from the tile
     // shape picked below (which does depend on it): a pair's flow must not depend on its batch mates, bit for bit.
+    int ksplit = 1;
     {
         const int nfull = p.nchunk - p.tail;
         const long blocks1 = (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 4) * (p.cout_pad / 32);
-        p.ksplit = 1;
-        if (p.scratch && blocks1 <= 128 && nfull >= 4 && !(PIV_KNOB(1) & 128)) {
-            p.ksplit = (int)std::min<long>(std::min(8, nfull / 2), std::max<long>(1, 512 / blocks1));
-            if ((size_t)p.B * p.Ho * p.Wo * p.cout_pad * p.ksplit > p.scratch_floats) p.ksplit = 1;   // standalone layers with a small scratch only
+        if (p.scratch_floats && blocks1 <= 128 && nfull >= 4 && !(PIV_KNOB(1) & 128)) {
+            ksplit = (int)std::min<long>(std::min(8, nfull / 2), std::max<long>(1, 512 / blocks1));
+            if ((size_t)p.B * p.Ho * p.Wo * p.cout_pad * ksplit > p.scratch_floats) ksplit = 1;   // a scratch smaller than the batch needs
         }
     }
     const long px_blocks1 = (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 4) * p.B;     // workgroups with MT = 1 per N block
     // widest N tile (32*nt channels) that still leaves >= 256 workgroups; with fewer the tile is narrowed so more CUs get
     // work (the input patch is then re-staged once per N block, which is cheap at the small levels where this happens)
     int nt = 1;
-    for (int cand = 4; cand >= 1; --cand) {
+    for (int cand = std::min(4, nt_cap); cand >= 1; --cand) {
         if (p.cout_pad % (cand * 32)) continue;
         if (px_blocks1 * (p.cout_pad / (cand * 32)) >= 256 || cand == 1) { nt = cand; break; }
     }
     if ((PIV_KNOB(1) & 8) && nt == 4) nt = 2;              // A/B: 64-channel N tiles (three workgroups per CU) for 128-channel layers
-    int mt = (px_blocks1 / 2) * (p.cout_pad / (nt * 32)) >= 512 ? 2 : 1;
+    int mt = (px_blocks1 / 2) * (p.cout_pad / (nt * 32)) >= 512 && mt_cap >= 2 ? 2 : 1;
     auto need = [&](int mt_, int nt_, int &pm, int &wm) {
         const int PH = (4 * mt_ - 1) * p.S + p.KH, PW = 31 * p.S + p.KW;
         pm = cdiv(PH * PW * 2, 256);
         wm = cdiv(taps * 2 * nt_ * 32, 256);
     };
+    auto take = [&](int mt_, int nt_, int pmax, int wmax) {
+        const size_t lds = tile_lds_bytes(p, 4 * mt_, 32 * nt_);
+        CHOOSE_REQUIRE(lds <= 160 * 1024, "conv: LDS tile of %zu bytes exceeds 160 KiB (k=%dx%d s=%d)", lds, p.KH, p.KW, p.S);
+        int pm_, wm_;
+        need(mt_, nt_, pm_, wm_);
+        CHOOSE_REQUIRE(pm_ <= pmax && wm_ <= wmax, "conv: internal staging bound exceeded");
+        pl = ConvPlan{PIVLFN_CONV_PLAN_V2, 4 * mt_, 32 * nt_, 100 * pmax + wmax, ksplit};
+        return PIVLFN_OK;
+    };
     int pm, wm;
     // 16-row tiles for the 64-channel layers of the fine levels: the weight slab and the patch halo a workgroup restages per
     // K chunk are amortised over twice the pixels (same accumulator budget as the 8-row x 128-channel tile).  Measured at level 1:
     // 128->64 113 -> 129 TFLOP/s, 64->64 104 -> 119; the 32-channel layers LOSE with 16 rows (116 -> 96) and keep 8.
-    if (nt == 2 && mt == 2 && (px_blocks1 / 4) * (p.cout_pad / 64) >= 512 && !(PIV_KNOB(1) & 16)) {
+    if (nt == 2 && mt == 2 && mt_cap >= 4 && (px_blocks1 / 4) * (p.cout_pad / 64) >= 512 && !(PIV_KNOB(1) & 16)) {
         need(4, nt, pm, wm);
-        if (pm <= 5 && wm <= 5) return launch_t2<4, 2, 5, 5>(p, st);
+        if (pm <= 5 && wm <= 5) return take(4, 2, 5, 5);
     }
     need(mt, nt, pm, wm);
     if ((pm > 3 || wm > 9) && mt == 2 && nt >= 3) { mt = 1; need(mt, nt, pm, wm); }   // keep the big-staging class under 256 VGPRs
@@ -1050,23 +1091,30 @@ static int launch_conv2(const ConvParams &p_in, hipStream_t st)
     // a middle staging class (<= 5 patch loads, <= 5 slab loads per thread) for the k x 1 layers of conv_dist_R (7 x 1: a 14-row
     // patch, 4 + 4 loads): 168 instead of 240 registers, three workgroups per CU instead of two
     const bool mid = !small && pm <= 5 && wm <= 5 && !(PIV_KNOB(1) & 4);
-#define PICK(MT_, NT_)                                                                     \
-    (small ? launch_t2<MT_, NT_, 3, 9>(p, st) : launch_t2<MT_, NT_, 9, 13>(p, st))
-    if (mt == 2) {
-        switch (nt) {
-            case 4: return small ? launch_t2<2, 4, 3, 9>(p, st) : -1;
-            case 3: return small ? launch_t2<2, 3, 3, 9>(p, st) : -1;
-            case 2: return mid ? launch_t2<2, 2, 5, 5>(p, st) : PICK(2, 2);
-            default: return mid ? launch_t2<2, 1, 5, 5>(p, st) : PICK(2, 1);
-        }
-    }
-    switch (nt) {
-        case 4: return PICK(1, 4);
-        case 3: return PICK(1, 3);
-        case 2: return PICK(1, 2);
-        default: return PICK(1, 1);
-    }
-#undef PICK
+    if (mt == 2 && nt >= 3 && !small) return -1;
+    if (small) return take(mt, nt, 3, 9);
+    if (mt == 2 && mid) return take(mt, nt, 5, 5);
+    return take(mt, nt, 9, 13);
+}
+
+// The compiled v2 instantiations, by plan.  tests/test_conv_plan.py::COMPILED lists the same kernels (and launch_conv1's below) and
+// asserts that choose_conv reaches each of them: keep the two in step when a kernel is added or retired.
+static int launch_conv2(const ConvParams &p_in, const ConvPlan &pl, hipStream_t st)
+{
+    ConvParams p = p_in;
+    p.stamps = reinterpret_cast<unsigned long long *>(((unsigned long long)(unsigned)PIV_KNOB(6) << 32) | (unsigned)PIV_KNOB(5));   // tools only
+    PIV_SET_DBG(p, PIV_KNOB(7));
+    p.ksplit = pl.ksplit;
+#define T2(MT_, NT_, PM_, WM_)                                                             \
+    if (pl.rows == 4 * MT_ && pl.chans == 32 * NT_ && pl.staging == 100 * PM_ + WM_) return launch_t2<MT_, NT_, PM_, WM_>(p, st);
+    T2(4, 2, 5, 5)
+    T2(2, 4, 3, 9) T2(2, 3, 3, 9)
+    T2(2, 2, 5, 5) T2(2, 2, 3, 9) T2(2, 2, 9, 13)
+    T2(2, 1, 5, 5) T2(2, 1, 3, 9) T2(2, 1, 9, 13)
+    T2(1, 4, 3, 9) T2(1, 4, 9, 13) T2(1, 3, 3, 9) T2(1, 3, 9, 13)
+    T2(1, 2, 3, 9) T2(1, 2, 9, 13) T2(1, 1, 3, 9) T2(1, 1, 9, 13)
+#undef T2
+    PIV_REQUIRE(false, "conv: internal: no v2 kernel of %d rows x %d channels, staging class %d", pl.rows, pl.chans, pl.staging);
 }
 
 
@@ -1074,9 +1122,7 @@ template <int MT, int NT>
 static int launch_t(const ConvParams &p, hipStream_t st)
 {
     constexpr int TH = 4 * MT, BN = NT * 32;
-    const int PH = (TH - 1) * p.S + p.KH, PW = 31 * p.S + p.KW;
-    const size_t lds = ((size_t)PH * PW * PIXP + (size_t)p.KH * p.KW * 2 * BN * 4) * sizeof(float);
-    PIV_REQUIRE(lds <= 160 * 1024, "conv: LDS tile of %zu bytes exceeds 160 KiB (k=%dx%d s=%d)", lds, p.KH, p.KW, p.S);
+    const size_t lds = tile_lds_bytes(p, TH, BN);            // bound: choose_conv1
     static LdsAttr attr;
     if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_mfma_kernel<MT, NT>), 160 * 1024)) return rc;
     const int tiles = cdiv(p.Wo, 32) * cdiv(p.Ho, TH) * p.B;
@@ -1086,24 +1132,10 @@ static int launch_t(const ConvParams &p, hipStream_t st)
     return PIVLFN_OK;
 }
 
-int launch_conv(const ConvParams &p, hipStream_t st)
+// Tile choice for v1, the fallback for what v2's staging classes do not cover
+static int choose_conv1(const ConvParams &p, ConvPlan &pl, bool say)
 {
-    PIV_REQUIRE(p.nseg >= 1 && p.nseg <= 3, "conv: nseg=%d", p.nseg);
-    PIV_REQUIRE(p.cout_pad % 32 == 0 && p.cout_store <= p.cout_pad, "conv: cout_pad=%d cout_store=%d", p.cout_pad, p.cout_store);
-    PIV_REQUIRE(p.B > 0 && p.H > 0 && p.W > 0 && p.Ho > 0 && p.Wo > 0, "conv: empty shape");
-    for (int s = 0; s < p.nseg; ++s)
-        PIV_REQUIRE(p.seg[s].cload % 4 == 0 && p.seg[s].stride % 4 == 0 && p.seg[s].ptr, "conv: segment %d misaligned", s);
-    if (!(PIV_KNOB(1) & 2)) {               // shipped path: v2 (register prefetch); knob bit 1 forces v1 for A/B
-        const int rc3 = launch_conv_c3k7(p, st);
-        if (rc3 >= 0) return rc3;
-        const int rk = launch_conv_k1(p, st);
-        if (rk >= 0) return rk;
-        const int rs2 = launch_conv_s2(p, st);
-        if (rs2 >= 0) return rs2;
-        const int rc = launch_conv2(p, st);
-        if (rc >= 0) return rc;
-    }
-    PIV_REQUIRE(!p.tail, "conv: this layer's weights are packed with a 4-channel tail chunk, which only the v2 kernel understands");
+    CHOOSE_REQUIRE(!p.tail, "conv: this layer's weights are packed with a 4-channel tail chunk, which only the v2 kernel understands");
     int nt;
     if (p.cout_pad % 128 == 0) nt = 4;
     else if (p.cout_pad % 96 == 0) nt = 3;
@@ -1112,19 +1144,64 @@ int launch_conv(const ConvParams &p, hipStream_t st)
     // Two output rows per wave when that still leaves a full chip's worth of workgroups.
     const long blocks2 = (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 8) * p.B * (p.cout_pad / (nt * 32));
     const bool big = blocks2 >= 512 && (p.KH * p.KW <= 25 || nt == 1);
-    if (big) {
-        switch (nt) {
-            case 4: return launch_t<2, 4>(p, st);
-            case 3: return launch_t<2, 3>(p, st);
-            case 2: return launch_t<2, 2>(p, st);
-            default: return launch_t<2, 1>(p, st);
+    const int mt = big && tile_lds_bytes(p, 8, 32 * nt) <= 160 * 1024 ? 2 : 1;      // a refusal must not depend on the batch
+    const size_t lds = tile_lds_bytes(p, 4 * mt, 32 * nt);
+    CHOOSE_REQUIRE(lds <= 160 * 1024, "conv: LDS tile of %zu bytes exceeds 160 KiB (k=%dx%d s=%d)", lds, p.KH, p.KW, p.S);
+    pl = ConvPlan{PIVLFN_CONV_PLAN_V1, 4 * mt, 32 * nt, 0, 1};
+    return PIVLFN_OK;
+}
+
+static int launch_conv1(const ConvParams &p, const ConvPlan &pl, hipStream_t st)
+{
+#define T1(MT_, NT_) if (pl.rows == 4 * MT_ && pl.chans == 32 * NT_) return launch_t<MT_, NT_>(p, st);
+    T1(2, 4) T1(2, 3) T1(2, 2) T1(2, 1) T1(1, 4) T1(1, 3) T1(1, 2) T1(1, 1)
+#undef T1
+    PIV_REQUIRE(false, "conv: internal: no v1 kernel of %d rows x %d channels", pl.rows, pl.chans);
+}
+
+// Which kernel a call runs, from its geometry alone: no pointer is read and no device is touched, so pivlfn_conv2d_nhwc_plan reports
+// exactly what launch_conv launches.  p.scratch_floats > 0 stands for "a split-K scratch of that size exists".
+int choose_conv(const ConvParams &p, ConvPlan &pl)
+{
+    PIV_REQUIRE(p.nseg >= 1 && p.nseg <= 3, "conv: nseg=%d", p.nseg);
+    PIV_REQUIRE(p.cout_pad % 32 == 0 && p.cout_store <= p.cout_pad, "conv: cout_pad=%d cout_store=%d", p.cout_pad, p.cout_store);
+    PIV_REQUIRE(p.B > 0 && p.H > 0 && p.W > 0 && p.Ho > 0 && p.Wo > 0, "conv: empty shape");
+    for (int s = 0; s < p.nseg; ++s)
+        PIV_REQUIRE(p.seg[s].cload % 4 == 0 && p.seg[s].stride % 4 == 0, "conv: segment %d misaligned", s);
+    if (!(PIV_KNOB(1) & 2)) {               // shipped path: v2 (register prefetch); knob bit 1 forces v1 for A/B
+        if (choose_conv_c3k7(p, pl) || choose_conv_k1(p, pl) || choose_conv_s2(p, pl)) return PIVLFN_OK;
+        const int rc = choose_conv2(p, 4, 4, pl, false);
+        if (rc == PIVLFN_OK) return rc;
+        if (rc == -1) {
+            if (choose_conv1(p, pl, false) == PIVLFN_OK) return PIVLFN_OK;
+            // Neither the tile v2 wants at this batch nor v1 (no 4-channel tail chunks, one LDS tile) takes the layer: a v2 tile of
+            // fewer rows and channels may.  Same bits: the K order of an output does not depend on the tile.
+            for (int cap = 4; cap >= 1; --cap)
+                if (choose_conv2(p, cap, 1, pl, false) == PIVLFN_OK) return PIVLFN_OK;
         }
+        // conv_k1 at any tile count before a refusal: it alone takes a 4-channel tail chunk of more than 52 taps, and an image row
+        // beyond v2's descriptor range.  With these two steps every condition of a refusal is one of the geometry of a single image:
+        // whether a call is accepted never depends on the batch.
+        if (choose_conv_k1(p, pl, true)) return PIVLFN_OK;
+        return rc == -1 ? choose_conv1(p, pl, true) : choose_conv2(p, 4, 4, pl, true);
     }
-    switch (nt) {
-        case 4: return launch_t<1, 4>(p, st);
-        case 3: return launch_t<1, 3>(p, st);
-        case 2: return launch_t<1, 2>(p, st);
-        default: return launch_t<1, 1>(p, st);
+    return choose_conv1(p, pl, true);
+}
+#undef CHOOSE_REQUIRE
+
+int launch_conv(const ConvParams &p, hipStream_t st)
+{
+    ConvPlan pl;
+    ConvParams q = p;
+    if (!q.scratch) q.scratch_floats = 0;
+    if (int rc = choose_conv(q, pl)) return rc;
+    for (int s = 0; s < p.nseg; ++s) PIV_REQUIRE(p.seg[s].ptr, "conv: segment %d has no data", s);
+    switch (pl.family) {
+        case PIVLFN_CONV_PLAN_C3K7: return launch_conv_c3k7(p, st);
+        case PIVLFN_CONV_PLAN_K1: return launch_conv_k1(p, st);
+        case PIVLFN_CONV_PLAN_S2: return launch_conv_s2(p, st);
+        case PIVLFN_CONV_PLAN_V2: return launch_conv2(p, pl, st);
+        default: return launch_conv1(p, pl, st);
     }
 }
 

@@ -133,6 +133,13 @@ static const pivlfn_tensor *find(const TMap &m, const std::string &name, int d0,
     return t;
 }
 
+// What pack_conv makes of a layer's shape, for the callers that have the shape and no packed layer (pivlfn_conv2d_nhwc_plan):
+// K chunks of 8 staged channels per source, the last one a 4-channel tail chunk when cload = 4 mod 8; the streaming kernels' packings
+static inline int seg_chunks(int cload) { return (cload + 7) / 8; }
+static inline int seg_tail(int cload) { return cload % 8 != 0 && cload % 8 <= 4; }
+static inline bool packs_col7(int cout, int cin, int kh, int kw, size_t nseg, int cload0) { return kh == 7 && kw == 1 && cin == 32 && cout <= 64 && nseg == 1 && cload0 == 32; }
+static inline bool packs_row7(int cout, int cin, int kh, int kw, size_t nseg, int cload0) { return kh == 1 && kw == 7 && cin == 49 && cout == 49 && nseg == 1 && cload0 == 52; }
+
 struct SegDef { int creal, cload; int coff = -1; };   // coff: first input channel of this source in the OIHW weight (-1 = running offset)
 
 // OIHW weights -> [chunk][tap][half][cout_pad][4]; chunk = 8 staged input channels of one source.
@@ -145,7 +152,7 @@ static int pack_conv(pivlfn_net *net, const TMap &m, const std::string &name, in
     const pivlfn_tensor *b = find(m, name + ".bias", cout, 0, 0, 0, 1);
     if (!w || !b) return PIVLFN_ERR_WEIGHTS;
     int creal = 0, nchunk = 0;
-    for (auto &s : segs) { creal += s.creal; nchunk += (s.cload + 7) / 8; }
+    for (auto &s : segs) { creal += s.creal; nchunk += seg_chunks(s.cload); }
     if (creal != cin) { set_error("internal: segment channels %d != cin %d for %s", creal, cin, name.c_str()); return PIVLFN_ERR_WEIGHTS; }
     const int taps = kh * kw, cp = rup(cout, 32);
     std::vector<float> pk((size_t)nchunk * taps * 2 * cp * 4, 0.f), bias(cp, 0.f);
@@ -187,7 +194,7 @@ static int pack_conv(pivlfn_net *net, const TMap &m, const std::string &name, in
         PIV_CHECK_HIP(hipMemcpy(d, ph.data(), ph.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
         out->wpk_h = d;
     }
-    if (kh == 7 && kw == 1 && cin == 32 && cout <= 64 && segs.size() == 1 && segs[0].cload == 32) {   // conv_dist_R.0 of levels 1 and 2
+    if (packs_col7(cout, cin, kh, kw, segs.size(), segs[0].cload)) {   // conv_dist_R.0 of levels 1 and 2
         std::vector<float> pc((size_t)4 * 7 * 2 * 64 * 4, 0.f);
         for (int blk = 0; blk < 4; ++blk)
             for (int ky = 0; ky < 7; ++ky)
@@ -201,7 +208,7 @@ static int pack_conv(pivlfn_net *net, const TMap &m, const std::string &name, in
         rc = upload(net, pc, &out->wpk_c);
         if (rc) return rc;
     }
-    if (kh == 1 && kw == 7 && cin == 49 && cout == 49 && segs.size() == 1 && segs[0].cload == 52) {   // conv_dist_R.1 of levels 1 and 2
+    if (packs_row7(cout, cin, kh, kw, segs.size(), segs[0].cload)) {   // conv_dist_R.1 of levels 1 and 2
         std::vector<float> pr((size_t)4 * 7 * 3 * 64 * 4, 0.f), p12((size_t)4 * 7 * 64, 0.f);
         for (int blk = 0; blk < 4; ++blk)
             for (int kx = 0; kx < 7; ++kx)
@@ -511,6 +518,14 @@ int conv_create(const float *weight, const float *bias, int cout, int cin, int k
     c->owner = new pivlfn_net();
     c->cin = cin;
     int rc = pack_conv(c->owner, m, "c", cout, cin, kh, kw, {{cin, rup(cin, 4)}}, &c->cw);
+    if (!rc) {      // pivlfn_conv2d_nhwc_plan derives these from the shape alone
+        const ConvShape sh = conv_shape(cout, cin, kh, kw);
+        if (sh.cout_pad != c->cw.cout_pad || sh.nchunk != c->cw.nchunk || sh.tail != c->cw.tail || sh.col7 != (c->cw.wpk_c != nullptr) ||
+            sh.row7 != (c->cw.wpk_r != nullptr)) {
+            set_error("internal: conv_shape disagrees with pack_conv for %d<-%d %dx%d", cout, cin, kh, kw);
+            rc = PIVLFN_ERR_WEIGHTS;
+        }
+    }
     if (!rc && cout == 2 && cin == 32 && kh == kw && (kh == 3 || kh == 5 || kh == 7)) rc = pack_head(c->owner, m, "c", kh, &c->head, c->hb);
     if (!rc) {
         void *d = nullptr;
@@ -530,33 +545,82 @@ int conv_destroy(pivlfn_conv *c)
     return PIVLFN_OK;
 }
 
+// The kernel choice of pivlfn_conv2d_nhwc from the layer's shape and the call's geometry: its argument checks, the streaming kernels'
+// conditions and launch_conv's own choice.  No pointer is read (res only says whether there is a residual): pivlfn_conv2d_nhwc and
+// pivlfn_conv2d_nhwc_plan both come through here.  p receives everything but the pointers.  per_image: the handle's split-K scratch
+// holds one image's shares, so a batch it is too small for runs image by image (pl is then one image's plan) -- the split factor,
+// hence the summation order and the bits of a sample, is pivlfn_forward's at any B.
+int conv_forward_choose(const ConvShape &c, int x_stride, int y_stride, const float *res, int B, int H, int W, int stride, int pad_y,
+                        int pad_x, int leaky, ConvParams &p, ConvPlan &pl, bool &per_image)
+{
+    PIV_REQUIRE(x_stride % 4 == 0 && x_stride >= rup(c.cin, 4), "conv2d: x_stride=%d must be a multiple of 4 and >= %d", x_stride, rup(c.cin, 4));
+    PIV_REQUIRE(y_stride >= c.cout, "conv2d: y_stride=%d < cout=%d", y_stride, c.cout);
+    PIV_REQUIRE(stride >= 1 && pad_y >= 0 && pad_x >= 0 && H + 2 * pad_y >= c.KH && W + 2 * pad_x >= c.KW, "conv2d: bad geometry");
+    memset(&p, 0, sizeof(p));
+    p.seg[0] = ConvSeg{nullptr, rup(c.cin, 4), x_stride};
+    p.nseg = 1;
+    p.out_stride = y_stride;
+    p.cout_store = std::min(rup(c.cout, 4), y_stride);
+    p.cout_pad = c.cout_pad; p.res = res;
+    p.B = B; p.H = H; p.W = W; p.KH = c.KH; p.KW = c.KW; p.S = stride; p.padY = pad_y; p.padX = pad_x;
+    p.Ho = (H + 2 * pad_y - c.KH) / stride + 1;
+    p.Wo = (W + 2 * pad_x - c.KW) / stride + 1;
+    p.nchunk = c.nchunk; p.tail = c.tail; p.lrelu = leaky; p.cin_real = c.cin;
+    p.scratch_floats = KSPLIT_FLOATS;
+    per_image = false;
+    // the (7 x 1) distance convolution on >= 256 x 256 images: the kernel pivlfn_forward uses for it in the fp32 mode
+    if (c.col7 && !res && !leaky && stride == 1 && pad_y == 3 && pad_x == 0 && (long)H * W >= 256 * 256 && p.cout_store % 4 == 0 &&
+        (long)H * W * std::max(x_stride, y_stride) * 4 < (1L << 31) && !(PIV_KNOB(1) & 65536)) {
+        pl = ConvPlan{PIVLFN_CONV_PLAN_COL7, 16, 64, 0, 1};
+        return check_conv_col7(x_stride, y_stride, p.cout_store, c.cout == 49, B, H, W);
+    }
+    if (c.row7 && !res && !leaky && stride == 1 && pad_y == 0 && pad_x == 3 && (long)H * W >= 256 * 256 && x_stride >= 52 && y_stride >= 52 &&
+        (long)H * W * std::max(x_stride, y_stride) * 4 < (1L << 31) && !(PIV_KNOB(1) & 65536)) {
+        pl = ConvPlan{PIVLFN_CONV_PLAN_ROW7, 16, 64, 0, 1};
+        return check_conv_row7(x_stride, y_stride, B, H, W);
+    }
+    if (int rc = choose_conv(p, pl)) return rc;
+    if (B > 1) {
+        ConvParams p1 = p;
+        ConvPlan pl1;
+        p1.B = 1;
+        if (choose_conv(p1, pl1) == PIVLFN_OK && pl1.ksplit != pl.ksplit) { pl = pl1; per_image = true; }
+    }
+    return PIVLFN_OK;
+}
+
+ConvShape conv_shape(int cout, int cin, int kh, int kw)
+{
+    const int cload = rup(cin, 4);
+    return ConvShape{cout, rup(cout, 32), cin, kh, kw, seg_chunks(cload), seg_tail(cload), packs_col7(cout, cin, kh, kw, 1, cload),
+                     packs_row7(cout, cin, kh, kw, 1, cload)};
+}
+
 int conv_forward(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride, const float *res, int res_stride,
                  int B, int H, int W, int stride, int pad_y, int pad_x, int leaky, hipStream_t st)
 {
     PIV_REQUIRE(c && x && y, "conv2d: null argument");
-    PIV_REQUIRE(x_stride % 4 == 0 && x_stride >= rup(c->cin, 4), "conv2d: x_stride=%d must be a multiple of 4 and >= %d", x_stride, rup(c->cin, 4));
-    PIV_REQUIRE(y_stride >= c->cw.cout, "conv2d: y_stride=%d < cout=%d", y_stride, c->cw.cout);
-    PIV_REQUIRE(stride >= 1 && pad_y >= 0 && pad_x >= 0 && H + 2 * pad_y >= c->cw.KH && W + 2 * pad_x >= c->cw.KW, "conv2d: bad geometry");
+    const ConvShape sh{c->cw.cout, c->cw.cout_pad, c->cin, c->cw.KH, c->cw.KW, c->cw.nchunk, c->cw.tail, c->cw.wpk_c != nullptr, c->cw.wpk_r != nullptr};
     ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.seg[0] = ConvSeg{x, rup(c->cin, 4), x_stride};
-    p.nseg = 1;
-    p.wpk = c->cw.wpk; p.bias = c->cw.bias; p.out = y; p.out_stride = y_stride;
-    p.cout_store = std::min(rup(c->cw.cout, 4), y_stride);
-    p.cout_pad = c->cw.cout_pad; p.res = res; p.res_stride = res_stride;
-    p.B = B; p.H = H; p.W = W; p.KH = c->cw.KH; p.KW = c->cw.KW; p.S = stride; p.padY = pad_y; p.padX = pad_x;
-    p.Ho = (H + 2 * pad_y - c->cw.KH) / stride + 1;
-    p.Wo = (W + 2 * pad_x - c->cw.KW) / stride + 1;
-    p.nchunk = c->cw.nchunk; p.tail = c->cw.tail; p.lrelu = leaky; p.cin_real = c->cw.cin;
-    p.scratch = c->scratch; p.scratch_floats = KSPLIT_FLOATS;
-    // the (7 x 1) distance convolution on >= 256 x 256 images: the kernel pivlfn_forward uses for it in the fp32 mode
-    if (c->cw.wpk_c && !res && !leaky && stride == 1 && pad_y == 3 && pad_x == 0 && (long)H * W >= 256 * 256 && p.cout_store % 4 == 0 &&
-        (long)H * W * std::max(x_stride, y_stride) * 4 < (1L << 31) && !(PIV_KNOB(1) & 65536))
+    ConvPlan pl;
+    bool per_image;
+    if (int rc = conv_forward_choose(sh, x_stride, y_stride, res, B, H, W, stride, pad_y, pad_x, leaky, p, pl, per_image)) return rc;
+    if (pl.family == PIVLFN_CONV_PLAN_COL7)
         return launch_conv_col7(x, x_stride, c->cw.wpk_c, c->cw.bias, y, y_stride, p.cout_store, c->cw.cout == 49, B, H, W, st);
-    if (c->cw.wpk_r && !res && !leaky && stride == 1 && pad_y == 0 && pad_x == 3 && (long)H * W >= 256 * 256 && x_stride >= 52 && y_stride >= 52 &&
-        (long)H * W * std::max(x_stride, y_stride) * 4 < (1L << 31) && !(PIV_KNOB(1) & 65536))
+    if (pl.family == PIVLFN_CONV_PLAN_ROW7)
         return launch_conv_row7(x, x_stride, c->cw.wpk_r, c->cw.wpk_r12, c->cw.bias, y, y_stride, B, H, W, st);
-    return launch_conv(p, st);
+    p.seg[0].ptr = x;
+    p.wpk = c->cw.wpk; p.bias = c->cw.bias; p.out = y; p.res_stride = res_stride;
+    p.scratch = c->scratch;
+    if (!per_image) return launch_conv(p, st);
+    p.B = 1;
+    for (int b = 0; b < B; ++b) {
+        p.seg[0].ptr = x + (size_t)b * H * W * x_stride;
+        p.out = y + (size_t)b * p.Ho * p.Wo * y_stride;
+        if (res) p.res = res + (size_t)b * p.Ho * p.Wo * res_stride;
+        if (int rc = launch_conv(p, st)) return rc;
+    }
+    return PIVLFN_OK;
 }
 
 // One Conv2d over the channel concatenation of up to three sources (torch.cat + Conv2d, src/models.py:165-187, 209-217, 280: the

@@ -11,6 +11,7 @@ or zero.  Outputs are pre-filled with a sentinel.  After the call each test asse
 The whole forward runs on a workspace filled with zeros, NaN and the finite poison (including the alignment gaps between its
 buffers): flows and per-level flows must be bit-identical, and the guards around the workspace, the images, flow and levels intact."""
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -66,7 +67,8 @@ def _launch(kernel, conv, x, xs, y, ys, B, H, W, s, pad, leaky, dev, res=None, t
 
 
 def _conv_case(kernel, case, dev, terms=6, x16=0):
-    """case: cout, cin, kh, kw, stride, pad, H, W, B, x lanes past roundup(cin), y lanes past roundup(cout, 4), residual."""
+    """case: cout, cin, kh, kw, stride, pad, H, W, B, x lanes past roundup(cin), y lanes past roundup(cout, 4), residual.
+    Returns the layer, its inputs and the plain call's result for the tests that go on with them (tests/test_gpu_conv_tiles.py)."""
     co, ci, kh, kw, s, pad, H, W, B, xextra, yextra, with_res = case
     g = torch.Generator().manual_seed(co * 1000 + ci + kh * 7 + H + B + terms + 3 * x16)
     w = torch.randn(co, ci, kh, kw, generator=g) / (ci * kh * kw) ** 0.5
@@ -127,6 +129,7 @@ def _conv_case(kernel, case, dev, terms=6, x16=0):
     assert err < bar * max(1.0, want.abs().max().item()), (kernel, case, err)
     for kind in KINDS:
         assert same_bits(call(kind), plain), f"{kernel} {case}: {kind}-poisoned, guarded call differs from the plain call"
+    return SimpleNamespace(conv=conv, x=x, res=res, xs=xs, ys=ys, leaky=leaky, plain=plain)
 
 
 DIRECT = [
