@@ -393,6 +393,64 @@ size_t pivlfn_vortex_gamma_workspace_bytes(int B, int H, int W, int radius, int 
 int pivlfn_vortex_gamma(const float *flow, const unsigned char *mask, float *gamma, unsigned char *flag, int B, int H, int W, int radius,
                         int spacing, int min_count, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Lagrangian flow maps of a flow SEQUENCE: particles carried through consecutive displacement fields (pathlines, the flow map)
+ * and the largest stretching of the map, whose logarithm over the interval is the finite-time Lyapunov exponent (FTLE).  An estimated
+ * flow is a displacement field: F_k(x) is where the content at pixel x of frame k sits in frame k+1, so the flow map over an interval
+ * is x -> x + F_k(x) composed over k -- one bilinear sample per particle and field, no velocities and no integrator.  Added without
+ * an ABI bump (additive).
+ * State: N particles, pos planar [2,N] fp64 (the x plane, then the y plane; x is the column index, y the row index, pixel centres at
+ * integers) and flag [N] bytes.  A particle with a nonzero flag byte is frozen: no call changes its position or its flag again.
+ * Flag bits: PIVLFN_FLOWMAP_OUT -- the particle left the image; PIVLFN_FLOWMAP_LOST -- it met a masked or unknown vector;
+ * PIVLFN_FLOWMAP_UNDEFINED -- only in the oflag of pivlfn_flowmap_ftle.
+ * All three entry points launch only on `stream` (one launch each), never synchronise the host, allocate nothing, need no workspace
+ * and can be captured into a graph.  No result depends on the launch geometry, on N, or on how a sequence is cut into calls: B fields
+ * in one call give the bits of B calls of one field.
+ * Arithmetic contract, all fp64, every operation a correctly rounded fp64 operation in the stated order (no fma; (double) of a float
+ * is exact):
+ *
+ * pivlfn_flowmap_advect -- every particle through the B fields flows[0..B-1] in index order ([B,2,H,W] fp32 NCHW; mask [B,H,W] bytes
+ * or NULL, nonzero = the vector is not to be used).  A step depends on the particle's own state alone.
+ *   sample S_k(x, y) of field k:
+ *     1. if not (0 <= x <= W-1 and 0 <= y <= H-1): the sample sets OUT (a NaN coordinate fails the test).
+ *     2. ix = min((int)floor(x), W-2), fx = x - (double)ix;  iy = min((int)floor(y), H-2), fy = y - (double)iy  (so x = W-1 is
+ *        sampled with ix = W-2 and fx = 1).
+ *     3. the four corners (iy + {0,1}, ix + {0,1}) are all required whatever their weights: if any has a nonzero mask byte or a
+ *        component c that fails |c| <= 1e9 (NaN, +-inf, the 1e10 of a masked flow), the sample sets LOST.
+ *     4. per component, with c00 = (iy, ix), c01 = (iy, ix+1), c10 = (iy+1, ix), c11 = (iy+1, ix+1) as (double):
+ *        top = (1 - fx)*c00 + fx*c01;  bot = (1 - fx)*c10 + fx*c11;  S = top*(1 - fy) + bot*fy.
+ *   forward step (backward = 0): (u, v) = S_k(x, y);  x = x + u, y = y + v.  A sample that sets a flag leaves (x, y) as it is.  A
+ *     particle is not flagged for where a step puts it, only by the next sample taken there.
+ *   backward step (backward = 1; the caller passes the fields newest first): solves p + F_k(p) = (x, y) by exactly `iters` fixed-point
+ *     iterations, 1..32:  p_0 = (x, y);  p_i = (x, y) - S_k(p_(i-1));  the new position is p_iters.  A sample that sets a flag ends
+ *     the step with the particle frozen at (x, y).
+ *   trace: NULL, or [B,2,N] fp64 that receives the state of every particle, frozen ones included, after each field (pathlines).
+ *   Errors (PIVLFN_ERR_ARG, before any launch): H < 2 or W < 2, H*W >= 2^31, B < 0, N < 0, backward not 0 or 1, iters outside 1..32
+ *   (also where backward = 0);  then N == 0 or B == 0 succeeds, launches nothing and reads no pointer;  otherwise null flows / pos /
+ *   flag, and pos, flag or trace overlapping flows, mask or each other.
+ *
+ * pivlfn_flowmap_seed -- the h x w lattice at `spacing` pixels, row-major, n = i*w + j:  pos = ((double)(j*spacing),
+ * (double)(i*spacing)), flag = 0.
+ *
+ * pivlfn_flowmap_ftle -- for particles seeded on that lattice; X and Y are the planes of pos.  At node (i, j):
+ *     jl = max(j-1, 0), jr = min(j+1, w-1), iu = max(i-1, 0), id = min(i+1, h-1)  (central inside, one-sided at the border);
+ *     dx = (double)((jr - jl)*spacing), dy = (double)((id - iu)*spacing);
+ *     a = (X[i][jr] - X[i][jl]) / dx;  b = (X[id][j] - X[iu][j]) / dy;  c = (Y[i][jr] - Y[i][jl]) / dx;  d = (Y[id][j] - Y[iu][j]) / dy;
+ *     c11 = a*a + c*c;  c22 = b*b + d*d;  c12 = a*b + c*d;  g = 0.5*(c11 - c22);  lam = 0.5*(c11 + c22) + sqrt(g*g + c12*c12);
+ *     stretch = sqrt(lam)  [h,w] fp64: the largest singular value of the map's gradient.
+ *   UNDEFINED is set and stretch is NaN where the node's own flag or the flag of one of the four particles used is nonzero, and
+ *   everywhere if h < 2 or w < 2.  oflag [h,w] bytes = the node's own flag | UNDEFINED.
+ *   The logarithm is not part of the contract (the device's log is not correctly rounded): FTLE = log(stretch) / steps is the caller's.
+ *   Errors of seed and ftle (PIVLFN_ERR_ARG, before any launch): h < 1 or w < 1, h*w >= 2^31, spacing outside 1..32768, a lattice that
+ *   reaches past pixel 2^31, a null pointer, outputs overlapping an input or each other. */
+#define PIVLFN_FLOWMAP_OUT       1
+#define PIVLFN_FLOWMAP_LOST      2
+#define PIVLFN_FLOWMAP_UNDEFINED 4
+int pivlfn_flowmap_advect(const float *flows, const unsigned char *mask, int B, int H, int W, double *pos, unsigned char *flag, int N,
+                          int backward, int iters, double *trace, void *stream);
+int pivlfn_flowmap_seed(double *pos, unsigned char *flag, int h, int w, int spacing, void *stream);
+int pivlfn_flowmap_ftle(const double *pos, const unsigned char *flag, int h, int w, int spacing, double *stretch, unsigned char *oflag,
+                        void *stream);
+
 /* ---- snapshot POD of a flow sequence: the two device steps of proper orthogonal decomposition by the method of snapshots.  The
  * eigenproblem of the n x n matrix stays a host job.  Added without an ABI bump (additive).
  * X: n rows (snapshots) of P fp32 values, row stride ldx >= P floats.  Nothing beyond column P of a row and nothing beyond row n is

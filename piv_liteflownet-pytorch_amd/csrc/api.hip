@@ -237,6 +237,23 @@ int pivlfn_vortex_gamma(const float *flow, const unsigned char *mask, float *gam
                                (hipStream_t)stream);
 }
 
+int pivlfn_flowmap_advect(const float *flows, const unsigned char *mask, int B, int H, int W, double *pos, unsigned char *flag, int N,
+                          int backward, int iters, double *trace, void *stream)
+{
+    return launch_flowmap_advect(flows, mask, B, H, W, pos, flag, N, backward, iters, trace, (hipStream_t)stream);
+}
+
+int pivlfn_flowmap_seed(double *pos, unsigned char *flag, int h, int w, int spacing, void *stream)
+{
+    return launch_flowmap_seed(pos, flag, h, w, spacing, (hipStream_t)stream);
+}
+
+int pivlfn_flowmap_ftle(const double *pos, const unsigned char *flag, int h, int w, int spacing, double *stretch, unsigned char *oflag,
+                        void *stream)
+{
+    return launch_flowmap_ftle(pos, flag, h, w, spacing, stretch, oflag, (hipStream_t)stream);
+}
+
 int pivlfn_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, void *stream)
 {
     return launch_flow_maxrad(flow, mask, maxrad, B, H, W, (hipStream_t)stream);

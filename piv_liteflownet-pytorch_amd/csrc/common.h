@@ -302,6 +302,13 @@ size_t vortex_gamma_workspace_bytes(int B, int H, int W, int radius, int spacing
 int launch_vortex_gamma(const float *flow, const unsigned char *mask, float *gamma, unsigned char *flag, int B, int H, int W, int radius,
                         int spacing, int min_count, void *ws, size_t ws_bytes, hipStream_t st);
 
+// ---- Lagrangian flow maps (flowmap.hip): particles through consecutive displacement fields, the stretching of the map they trace ------
+int launch_flowmap_advect(const float *flows, const unsigned char *mask, int B, int H, int W, double *pos, unsigned char *flag, int N,
+                          int backward, int iters, double *trace, hipStream_t st);
+int launch_flowmap_seed(double *pos, unsigned char *flag, int h, int w, int spacing, hipStream_t st);
+int launch_flowmap_ftle(const double *pos, const unsigned char *flag, int h, int w, int spacing, double *stretch, unsigned char *oflag,
+                        hipStream_t st);
+
 // ---- snapshot POD (pod.hip): fp64 Gram matrix of n fp32 snapshots on the fp64 matrix instruction, fp64 weighted sums of snapshots -----
 size_t snapshot_gram_workspace_bytes(int n, long P);
 int launch_snapshot_gram(const float *X, int n, long P, long ldx, double *G, void *ws, size_t ws_bytes, hipStream_t st);

@@ -6,6 +6,7 @@
                 [--background min|FILE] [--minmax K] [--minmax-floor N] [--truth DIR [--truth-levels]]
                 [--color [--color-max X] [--color-wheel interp|original]] [--vort-image [--vort-max X]] [--quiver [CELL]]
                 [--quality [R] [--quality-image]] [--vortex [R] [--vortex-spacing S] [--vortex-image]] [--pod K [--pod-cell C]]
+                [--ftle [SPACING] [--ftle-steps T] [--ftle-image [--ftle-max X]]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -48,6 +49,13 @@ Differences, all deliberate:
     and the energy fractions go to <save>/pod.npz, one line per mode is printed, and with --color the modes are drawn as
     <save>/pod_mode<k>.png; `--pod-cell C` decomposes the means over C x C blocks of vectors.  2..4096 pairs per directory, a
     single process, not with -b/-c; a rejected vector that leaves a cell empty is refused (use --validate replace or a larger cell);
+  * `--ftle [SPACING]` follows fluid through the flows of every input directory, which must be a time-resolved frame sequence (not
+    -p), on the device (pivlfn.flowmap.FlowMap: particles seeded every SPACING pixels, carried through consecutive flows by one
+    bilinear sample per flow): the finite-time Lyapunov exponent over windows of `--ftle-steps T` pairs (default: the whole
+    directory), <first pair of the window>_ftle.flo with the bands ftle and stretch on the seed lattice, the summaries in
+    <save>/ftle.json, and with `--ftle-image` <name>_ftle.png (gray on 0..X of `--ftle-max`, else the window's own maximum; undefined
+    nodes red).  A trailing incomplete window is dropped and counted; with --validate flag|mask a particle that meets a rejected
+    vector is LOST.  A single process, not with -b/-c;
   * a trailing slash on an input directory is ignored (the reference would name the output directory '');
   * with -b/-c a frame whose file name has no '_' gets the tag appended (<stem>_<BBB>_<CCC>_out.flo) -- the reference splits
     the whole path at its last '_' and then either fails or lets the combinations overwrite each other.
@@ -72,7 +80,7 @@ HERE = os.path.dirname(os.path.realpath(__file__))
 sys.path.insert(0, HERE)
 
 from pivlfn import Network                               # noqa: E402
-from pivlfn import quality, synth, viz, vortex           # noqa: E402
+from pivlfn import flowmap, quality, synth, viz, vortex  # noqa: E402
 from pivlfn.datasets import Run, image_files_from_folder, pair_files     # noqa: E402
 from pivlfn.dist import shard_bounds                     # noqa: E402
 from pivlfn.evaluate import ErrorStats, flow_errors, level_errors        # noqa: E402
@@ -183,13 +191,28 @@ parser.add_argument("--pod", type=int, default=None, metavar="K",
                          "<save>/pod_mode<k>.png (not a reference flag; not with -b/-c, single process only, at most 4096 pairs)")
 parser.add_argument("--pod-cell", type=int, default=None, metavar="C",
                     help="with --pod: decompose the means over C x C blocks of vectors (default 1: every vector)")
+parser.add_argument("--ftle", type=int, nargs="?", const=1, default=None, metavar="SPACING",
+                    help="follow fluid through the consecutive flows of each input directory (pivlfn.flowmap.FlowMap; not a reference "
+                         "flag; not with -p or -b/-c, single process only): particles seeded every SPACING pixels (default 1), the "
+                         "finite-time Lyapunov exponent of their flow map in <first pair of the window>_ftle.flo (bands ftle and "
+                         "stretch, on the seed lattice) and the summaries in <save>/ftle.json.  With --validate flag|mask a particle "
+                         "that meets a rejected vector is lost, with --validate replace the replaced flow carries it")
+parser.add_argument("--ftle-steps", type=int, default=None, metavar="T",
+                    help="with --ftle: the pairs per window (default: all pairs of the directory, one window); the map is reseeded after "
+                         "each window and a trailing incomplete window is dropped")
+parser.add_argument("--ftle-image", action="store_true",
+                    help="with --ftle: also <name>_ftle.png, the exponent in gray on 0..X, nodes without a value in red")
+parser.add_argument("--ftle-max", type=float, default=None, metavar="X",
+                    help="with --ftle-image: the exponent (per pair interval) that is drawn white; without it every window takes its own "
+                         "maximum")
 PREP_FLAGS = ("background", "minmax", "minmax_floor")
 POD_FLAGS = ("pod", "pod_cell")
 QUALITY_FLAGS = ("quality", "quality_image")
 QUALITY_BAD_RGB = (255, 0, 0)
 VORTEX_FLAGS = ("vortex", "vortex_spacing", "vortex_image")
 PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
-VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + VORTEX_FLAGS + POD_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
+FTLE_FLAGS = ("ftle", "ftle_steps", "ftle_image", "ftle_max")
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -699,6 +722,62 @@ the directory has (check_pod_pairs); `wheel`: the name of the colour wheel the m
                     pictures.submit(pics[k], self.file[:-4] + f"_mode{k + 1}.png")
 
 
+class Ftle(Stage):
+    """Carries a FlowMap through the directory's flows in time order, batch by batch and on the same stream -- the raw flow with the
+    flags as the mask after "flag" and "mask", the written flow otherwise.  The directory's `pairs` pairs are cut into windows of
+    `steps`: a batch that straddles a window end is split there, the window's FTLEField stays on the device and the map is reseeded;
+    what is left after the last whole window is counted and not followed.  finish() writes the files."""
+
+    def __init__(self, spacing, steps, pairs, image, vmax, flowdir, file, mask=None):
+        self.spacing, self.steps, self.image, self.vmax, self.flowdir, self.file, self.mask = spacing, steps, image, vmax, flowdir, file, mask
+        self.windows, self.leftover = pairs // steps, pairs % steps
+        self.map, self.fields, self.skipped = None, [], 0
+
+    def __call__(self, batch):
+        flow, mask = batch.masked()
+        if self.map is None:
+            self.map = flowmap.FlowMap(flow.size(2), flow.size(3), self.spacing, device=flow.device)
+        at, n = 0, flow.size(0)
+        while at < n and len(self.fields) < self.windows:
+            take = min(n - at, self.steps - self.map.steps)
+            self.map.update(flow[at:at + take], None if mask is None else mask[at:at + take])
+            at += take
+            if self.map.steps == self.steps:
+                self.fields.append(self.map.ftle())
+                self.map.reset()
+        self.skipped += n - at
+
+    def finish(self, names, ctx):
+        """<flow dir>/<first pair of the window>_ftle.flo (bands ftle and stretch, float32), with `image` the picture beside it, and
+        <save>/ftle.json: the parameters, per window FTLEField.summary(), and the pairs left over.  A value that is not finite is
+        written as null."""
+        assert len(self.fields) == self.windows and self.skipped == self.leftover and len(names) == self.windows * self.steps + self.leftover
+        doc = {"spacing": self.spacing, "steps": self.steps, "iters": None if self.map is None else self.map.iters, "mask": self.mask,
+               "lattice": None if self.map is None else [self.map.h, self.map.w], "windows": {}, "leftover": self.leftover}
+        with FloWriter() as writer, viz.PngWriter() as pictures:
+            for k, field in enumerate(self.fields):
+                first = names[k * self.steps]
+                summary = field.summary()
+                doc["windows"][os.path.basename(flowname_modifier(first, self.flowdir, ext="", pair=False))] = summary
+                bands = torch.stack([field.ftle, field.stretch.to(torch.float32)], dim=2)
+                writer.submit(bands.cpu().numpy(), flowname_modifier(first, self.flowdir, ext="_ftle.flo", pair=False))
+                if self.image:
+                    top = self.vmax if self.vmax is not None else summary["max_ftle"]
+                    top = top if math.isfinite(top) and top > 0.0 else 1.0            # nothing defined, or nothing stretched
+                    rgb = viz.scalar_to_color(field.ftle[None].contiguous(), 0.0, top, cmap="gray", bad=QUALITY_BAD_RGB)
+                    pictures.submit(rgb[0].cpu().numpy(), flowname_modifier(first, self.flowdir, ext="_ftle.png", pair=False))
+        write_json(self.file, json_strict(doc), allow_nan=False)
+        print(f"FTLE over {self.windows} window(s) of {self.steps} pairs ({self.leftover} pairs left over) -> '{self.file}'")
+
+
+def check_ftle_pairs(pairs, steps, inputdir):
+    """The pairs per window in effect (`steps` None: the whole directory)."""
+    steps = pairs if steps is None else steps
+    if pairs < 1 or steps > pairs:
+        raise SystemExit(f"run.py: --ftle: '{inputdir}' has {pairs} pairs, fewer than the {steps} of one window")
+    return steps
+
+
 def check_pod_pairs(pairs, modes, inputdir):
     if not 2 <= pairs <= 4096:
         raise SystemExit(f"run.py: --pod: '{inputdir}' has {pairs} pairs; the method of snapshots here takes 2..4096 (decompose a "
@@ -714,6 +793,9 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
     if args.pod is not None:                # refused before anything is launched
         pairs = len(Run(root=inputdir, is_pair=args.is_pair, n_images=args.num_images, start_at=args.start))
         check_pod_pairs(pairs, args.pod, inputdir)
+    if args.ftle is not None:
+        ftle_pairs = len(Run(root=inputdir, is_pair=args.is_pair, n_images=args.num_images, start_at=args.start))
+        ftle_steps = check_ftle_pairs(ftle_pairs, args.ftle_steps, inputdir)
     if args.validate is not None:
         stages.append(Validate(args.validate, args.validate_radius, args.validate_spacing, args.validate_eps, args.validate_thresh,
                                layout.sibling("validation.json")))
@@ -731,6 +813,9 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
     if args.vortex is not None:
         stages.append(Vortex(args.vortex, args.vortex_spacing or 1, args.vortex_image, layout.sibling("vortices.json"),
                              args.validate if args.validate in ("flag", "mask") else None))
+    if args.ftle is not None:
+        stages.append(Ftle(args.ftle, ftle_steps, ftle_pairs, args.ftle_image, args.ftle_max, layout.flow, layout.sibling("ftle.json"),
+                           args.validate if args.validate in ("flag", "mask") else None))
     if args.pod is not None:
         stages.append(Pod(args.pod, args.pod_cell or 1, pairs, layout.sibling("pod.npz"), (args.color_wheel or "interp") if args.color else None))
     return stages
@@ -868,14 +953,14 @@ def main_mod(net, inputdir, savedir, start_id, num_images, device, mod_factors: 
 
 
 def args_lines(args) -> List[str]:
-    """The lines of args.txt.  The flags of validation, pre-processing, scoring, pictures, quality and vortices appear only in runs that use them:
+    """The lines of args.txt.  The flags of validation, pre-processing, scoring, pictures, quality, vortices and flow maps appear only in runs that use them:
     without them the file is what it was before they existed."""
     prep, pictures = _used(args, PREP_FLAGS), _used(args, PICTURE_FLAGS)
     return [f"{k}: {v}\n" for k, v in sorted(vars(args).items())
             if not ((args.validate is None and k.startswith("validate")) or (not prep and k in PREP_FLAGS) or
                     (args.truth is None and k in TRUTH_FLAGS) or (not pictures and k in PICTURE_FLAGS) or
                     (args.quality is None and k in QUALITY_FLAGS) or (args.vortex is None and k in VORTEX_FLAGS) or
-                    (args.pod is None and k in POD_FLAGS))]
+                    (args.pod is None and k in POD_FLAGS) or (args.ftle is None and k in FTLE_FLAGS))]
 
 
 def load_weights(args) -> Tuple[dict, str]:
@@ -965,6 +1050,20 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.vortex is not None:
         refuse_mods(args, "--vortex is")
         checked("--vortex: ", vortex.check_params, args.vortex, 1 if args.vortex_spacing is None else args.vortex_spacing, None)
+    if (args.ftle_steps is not None or args.ftle_image or args.ftle_max is not None) and args.ftle is None:
+        raise SystemExit("run.py: --ftle-steps, --ftle-image and --ftle-max need --ftle")
+    if args.ftle is not None:
+        refuse_mods(args, "--ftle is")
+        if args.is_pair:
+            raise SystemExit("run.py: --ftle is not available with -p (the pairs of a pair folder are not consecutive in time)")
+        refuse_sharded("--ftle", "a flow map follows the pairs of a directory in order, on one device")
+        checked("--ftle: ", flowmap.check_params, None, None, args.ftle)
+        if args.ftle_steps is not None and args.ftle_steps < 1:
+            raise SystemExit(f"run.py: --ftle-steps {args.ftle_steps}: a window has at least 1 pair")
+        if args.ftle_max is not None and not args.ftle_image:
+            raise SystemExit("run.py: --ftle-max needs --ftle-image")
+        if args.ftle_max is not None and not (math.isfinite(args.ftle_max) and args.ftle_max > 0):
+            raise SystemExit(f"run.py: --ftle-max {args.ftle_max} must be a finite positive number")
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run.py: this build has no CPU path (the reference's correlation has none either, "
                          "src/correlation.py:339-340); a GPU is required")
