@@ -2,10 +2,7 @@
 #include <atomic>
 #include <mutex>
 #include <vector>
-#include "common.h"
-
-struct pivlfn_net;
-struct pivlfn_conv;
+#include "net.h"
 
 namespace pivlfn {
 
@@ -49,37 +46,6 @@ void set_error(const char *fmt, ...)
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-
-int net_create(const pivlfn_tensor *tensors, int n, float starting_scale, int lowest, const float mean[6], pivlfn_net **out);
-size_t net_workspace_bytes(const pivlfn_net *net, int B, int H, int W);
-size_t net_levels_floats(const pivlfn_net *net, int B, int H, int W);
-int net_forward(pivlfn_net *net, const float *img1, const float *img2, float *flow, float *levels, int B, int H, int W,
-                void *ws, size_t ws_bytes, hipStream_t st);
-int net_destroy(pivlfn_net *net);
-int net_profile_enable(pivlfn_net *net, int level);
-int net_profile_read(pivlfn_net *net, double *ms, double *ms_empty, long *launches, int reset);
-int conv_create(const float *weight, const float *bias, int cout, int cin, int kh, int kw, pivlfn_conv **out);
-int conv_destroy(pivlfn_conv *c);
-int conv_forward(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride, const float *res, int res_stride,
-                 int B, int H, int W, int stride, int pad_y, int pad_x, int leaky, hipStream_t st);
-int conv_forward_h(const pivlfn_conv *c, const void *x, int x_stride, int x_f16, void *y, int y_stride, int y_f16,
-                   int B, int H, int W, int stride, int pad_y, int pad_x, int leaky, hipStream_t st);
-int net_set_precision(pivlfn_net *net, int precision);
-int conv_forward_x(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride,
-                   int B, int H, int W, int stride, int pad_y, int pad_x, int leaky, int terms, hipStream_t st);
-int conv_head_forward(const pivlfn_conv *c, const float *x, const float *res4, float *out4, int B, int H, int W, hipStream_t st);
-int conv_create_cat(const float *weight, const float *bias, int cout, int nsrc, const int *channels, int kh, int kw, pivlfn_conv **out);
-int conv_forward_cat(const pivlfn_conv *c, int nsrc, const float *const *x, const int *x_stride, float *y, int y_stride,
-                     int B, int H, int W, int leaky, hipStream_t st);
-int conv_forward_wb(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride, int B, int H, int W, int leaky,
-                    int terms, hipStream_t st);
-int conv_forward_w(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride, int B, int H, int W, int leaky,
-                   hipStream_t st, int tile);
-int upconv_forward(const float *in, const float *w, float *out, int B, int H, int W, int quads, int stride_in, int stride_out,
-                   hipStream_t st);
-int conv1_fused_forward(const float *w1, const float *b1, const float *we, const float *be, const float *wf, const float *bfe,
-                        const float *x, float *out, float *out_ext, float *out_feat, int N, int H, int W, int B_feat, int *fused,
-                        hipStream_t st);
 
 }  // namespace pivlfn
 

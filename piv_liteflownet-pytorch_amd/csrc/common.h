@@ -129,11 +129,6 @@ struct ConvPlan { int family, rows, chans, staging, ksplit; };
 // The launcher's decision from the geometry alone (no pointer read, no device call); scratch_floats == 0 stands for "no scratch".
 int choose_conv(const ConvParams &p, ConvPlan &pl);
 int launch_conv(const ConvParams &p, hipStream_t st);
-// A single-source layer's shape as pivlfn_conv_create packs it, and pivlfn_conv2d_nhwc's kernel choice for a call of it (net.hip)
-struct ConvShape { int cout, cout_pad, cin, KH, KW, nchunk, tail; bool col7, row7; };
-ConvShape conv_shape(int cout, int cin, int kh, int kw);
-int conv_forward_choose(const ConvShape &c, int x_stride, int y_stride, const float *res, int B, int H, int W, int stride, int pad_y,
-                        int pad_x, int leaky, ConvParams &p, ConvPlan &pl, bool &per_image);
 // NetC.conv1 with the two 1 x 1 layers that read its output at level 1 -- NetC_ext (32 -> 64, both frames) and Regularization's
 // moduleFeat (32 -> 128, first frame) -- computed from the activated accumulators in the same kernel (conv_mfma.hip).
 struct Conv1Fuse {

@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void conv_col7_kernel(const float *__restri
     }       // tiles of the workgroup
 }
 
-// wf: [4 blocks][7][2][64][4] fragments (net.hip pack_conv), bias: [64]; single48: the layer has 49 output channels and block 3 of
+// wf: [4 blocks][7][2][64][4] fragments (net_weights.hip pack_conv), bias: [64]; single48: the layer has 49 output channels and block 3 of
 // wf holds channel 48's weights replicated over the slots (vector path of the fourth wave)
 // What launch_conv_col7 accepts, apart from its pointers (also behind pivlfn_conv2d_nhwc_plan)
 int check_conv_col7(int x_stride, int out_stride, int cout_store, int single48, int B, int H, int W)
@@ -560,7 +560,7 @@ __global__ __launch_bounds__(256, 2) void conv_row7_kernel(const float *__restri
     }       // tiles of the workgroup
 }
 
-// wf: [4 blocks][7][3][64][4] fragments of channel quads kq + 4 g, wf12: [4][7][64] = channel 48 in lane group 0 (net.hip pack_conv);
+// wf: [4 blocks][7][3][64][4] fragments of channel quads kq + 4 g, wf12: [4][7][64] = channel 48 in lane group 0 (net_weights.hip pack_conv);
 // block 3 of both holds output channel 48's weights replicated over the slots; bias: [64]
 // What launch_conv_row7 accepts, apart from its pointers (also behind pivlfn_conv2d_nhwc_plan)
 int check_conv_row7(int x_stride, int out_stride, int B, int H, int W)

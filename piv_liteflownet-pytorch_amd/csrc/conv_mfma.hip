@@ -660,7 +660,7 @@ __global__ __launch_bounds__(256, FUSE ? 2 : 3) void conv_c3k7_kernel(const Conv
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int row = lane & 31, hh = lane >> 5;
     if ((int)blockIdx.x >= ntiles) return;
-    // weight fragments: slot s = 3 kx + c of row ky is wpk[((ky * 7 + kx) * 2 + (c >> 1)) * cout_pad + n][c & 1] (net.hip pack_conv,
+    // weight fragments: slot s = 3 kx + c of row ky is wpk[((ky * 7 + kx) * 2 + (c >> 1)) * cout_pad + n][c & 1] (net_weights.hip pack_conv,
     // 4-channel tail layout); slot 21 is the pad
     float wq[7][11];
 #pragma unroll

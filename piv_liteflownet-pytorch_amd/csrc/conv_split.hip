@@ -634,7 +634,7 @@ static int launch_xbig(const ConvParamsX &p, hipStream_t st)
     return PIVLFN_OK;
 }
 
-// Which layers the kernel takes (net.hip asks before routing): stride 1 with at most 7 taps per kernel row, or 3 x 3 at stride 2
+// Which layers the kernel takes (conv_layer.hip asks before routing): stride 1 with at most 7 taps per kernel row, or 3 x 3 at stride 2
 // with three-term products (4-row tiles: the stride-2 patch of an 8-row tile does not fit twice per CU); 16-byte granular sources.
 bool conv_split_supports(int KH, int KW, int S, int cout_pad, int terms)
 {
