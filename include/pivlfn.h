@@ -451,6 +451,66 @@ int pivlfn_flowmap_seed(double *pos, unsigned char *flag, int h, int w, int spac
 int pivlfn_flowmap_ftle(const double *pos, const unsigned char *flag, int h, int w, int spacing, double *stretch, unsigned char *oflag,
                         void *stream);
 
+/* ---- synthetic PIV pairs from a known flow: N particles carried through ONE displacement field (pivlfn_particles_displace) and
+ * particle images rendered as sums of Gaussian blobs (pivlfn_particles_render): rendering a seeding before and after the displacement
+ * gives an image pair whose true displacement is the field.  Added without an ABI bump (additive).
+ * Coordinates as in the flow-map section: x is the column, y the row, pixel centres at integers.  Both entry points launch only on
+ * `stream`, never synchronise the host, allocate nothing and can be captured into a graph as one linear chain of kernels.
+ *
+ * pivlfn_particles_displace -- pos [2,N] fp64 planar (x plane, y plane);  flow [2,H,W] fp32 (u, v);  mask [H,W] bytes or NULL, nonzero =
+ * the vector is not to be used;  flag [N] bytes, read and written;  out [2,N] fp64.  One launch.  All fp64, every operation a correctly
+ * rounded fp64 operation in the stated order (no fma; (double) of a float is exact):
+ *   0. a particle whose flag byte is nonzero on entry is copied through: out = pos, the flag as it was.
+ *   1. a NaN coordinate sets PIVLFN_PARTICLES_BAD; out = pos.
+ *   2. clamp to the image:  xc = 0.0 if x < 0, (double)(W-1) if x > W-1, else x (so -0.0 and +-inf are defined);  yc likewise with H.
+ *      A particle in the seeding margin round the image takes the displacement of the edge.
+ *   3. the cell, as the flow-map sampler: ix = min((int)floor(xc), W-2), fx = xc - (double)ix;  iy and fy likewise.
+ *   4. method 0, bilinear: the four corners c00 = (iy, ix), c01 = (iy, ix+1), c10 = (iy+1, ix), c11 = (iy+1, ix+1) as (double), per
+ *      component:  top = (1 - fx)*c00 + fx*c01;  bot = (1 - fx)*c10 + fx*c11;  S = top*(1 - fy) + bot*fy.
+ *      method 1, Catmull-Rom bicubic (Keys, a = -0.5): 16 taps at rows iy-1 .. iy+2 and columns ix-1 .. ix+2, every tap index clamped to
+ *      the image.  Weights of the taps -1, 0, 1, 2 as polynomials in f (f = fx along x, fy along y), evaluated as written:
+ *        w0 = ((-0.5*f + 1.0)*f - 0.5)*f;   w1 = ((1.5*f - 2.5)*f)*f + 1.0;   w2 = ((-1.5*f + 2.0)*f + 0.5)*f;   w3 = ((0.5*f - 0.5)*f)*f.
+ *      Along x first, per row r = 0..3 and component:  row_r = ((w0*c_r0 + w1*c_r1) + w2*c_r2) + w3*c_r3 with the weights of fx;
+ *      then along y:  S = ((w0*row_0 + w1*row_1) + w2*row_2) + w3*row_3 with the weights of fy.
+ *   5. every tap of the method is required whatever its weight: one with a nonzero mask byte or a component c that fails |c| <= 1e9
+ *      (NaN, +-inf, the 1e10 of a masked flow) sets PIVLFN_PARTICLES_LOST; out = pos.
+ *   6. otherwise out = (x + Su, y + Sv), of the unclamped position, and the flag stays 0.
+ *   Errors (PIVLFN_ERR_ARG, before any launch): H < 2 or W < 2, H*W >= 2^31, N < 0, method not 0 or 1;  then N == 0 succeeds, launches
+ *   nothing and reads no pointer;  otherwise null pos / flow / flag / out, and out or flag overlapping pos, flow, mask or each other.
+ *
+ * pivlfn_particles_render -- B images of N particles each.  pos [B,2,N] fp64;  diam [B,N] fp32, the diameter in pixels;  amp [B,N] fp32,
+ * the peak grey level;  flag [B,N] bytes or NULL;  intensity [B,H,W] fp32 and image [B,H,W] bytes, both written completely;  radius R in
+ * 1..8;  workspace: 8-byte aligned, at least pivlfn_particles_render_workspace_bytes(B,N,H,W,radius) bytes (0 for arguments out of
+ * range), needs no initial contents.  Five launches in a chain (three where N == 0: nothing to bin); integer atomics only.
+ *   particle:  left out if its flag byte is nonzero, if x, y, diam or amp is not finite, if diam <= 0 or amp < 0, if |x| >= 2^30 or
+ *              |y| >= 2^30, or if w below is not finite (a diameter under 4e-19).  Otherwise ix = (int)floor(x), iy = (int)floor(y)
+ *              (floor, not truncation: the margin has negative coordinates);  its footprint is the pixels j in [ix-R, ix+R+1],
+ *              i in [iy-R, iy+R+1] that lie inside the image;  in fp32, once:  s = 0.5f*diam;  w = 1.0f/(s*s)  (a correctly rounded division).
+ *   term:      per pixel (i, j) of the footprint, fp32, every operation rounded on its own (no fma):
+ *              dx = (float)((double)j - x);  dy = (float)((double)i - y);  q = (dx*dx + dy*dy)*w;  t = amp*expf(-q),  expf within one ulp.
+ *   pixel:     intensity[i][j] = the fp32 sum of the t of all particles whose footprint holds the pixel, added in ASCENDING PARTICLE
+ *              INDEX starting from +0.0f;  image[i][j] = (unsigned char)min(intensity, 255.0f), truncating.
+ *   The order of the sum is fixed by this contract and not by the launch geometry, by how the particles were binned or by the batch: an
+ *   image has the same bits alone, inside any batch, whatever the workspace held, and from run to run.
+ *   Against a sum V of the same terms in exact arithmetic, with A = the sum of amp and n = the number of the covering particles and
+ *   u = 2^-24:  dx and dy carry one rounding each (the fp64 difference adds less than 2^-52 of it), so q is off by at most 7u relative
+ *   (3u in each square -- two from dx, one of its own --, one more in their sum, two in w -- s*s and the division --, one in the
+ *   product);  d(e^-q) = q e^-q dq/q and q e^-q <= 1/e, so the exponential is off by at most 7u/e + 2u (its own ulp is up to 2u
+ *   relative) and the product with amp by one more rounding: a term is off by at most about 5.6u*amp, and 8u*amp leaves margin;
+ *   all terms are >= 0, so each of the n additions rounds a partial sum <= V:
+ *       |intensity - V| <= 2^-21*A + n*2^-24*V.
+ *   Errors (PIVLFN_ERR_ARG, before any launch): H < 1 or W < 1, H or W > 2^31 - 17, H*W >= 2^31, B < 0 or N < 0, radius outside 1..8;  then B == 0 succeeds,
+ *   launches nothing and reads no pointer;  otherwise B*ceil(H/16)*ceil(W/16) >= 2^31 tiles, B*N >= 2^39, null intensity / image /
+ *   workspace, null pos / diam / amp where N > 0, a misaligned or too-small workspace, and intensity, image or the workspace overlapping
+ *   an input or each other.  N == 0 with B > 0 writes images of zeros. */
+#define PIVLFN_PARTICLES_LOST 2
+#define PIVLFN_PARTICLES_BAD  8
+int pivlfn_particles_displace(const double *pos, const float *flow, const unsigned char *mask, int H, int W, int N, int method,
+                              unsigned char *flag, double *out, void *stream);
+size_t pivlfn_particles_render_workspace_bytes(int B, int N, int H, int W, int radius);
+int pivlfn_particles_render(const double *pos, const float *diam, const float *amp, const unsigned char *flag, int B, int N, int H, int W,
+                            int radius, float *intensity, unsigned char *image, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- snapshot POD of a flow sequence: the two device steps of proper orthogonal decomposition by the method of snapshots.  The
  * eigenproblem of the n x n matrix stays a host job.  Added without an ABI bump (additive).
  * X: n rows (snapshots) of P fp32 values, row stride ldx >= P floats.  Nothing beyond column P of a row and nothing beyond row n is

@@ -220,6 +220,24 @@ int pivlfn_flowmap_ftle(const double *pos, const unsigned char *flag, int h, int
     return launch_flowmap_ftle(pos, flag, h, w, spacing, stretch, oflag, (hipStream_t)stream);
 }
 
+int pivlfn_particles_displace(const double *pos, const float *flow, const unsigned char *mask, int H, int W, int N, int method,
+                              unsigned char *flag, double *out, void *stream)
+{
+    return launch_particles_displace(pos, flow, mask, H, W, N, method, flag, out, (hipStream_t)stream);
+}
+
+size_t pivlfn_particles_render_workspace_bytes(int B, int N, int H, int W, int radius)
+{
+    return particles_render_workspace_bytes(B, N, H, W, radius);
+}
+
+int pivlfn_particles_render(const double *pos, const float *diam, const float *amp, const unsigned char *flag, int B, int N, int H, int W,
+                            int radius, float *intensity, unsigned char *image, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return launch_particles_render(pos, diam, amp, flag, B, N, H, W, radius, intensity, image, workspace, workspace_bytes,
+                                   (hipStream_t)stream);
+}
+
 int pivlfn_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, void *stream)
 {
     return launch_flow_maxrad(flow, mask, maxrad, B, H, W, (hipStream_t)stream);

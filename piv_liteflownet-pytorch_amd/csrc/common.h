@@ -304,6 +304,13 @@ int launch_flowmap_seed(double *pos, unsigned char *flag, int h, int w, int spac
 int launch_flowmap_ftle(const double *pos, const unsigned char *flag, int h, int w, int spacing, double *stretch, unsigned char *oflag,
                         hipStream_t st);
 
+// ---- synthetic PIV pairs (particles.hip): particles through one displacement field, particle images as ordered sums of Gaussian blobs --
+int launch_particles_displace(const double *pos, const float *flow, const unsigned char *mask, int H, int W, int N, int method,
+                              unsigned char *flag, double *out, hipStream_t st);
+size_t particles_render_workspace_bytes(int B, int N, int H, int W, int radius);
+int launch_particles_render(const double *pos, const float *diam, const float *amp, const unsigned char *flag, int B, int N, int H, int W,
+                            int radius, float *intensity, unsigned char *image, void *workspace, size_t workspace_bytes, hipStream_t st);
+
 // ---- snapshot POD (pod.hip): fp64 Gram matrix of n fp32 snapshots on the fp64 matrix instruction, fp64 weighted sums of snapshots -----
 size_t snapshot_gram_workspace_bytes(int n, long P);
 int launch_snapshot_gram(const float *X, int n, long P, long ldx, double *G, void *ws, size_t ws_bytes, hipStream_t st);

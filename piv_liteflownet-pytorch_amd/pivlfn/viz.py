@@ -351,6 +351,15 @@ def write_png(path: str, rgb: np.ndarray, compress_level: int = PNG_COMPRESS_LEV
     PIL.Image.fromarray(np.ascontiguousarray(rgb), "RGB").save(path, format="PNG", compress_level=compress_level)
 
 
+def write_png_gray(path: str, gray: np.ndarray, compress_level: int = PNG_COMPRESS_LEVEL) -> None:
+    """uint8 [H,W] -> an 8-bit grey PNG file (a particle image): write_png's sibling for one channel."""
+    import PIL.Image
+    if not isinstance(gray, np.ndarray) or gray.dtype != np.uint8 or gray.ndim != 2:
+        raise TypeError(f"write_png_gray: expected a uint8 array [H,W], got "
+                        f"{gray.dtype if isinstance(gray, np.ndarray) else type(gray).__name__} {getattr(gray, 'shape', '')}")
+    PIL.Image.fromarray(np.ascontiguousarray(gray), "L").save(path, format="PNG", compress_level=compress_level)
+
+
 class PngWriter:
     """Background writer, as flo.FloWriter: submit(rgb_hw3, path) returns immediately; close() drains.  Errors surface on close()."""
 
@@ -368,9 +377,12 @@ class PngWriter:
             if item is None:
                 return
             try:
-                write_png(item[1], item[0], self._level)
+                self._write(item[1], item[0])
             except Exception as e:          # noqa: BLE001
                 self._err.append(e)
+
+    def _write(self, path: str, image: np.ndarray) -> None:
+        write_png(path, image, self._level)
 
     def submit(self, rgb: np.ndarray, filename: str) -> None:
         self._q.put((rgb, filename))
@@ -388,3 +400,10 @@ class PngWriter:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class GrayPngWriter(PngWriter):
+    """PngWriter for 8-bit grey images: submit(gray_hw, path)."""
+
+    def _write(self, path: str, image: np.ndarray) -> None:
+        write_png_gray(path, image, self._level)
