@@ -541,6 +541,37 @@ size_t pivlfn_snapshot_gram_workspace_bytes(int n, long P);
 int pivlfn_snapshot_gram(const float *X, int n, long P, long ldx, double *G, void *ws, size_t ws_bytes, void *stream);
 int pivlfn_snapshot_project(const float *X, int n, long P, long ldx, const double *Wt, int K, double *out, void *stream);
 
+/* ---- two-point statistics of a flow SEQUENCE: the sums from which the spatial correlation functions R_uu(r), R_vv(r), R_uv(r) and the
+ * second- and third-order structure functions follow, per image row, for separations along a row and down a column.  Added without an
+ * ABI bump (additive).
+ * flow: NCHW [B,2,H,W] fp32;  mask: [B,H,W] bytes or NULL, nonzero = leave the vector out;  mean: [2,H,W] fp64 (the planes of u and v)
+ * or NULL;  acc: [2, max_sep+1, PIVLFN_TWOPOINT_TERMS, H] fp64, read and written once per call: direction d (0: the partner lies r*step
+ * columns to the right, 1: r*step rows below), separation index r = 0..max_sep, term, base row y.  One launch, only on `stream`; no
+ * allocation, no workspace, no host synchronisation, no floating-point atomics; can be captured into a graph.  No value depends on the
+ * launch geometry or on how a sequence is cut into calls: B frames in one call give the bits of B calls of one frame.
+ * Arithmetic contract, all fp64, every operation rounded on its own (no fma; (double) of a float is exact):
+ *   validity:     k(p) = 1 iff (mask is NULL or mask(p) == 0) and |u(p)| <= 1e9 && |v(p)| <= 1e9 (the rule of pivlfn_vortex_gamma: NaN
+ *                 compares false; the 1e10 of a masked flow is invalid by itself).
+ *   values:       U(p) = (double)u(p) - mean_u(p), V(p) = (double)v(p) - mean_v(p);  with a NULL mean U = (double)u, V = (double)v.
+ *   pair:         base point a = (y, x);  partner b = (y, x + r*step) for d = 0 and (y + r*step, x) for d = 1.  The pair takes part iff
+ *                 b lies inside the image and k(a) = k(b) = 1.  A pair that does not take part is +0.0 in every term, the count
+ *                 included; its products are not formed (no 0 * NaN).
+ *   increments:   dL along the separation, dT across it:  d = 0: dL = Ub - Ua, dT = Vb - Va;  d = 1: dL = Vb - Va, dT = Ub - Ua.
+ *   terms:        0: 1 (the count);  1..4: Ua, Va, Ub, Vb;  5..8: Ua*Ua, Va*Va, Ub*Ub, Vb*Vb;  9..12: Ua*Ub, Va*Vb, Ua*Vb, Va*Ub;
+ *                 13: (dL*dL)*dL;  14: (dL*dT)*dT.
+ *   row sum:      for every (frame, d, r, term, row y) the sum over x = 0..W-1 is the root of the binary tree t[i] = t[2i] + t[2i+1]
+ *                 whose leaves are the terms at x = 0..W-1 padded with +0.0 to the next power of two >= W (a row of one pixel is its
+ *                 own root): the 1-D analogue of the tree of pivlfn_flow_errors.
+ *   accumulation: acc[d][r][term][y] = ((acc_before + rowsum(frame 0)) + rowsum(frame 1)) + ..., in frame order.
+ *   exactness:    the counts are exact integers;  with a NULL mean every product of two values is exact in fp64 (24 x 24 bits), so
+ *                 only the additions round.
+ * Errors (PIVLFN_ERR_ARG, before any launch): H < 1 or W < 1, B < 0, H*W >= 2^31, W > 16384, max_sep outside 0..255, step outside
+ * 1..16;  then B == 0 succeeds, launches nothing and reads no pointer;  otherwise null flow or acc, and acc overlapping flow, mask or
+ * mean. */
+#define PIVLFN_TWOPOINT_TERMS 15
+int pivlfn_twopoint_accumulate(const float *flow, const unsigned char *mask, const double *mean, double *acc, int B, int H, int W,
+                               int max_sep, int step, void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

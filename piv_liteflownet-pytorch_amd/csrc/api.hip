@@ -238,6 +238,12 @@ int pivlfn_particles_render(const double *pos, const float *diam, const float *a
                                    (hipStream_t)stream);
 }
 
+int pivlfn_twopoint_accumulate(const float *flow, const unsigned char *mask, const double *mean, double *acc, int B, int H, int W,
+                               int max_sep, int step, void *stream)
+{
+    return launch_twopoint_accumulate(flow, mask, mean, acc, B, H, W, max_sep, step, (hipStream_t)stream);
+}
+
 int pivlfn_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, void *stream)
 {
     return launch_flow_maxrad(flow, mask, maxrad, B, H, W, (hipStream_t)stream);

@@ -316,6 +316,10 @@ size_t snapshot_gram_workspace_bytes(int n, long P);
 int launch_snapshot_gram(const float *X, int n, long P, long ldx, double *G, void *ws, size_t ws_bytes, hipStream_t st);
 int launch_snapshot_project(const float *X, int n, long P, long ldx, const double *Wt, int K, double *out, hipStream_t st);
 
+// ---- two-point statistics (twopoint.hip): per-row sums of pair terms at separations along x and y, accumulated over a sequence ----------
+int launch_twopoint_accumulate(const float *flow, const unsigned char *mask, const double *mean, double *acc, int B, int H, int W,
+                               int max_sep, int step, hipStream_t st);
+
 // ---- image pre-processing (preproc.hip): [n,H,W,3] uint8 frames -> background minimum [H,W,3], network input [n,3,H,W] fp32 --------
 int launch_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, hipStream_t st);
 int launch_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W, int k, int floor,

@@ -7,6 +7,7 @@
                 [--color [--color-max X] [--color-wheel interp|original]] [--vort-image [--vort-max X]] [--quiver [CELL]]
                 [--quality [R] [--quality-image]] [--vortex [R] [--vortex-spacing S] [--vortex-image]] [--pod K [--pod-cell C]]
                 [--ftle [SPACING] [--ftle-steps T] [--ftle-image [--ftle-max X]]]
+                [--twopoint [R] [--twopoint-step S] [--twopoint-mean FILE]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -44,6 +45,11 @@ Differences, all deliberate:
     <name>_gamma.flo with the two bands, the vortex centres and core areas of every pair and the summary of the run in
     <save>/vortices.json, and with `--vortex-image` <name>_gamma2.png (Gamma2 on -1..1 in blue - white - red, undefined pixels
     black); with --validate flag|mask the rejected vectors are left out;
+  * `--twopoint [R]` accumulates the two-point statistics of the flows of every input directory on the device
+    (pivlfn.twopoint.TwoPointStats: per row the sums behind R_uu, R_vv, R_uv and the structure functions at the separations
+    0..R times `--twopoint-step S` pixels along x and along y; with --validate flag|mask the rejected vectors are left out) and
+    writes <save>/twopoint.npz and <save>/twopoint.json with the integral scales, Taylor microscales and noise shares;
+    `--twopoint-mean FILE` takes the per-pixel mean of a --stats run out first (flows that are not homogeneous along a row);
   * `--pod K` decomposes the flows of every input directory after it has been processed (pivlfn.pod.FlowPOD, snapshot POD: the
     Gram matrix of the flows in float64 on the device, its eigenvectors on the host): the first K modes, the mean, the coefficients
     and the energy fractions go to <save>/pod.npz, one line per mode is printed, and with --color the modes are drawn as
@@ -91,6 +97,8 @@ from pivlfn.pipeline import PairLoader, stream_pairs     # noqa: E402
 from pivlfn.pod import FlowPOD                           # noqa: E402
 from pivlfn.postpro import FlowStats                     # noqa: E402
 from pivlfn.preproc import FrameBackground, Preprocessor                 # noqa: E402
+from pivlfn.twopoint import TwoPointStats                # noqa: E402
+from pivlfn.twopoint import check_params as check_twopoint               # noqa: E402
 from pivlfn.preproc import check_params as check_prep    # noqa: E402
 from pivlfn.validate import NOT_REPLACED, OUTLIER, UNKNOWN, MaskedFlowStats, validate_flow      # noqa: E402
 from pivlfn.validate import check_params as check_validate               # noqa: E402
@@ -205,14 +213,25 @@ parser.add_argument("--ftle-image", action="store_true",
 parser.add_argument("--ftle-max", type=float, default=None, metavar="X",
                     help="with --ftle-image: the exponent (per pair interval) that is drawn white; without it every window takes its own "
                          "maximum")
+parser.add_argument("--twopoint", type=int, nargs="?", const=64, default=None, metavar="R",
+                    help="accumulate the two-point statistics of the flows of each input directory on the device "
+                         "(pivlfn.twopoint.TwoPointStats; not a reference flag; not with -b/-c, single process only): correlations and "
+                         "structure functions at the separations 0..R (0..255, default 64) along x and y, written to "
+                         "<save>/twopoint.npz, the integral scales, Taylor microscales and noise shares to <save>/twopoint.json")
+parser.add_argument("--twopoint-step", type=int, default=None, metavar="S",
+                    help="with --twopoint: the pixels between two separations, 1..16 (default 1)")
+parser.add_argument("--twopoint-mean", type=str, default=None, metavar="FILE",
+                    help="with --twopoint: a stats.npz of an earlier --stats run over the same frames; its mean_u and mean_v are taken "
+                         "out of every vector before the sums are formed")
 PREP_FLAGS = ("background", "minmax", "minmax_floor")
+TWOPOINT_FLAGS = ("twopoint", "twopoint_step", "twopoint_mean")
 POD_FLAGS = ("pod", "pod_cell")
 QUALITY_FLAGS = ("quality", "quality_image")
 QUALITY_BAD_RGB = (255, 0, 0)
 VORTEX_FLAGS = ("vortex", "vortex_spacing", "vortex_image")
 PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
 FTLE_FLAGS = ("ftle", "ftle_steps", "ftle_image", "ftle_max")
-VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -430,6 +449,39 @@ class Stats(Stage):
     def finish(self, names, ctx):
         if self.stats is not None:
             self.stats.save(self.file, **self.extra)
+
+
+class TwoPoint(Stage):
+    """Adds every batch of flows to a TwoPointStats, created at the first batch's size and fed like Stats: after "flag" and "mask" the
+    raw flow with the flags as the mask, otherwise the written flow.  finish() writes the sums and what follows from them."""
+
+    def __init__(self, max_sep, step, mean, file, json_file):
+        self.max_sep, self.step, self.mean, self.file, self.json_file = max_sep, step, mean, file, json_file
+        self.stats, self.mode = None, None
+
+    def __call__(self, batch):
+        flow, flag = batch.masked()
+        if self.stats is None:
+            try:
+                self.stats = TwoPointStats(flow.size(2), flow.size(3), self.max_sep, self.step, self.mean, flow.device)
+            except ValueError as e:
+                raise SystemExit(f"run.py: --twopoint: {e}")
+            self.mode = batch.mode
+        self.stats.update(flow, flag)
+
+    def finish(self, names, ctx):
+        """<save>/twopoint.npz (TwoPointStats.save) and <save>/twopoint.json: the parameters, the validation the flows went through and
+        TwoPointResult.summary(); one line with the four integral scales."""
+        if self.stats is None:
+            return
+        extra = {} if self.mode is None else {"validation": self.mode}
+        self.stats.save(self.file, **extra)
+        summary = self.stats.result().summary()
+        write_json(self.json_file, json_strict({"max_sep": self.max_sep, "step": self.step, "mean": self.mean, "validation": self.mode,
+                                                "summary": summary}))
+        scales = ", ".join(f"{key} {summary[key]['integral_scale']:.2f}{'+' if summary[key]['truncated'] else ''}"
+                           for key in ("uu_x", "uu_y", "vv_x", "vv_y"))
+        print(f"Two-point statistics of {self.stats.count} flows: integral scales in pixels {scales} ('+': the correlation did not reach zero)")
 
 
 def truth_files(ds, truth_dir, levels=False):
@@ -801,6 +853,9 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
                                layout.sibling("validation.json")))
     if args.stats:
         stages.append(Stats(layout.sibling("stats.npz")))
+    if args.twopoint is not None:
+        stages.append(TwoPoint(args.twopoint, args.twopoint_step or 1, args.twopoint_mean, layout.sibling("twopoint.npz"),
+                               layout.sibling("twopoint.json")))
     if args.truth is not None:
         lo, hi = shard_bounds(len(truth_paths), rank, world)
         stages.append(Truth(net, truth_paths[lo:hi], args.truth_levels, layout.sibling("errors.json"), layout.sibling("error_maps.npz"),
@@ -960,7 +1015,8 @@ def args_lines(args) -> List[str]:
             if not ((args.validate is None and k.startswith("validate")) or (not prep and k in PREP_FLAGS) or
                     (args.truth is None and k in TRUTH_FLAGS) or (not pictures and k in PICTURE_FLAGS) or
                     (args.quality is None and k in QUALITY_FLAGS) or (args.vortex is None and k in VORTEX_FLAGS) or
-                    (args.pod is None and k in POD_FLAGS) or (args.ftle is None and k in FTLE_FLAGS))]
+                    (args.pod is None and k in POD_FLAGS) or (args.ftle is None and k in FTLE_FLAGS) or
+                    (args.twopoint is None and k in TWOPOINT_FLAGS))]
 
 
 def load_weights(args) -> Tuple[dict, str]:
@@ -989,6 +1045,14 @@ def main(argv: Optional[List[str]] = None) -> int:
         refuse_mods(args, "--stats is")
         refuse_sharded("--stats", "run.py has no process group to merge the statistics; the sharded path for statistics is "
                                   "pivlfn.sequence.run_sequence")
+    if (args.twopoint_step is not None or args.twopoint_mean is not None) and args.twopoint is None:
+        raise SystemExit("run.py: --twopoint-step and --twopoint-mean need --twopoint")
+    if args.twopoint is not None:
+        refuse_mods(args, "--twopoint is")
+        refuse_sharded("--twopoint", "run.py has no process group to merge the sums of the ranks")
+        checked("--twopoint: ", check_twopoint, args.twopoint, 1 if args.twopoint_step is None else args.twopoint_step)
+        if args.twopoint_mean is not None and not os.path.isfile(args.twopoint_mean):
+            raise SystemExit(f"run.py: --twopoint-mean '{args.twopoint_mean}' is not a file")
     if args.pod_cell is not None and args.pod is None:
         raise SystemExit("run.py: --pod-cell needs --pod")
     if args.pod is not None:

@@ -2,6 +2,7 @@
 """A/B micro-benchmarks of single kernels at the shapes of the 1024x1024 PIV forward (one process, interleaved rounds).
 
   python tools/bench_ops.py warp_corr [--batch 1] [--variants 0,8,9]   (0 shipped policy, 8 v7, 9 v6)
+  python tools/bench_ops.py twopoint                                  (pivlfn_twopoint_accumulate against its HBM and fp64 bounds)
 Times N back-to-back launches between two events on the current stream (so each figure includes one ~1.5 us
 kernel boundary) and checks that all variants agree.
 """
@@ -387,9 +388,39 @@ def bench_evaluate(args):
               f"{100 * bound / tmed:5.1f} % of the time", flush=True)
 
 
+FP64_VECTOR_FLOP_PER_S = 78.6e12      # half the MI355X's fp32 vector peak of 157.3 TFLOP/s, an fma counted as two operations
+
+
+def bench_twopoint(args):
+    """pivlfn_twopoint_accumulate (csrc/twopoint.hip) at 8 x --size squared, R = 64, step 1, with and without a mask, on the production
+    library.  Beside the median time per frame two bounds: the bytes of the frame (and its mask) read once at the HBM peak, and the
+    arithmetic at the fp64 vector peak -- 2 * 65 * 15 * H * W additions of the trees plus as many products and differences, counted
+    as the contract counts them (the contract forbids fma, so a kernel can reach half that peak at the most)."""
+    from pivlfn import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream(dev).cuda_stream
+    B, S, R = 8, args.size, 64
+    g = torch.Generator().manual_seed(2)
+    flow = torch.randn(B, 2, S, S, generator=g).to(dev)
+    mask = (torch.rand(B, S, S, generator=g) < 0.05).to(torch.uint8).to(dev)
+    acc = torch.zeros(2, R + 1, 15, S, dtype=torch.float64, device=dev)
+    flops = 2 * (2 * (R + 1) * 15 * S * S)
+    for name, m in (("no mask", None), ("mask", mask)):
+        def fn(m=m):
+            _lib.check(lib.pivlfn_twopoint_accumulate(flow.data_ptr(), m.data_ptr() if m is not None else None, None, acc.data_ptr(), B, S, S,
+                                                      R, 1, st), "twopoint_accumulate")
+        tmin, tmed = time_it(fn, n=5, rounds=7)
+        hbm = (8 + (1 if m is not None else 0)) * S * S / HBM_BYTES_PER_S * 1e6
+        alu = flops / FP64_VECTOR_FLOP_PER_S * 1e6
+        print(f"twopoint_accumulate {name:7s} B={B} {S}x{S} R={R}: min {tmin:9.1f} us  med {tmed:9.1f} us  {tmed / B:8.1f} us/frame  "
+              f"HBM bound {hbm:5.2f} us/frame = {100 * hbm * B / tmed:5.2f} %  fp64 bound {alu:6.1f} us/frame = {100 * alu * B / tmed:5.2f} % of the time",
+              flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate"])
+    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate", "twopoint"])
     ap.add_argument("--once", action="store_true", help="preproc: one launch per shape, for a kernel trace")
     ap.add_argument("--filter", default="")
     ap.add_argument("--tune3", type=int, default=0, help="ablation mask of the fp16 conv kernel (pivlfn_tune(3, mask))")
@@ -403,4 +434,4 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=8, help="interleaved timing rounds per variant (warp_corr)")
     a = ap.parse_args()
     {"conv_stamps": bench_conv_stamps, "warp_corr": bench_warp_corr, "wc_ablate": bench_wc_ablate, "conv": bench_conv, "head": bench_head,
-     "preproc": bench_preproc, "evaluate": bench_evaluate}[a.what](a)
+     "preproc": bench_preproc, "evaluate": bench_evaluate, "twopoint": bench_twopoint}[a.what](a)
