@@ -572,6 +572,29 @@ int pivlfn_snapshot_project(const float *X, int n, long P, long ldx, const doubl
 int pivlfn_twopoint_accumulate(const float *flow, const unsigned char *mask, const double *mean, double *acc, int B, int H, int W,
                                int max_sep, int step, void *stream);
 
+/* ---- temporal spectra of a flow SEQUENCE: one segment of Welch's method.  Every vector's L samples of u and v are projected on K pairs of
+ * basis rows (the caller's windowed, detrended cosines and sines) and the power and cross-spectrum terms are added to running sums.
+ * Added without an ABI bump (additive).
+ * X: a ring of exactly L rows, one snapshot per row, row stride ldx >= 2N floats; a row is [2,N] fp32, the plane of u then the plane of
+ * v (the row layout of pivlfn_snapshot_gram); nothing past column 2N is read.  Sample t = 0..L-1 of the segment is row (first + t) % L.
+ * basis: [K,2,L] fp64, C_k[t] = basis[k][0][t], S_k[t] = basis[k][1][t]; the kernel gives them no meaning.  acc: [K,4,N] fp64 and
+ * count: [N] int32, both read and written once per call.  One launch, only on `stream`; no allocation, no workspace, no host
+ * synchronisation, no atomics; can be captured into a graph.  Nothing about one vector reaches another, and no value depends on the
+ * launch geometry.
+ * Arithmetic contract, all fp64, every operation rounded on its own (no fma; (double) of a float is exact):
+ *   validity:     vector p takes part iff all 2L of its values satisfy |x| <= 1e9f (the rule of pivlfn_vortex_gamma: NaN compares
+ *                 false; the 1e10 of pivlfn_flow_decimate's empty cell and of a masked flow is invalid by itself).  For a vector that
+ *                 does not take part acc[.][.][p] and count[p] keep their bits.
+ *   projections:  for each k, cu = the fold over t = 0..L-1 ascending of a = a + C_k[t] * (double)u[t][p] from a = +0.0;  su with S_k;
+ *                 cv and sv the same of v.
+ *   terms:        Suu = cu*cu + su*su;  Svv = cv*cv + sv*sv;  Co = cu*cv + su*sv;  Qd = cu*sv - su*cv  (with X = c - i s this is
+ *                 Im(U conj V): positive where v lags u).
+ *   accumulation: acc[k][j][p] = acc[k][j][p] + term_j, j = 0..3 in the order Suu, Svv, Co, Qd;  count[p] += 1.
+ * Errors (PIVLFN_ERR_ARG, before any launch): null X, basis, acc or count;  L outside 2..1024;  first outside 0..L-1;  K outside
+ * 1..513;  N < 1;  2N >= 2^31;  ldx < 2N.  acc is indexed with 64 bits (K*4*N passes 2^31 at full size). */
+int pivlfn_spectrum_accumulate(const float *X, int L, int first, long N, long ldx, const double *basis, int K, double *acc, int *count,
+                               void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

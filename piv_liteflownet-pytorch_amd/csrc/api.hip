@@ -244,6 +244,12 @@ int pivlfn_twopoint_accumulate(const float *flow, const unsigned char *mask, con
     return launch_twopoint_accumulate(flow, mask, mean, acc, B, H, W, max_sep, step, (hipStream_t)stream);
 }
 
+int pivlfn_spectrum_accumulate(const float *X, int L, int first, long N, long ldx, const double *basis, int K, double *acc, int *count,
+                               void *stream)
+{
+    return launch_spectrum_accumulate(X, L, first, N, ldx, basis, K, acc, count, (hipStream_t)stream);
+}
+
 int pivlfn_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, void *stream)
 {
     return launch_flow_maxrad(flow, mask, maxrad, B, H, W, (hipStream_t)stream);

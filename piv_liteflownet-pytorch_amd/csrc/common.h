@@ -320,6 +320,10 @@ int launch_snapshot_project(const float *X, int n, long P, long ldx, const doubl
 int launch_twopoint_accumulate(const float *flow, const unsigned char *mask, const double *mean, double *acc, int B, int H, int W,
                                int max_sep, int step, hipStream_t st);
 
+// ---- temporal spectra (spectrum.hip): one Welch segment of every vector's time series projected on K basis pairs, quadratic forms summed --
+int launch_spectrum_accumulate(const float *X, int L, int first, long N, long ldx, const double *basis, int K, double *acc, int *count,
+                               hipStream_t st);
+
 // ---- image pre-processing (preproc.hip): [n,H,W,3] uint8 frames -> background minimum [H,W,3], network input [n,3,H,W] fp32 --------
 int launch_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, hipStream_t st);
 int launch_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W, int k, int floor,

@@ -69,6 +69,8 @@ SIGNATURES = {
     "pivlfn_particles_render": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3
                                 + [ctypes.c_size_t, ctypes.c_void_p]),
     "pivlfn_twopoint_accumulate": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    "pivlfn_spectrum_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,
+                                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pivlfn_snapshot_gram_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_long]),
     "pivlfn_snapshot_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_size_t, ctypes.c_void_p]),

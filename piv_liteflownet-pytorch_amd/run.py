@@ -8,6 +8,7 @@
                 [--quality [R] [--quality-image]] [--vortex [R] [--vortex-spacing S] [--vortex-image]] [--pod K [--pod-cell C]]
                 [--ftle [SPACING] [--ftle-steps T] [--ftle-image [--ftle-max X]]]
                 [--twopoint [R] [--twopoint-step S] [--twopoint-mean FILE]]
+                [--spectrum [L] [--spectrum-overlap O] [--spectrum-cell C] [--spectrum-fps F] [--spectrum-image]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -50,6 +51,14 @@ Differences, all deliberate:
     0..R times `--twopoint-step S` pixels along x and along y; with --validate flag|mask the rejected vectors are left out) and
     writes <save>/twopoint.npz and <save>/twopoint.json with the integral scales, Taylor microscales and noise shares;
     `--twopoint-mean FILE` takes the per-pixel mean of a --stats run out first (flows that are not homogeneous along a row);
+  * `--spectrum [L]` estimates the temporal spectra of the flows of every input directory, which must be a time-resolved frame
+    sequence (not -p), on the device (pivlfn.spectrum.TemporalSpectrum, Welch's method: Hann-windowed segments of L pairs that
+    overlap by `--spectrum-overlap O` (default L/2), mean removed; `--spectrum-cell C` analyses the means over C x C blocks of
+    vectors; `--spectrum-fps F` the pairs per time unit, default 1: frequencies in cycles per pair) and writes <save>/spectrum.npz
+    (the raw sums and every parameter) and <save>/spectrum.json (the pooled peak frequency and its share, the resolution, the
+    segments and the pairs left over); with `--spectrum-image` <save>/spectrum_peak.png, the dominant-frequency map in gray on
+    0..the highest frequency kept, vectors without a segment red; with --validate flag|mask a rejected vector drops the segments
+    it sits in;
   * `--pod K` decomposes the flows of every input directory after it has been processed (pivlfn.pod.FlowPOD, snapshot POD: the
     Gram matrix of the flows in float64 on the device, its eigenvectors on the host): the first K modes, the mean, the coefficients
     and the energy fractions go to <save>/pod.npz, one line per mode is printed, and with --color the modes are drawn as
@@ -97,6 +106,8 @@ from pivlfn.pipeline import PairLoader, stream_pairs     # noqa: E402
 from pivlfn.pod import FlowPOD                           # noqa: E402
 from pivlfn.postpro import FlowStats                     # noqa: E402
 from pivlfn.preproc import FrameBackground, Preprocessor                 # noqa: E402
+from pivlfn.spectrum import TemporalSpectrum             # noqa: E402
+from pivlfn.spectrum import check_params as check_spectrum               # noqa: E402
 from pivlfn.twopoint import TwoPointStats                # noqa: E402
 from pivlfn.twopoint import check_params as check_twopoint               # noqa: E402
 from pivlfn.preproc import check_params as check_prep    # noqa: E402
@@ -223,7 +234,21 @@ parser.add_argument("--twopoint-step", type=int, default=None, metavar="S",
 parser.add_argument("--twopoint-mean", type=str, default=None, metavar="FILE",
                     help="with --twopoint: a stats.npz of an earlier --stats run over the same frames; its mean_u and mean_v are taken "
                          "out of every vector before the sums are formed")
+parser.add_argument("--spectrum", type=int, nargs="?", const=256, default=None, metavar="L",
+                    help="estimate the temporal spectra of the flows of each input directory, read as a frame sequence, on the device "
+                         "(pivlfn.spectrum.TemporalSpectrum, Welch's method; not a reference flag; not with -p or -b/-c, single process "
+                         "only): segments of L pairs (2..1024, default 256), the sums in <save>/spectrum.npz, the pooled peak frequency "
+                         "and its share in <save>/spectrum.json")
+parser.add_argument("--spectrum-overlap", type=int, default=None, metavar="O",
+                    help="with --spectrum: the pairs two consecutive segments share, 0..L-1 (default L/2)")
+parser.add_argument("--spectrum-cell", type=int, default=None, metavar="C",
+                    help="with --spectrum: analyse the means over C x C blocks of vectors (default 1: every vector)")
+parser.add_argument("--spectrum-fps", type=float, default=None, metavar="F",
+                    help="with --spectrum: the pairs per time unit (default 1: frequencies in cycles per pair)")
+parser.add_argument("--spectrum-image", action="store_true",
+                    help="with --spectrum: also <save>/spectrum_peak.png, the dominant-frequency map in gray, vectors without a segment in red")
 PREP_FLAGS = ("background", "minmax", "minmax_floor")
+SPECTRUM_FLAGS = ("spectrum", "spectrum_overlap", "spectrum_cell", "spectrum_fps", "spectrum_image")
 TWOPOINT_FLAGS = ("twopoint", "twopoint_step", "twopoint_mean")
 POD_FLAGS = ("pod", "pod_cell")
 QUALITY_FLAGS = ("quality", "quality_image")
@@ -231,7 +256,7 @@ QUALITY_BAD_RGB = (255, 0, 0)
 VORTEX_FLAGS = ("vortex", "vortex_spacing", "vortex_image")
 PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
 FTLE_FLAGS = ("ftle", "ftle_steps", "ftle_image", "ftle_max")
-VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + SPECTRUM_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -482,6 +507,59 @@ class TwoPoint(Stage):
         scales = ", ".join(f"{key} {summary[key]['integral_scale']:.2f}{'+' if summary[key]['truncated'] else ''}"
                            for key in ("uu_x", "uu_y", "vv_x", "vv_y"))
         print(f"Two-point statistics of {self.stats.count} flows: integral scales in pixels {scales} ('+': the correlation did not reach zero)")
+
+
+class Spectrum(Stage):
+    """Feeds every batch of flows to a TemporalSpectrum, created at the first batch's size and fed like Stats: after "flag" and "mask"
+    the raw flow with the flags as the mask (a rejected vector drops the segments it sits in), otherwise the written flow.  finish()
+    writes the sums, the summary and with `image` the dominant-frequency map."""
+
+    def __init__(self, segment, overlap, cell, fs, image, file, json_file, image_file):
+        self.segment, self.overlap, self.cell, self.fs, self.image = segment, overlap, cell, fs, image
+        self.file, self.json_file, self.image_file = file, json_file, image_file
+        self.spectrum, self.mode = None, None
+
+    def __call__(self, batch):
+        flow, flag = batch.masked()
+        if self.spectrum is None:
+            H, W = flow.size(2), flow.size(3)
+            need, free = TemporalSpectrum.device_bytes(H, W, self.segment, self.cell), torch.cuda.mem_get_info(flow.device)[0]
+            if need > free // 2:
+                raise SystemExit(f"run.py: --spectrum: the ring of {self.segment} flows of {H} x {W} and the sums take {need / 2**30:.1f} GiB, "
+                                 f"more than half of the {free / 2**30:.1f} GiB free on the device; analyse block means with --spectrum-cell C")
+            try:
+                self.spectrum = TemporalSpectrum(H, W, self.segment, self.overlap, cell=self.cell, fs=self.fs, device=flow.device)
+            except ValueError as e:
+                raise SystemExit(f"run.py: --spectrum: {e}")
+            self.mode = batch.mode
+        self.spectrum.update(flow, flag)
+
+    def finish(self, names, ctx):
+        """<save>/spectrum.npz (TemporalSpectrumResult.save), <save>/spectrum.json (the parameters, the validation the flows went
+        through and summary()), one line with the pooled peak, and with `image` <save>/spectrum_peak.png."""
+        if self.spectrum is None:
+            return
+        res = self.spectrum.result()
+        res.save(self.file, **({} if self.mode is None else {"validation": self.mode}))
+        summary = res.summary()
+        write_json(self.json_file, json_strict({"segment": self.segment, "overlap": res.overlap, "cell": self.cell, "fps": self.fs,
+                                                "window": res.window, "detrend": res.detrend, "validation": self.mode, "summary": summary}))
+        if summary["peak_frequency"] is None:
+            print(f"Temporal spectra of {res.frames} flows: no vector is known throughout a segment")
+        else:
+            print(f"Temporal spectra of {res.frames} flows in {summary['segments']} segments of {self.segment}: pooled peak at "
+                  f"{summary['peak_frequency']:.6g} cycles per {'pair' if self.fs == 1.0 else 'time unit'} (resolution "
+                  f"{summary['resolution']:.3g}), {100.0 * summary['peak_share']:.1f} % of the fluctuation energy")
+        if self.image:
+            f, _, _ = res.peak()
+            rgb = viz.scalar_to_color(torch.from_numpy(f[None]).to(self.spectrum.device), 0.0, float(res.freq[-1]), cmap="gray",
+                                      bad=QUALITY_BAD_RGB)
+            viz.write_png(self.image_file, rgb[0].cpu().numpy())
+
+
+def check_spectrum_pairs(pairs, segment, inputdir):
+    if pairs < segment:
+        raise SystemExit(f"run.py: --spectrum: '{inputdir}' has {pairs} pairs, fewer than the {segment} of one segment")
 
 
 def truth_files(ds, truth_dir, levels=False):
@@ -848,6 +926,9 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
     if args.ftle is not None:
         ftle_pairs = len(Run(root=inputdir, is_pair=args.is_pair, n_images=args.num_images, start_at=args.start))
         ftle_steps = check_ftle_pairs(ftle_pairs, args.ftle_steps, inputdir)
+    if args.spectrum is not None:
+        check_spectrum_pairs(len(Run(root=inputdir, is_pair=args.is_pair, n_images=args.num_images, start_at=args.start)), args.spectrum,
+                             inputdir)
     if args.validate is not None:
         stages.append(Validate(args.validate, args.validate_radius, args.validate_spacing, args.validate_eps, args.validate_thresh,
                                layout.sibling("validation.json")))
@@ -856,6 +937,10 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
     if args.twopoint is not None:
         stages.append(TwoPoint(args.twopoint, args.twopoint_step or 1, args.twopoint_mean, layout.sibling("twopoint.npz"),
                                layout.sibling("twopoint.json")))
+    if args.spectrum is not None:
+        stages.append(Spectrum(args.spectrum, args.spectrum_overlap, args.spectrum_cell or 1, 1.0 if args.spectrum_fps is None else args.spectrum_fps,
+                               args.spectrum_image, layout.sibling("spectrum.npz"), layout.sibling("spectrum.json"),
+                               layout.sibling("spectrum_peak.png")))
     if args.truth is not None:
         lo, hi = shard_bounds(len(truth_paths), rank, world)
         stages.append(Truth(net, truth_paths[lo:hi], args.truth_levels, layout.sibling("errors.json"), layout.sibling("error_maps.npz"),
@@ -1016,7 +1101,7 @@ def args_lines(args) -> List[str]:
                     (args.truth is None and k in TRUTH_FLAGS) or (not pictures and k in PICTURE_FLAGS) or
                     (args.quality is None and k in QUALITY_FLAGS) or (args.vortex is None and k in VORTEX_FLAGS) or
                     (args.pod is None and k in POD_FLAGS) or (args.ftle is None and k in FTLE_FLAGS) or
-                    (args.twopoint is None and k in TWOPOINT_FLAGS))]
+                    (args.twopoint is None and k in TWOPOINT_FLAGS) or (args.spectrum is None and k in SPECTRUM_FLAGS))]
 
 
 def load_weights(args) -> Tuple[dict, str]:
@@ -1053,6 +1138,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         checked("--twopoint: ", check_twopoint, args.twopoint, 1 if args.twopoint_step is None else args.twopoint_step)
         if args.twopoint_mean is not None and not os.path.isfile(args.twopoint_mean):
             raise SystemExit(f"run.py: --twopoint-mean '{args.twopoint_mean}' is not a file")
+    if _used(args, SPECTRUM_FLAGS[1:]) and args.spectrum is None:
+        raise SystemExit("run.py: --spectrum-overlap, --spectrum-cell, --spectrum-fps and --spectrum-image need --spectrum")
+    if args.spectrum is not None:
+        refuse_mods(args, "--spectrum is")
+        if args.is_pair:
+            raise SystemExit("run.py: --spectrum is not available with -p (the pairs of a pair folder are not a time series)")
+        refuse_sharded("--spectrum", "a spectrum follows the pairs of a directory in order, on one device")
+        checked("--spectrum: ", check_spectrum, args.spectrum, args.spectrum_overlap, "hann", "constant",
+                1 if args.spectrum_cell is None else args.spectrum_cell, 1.0 if args.spectrum_fps is None else args.spectrum_fps)
     if args.pod_cell is not None and args.pod is None:
         raise SystemExit("run.py: --pod-cell needs --pod")
     if args.pod is not None:

@@ -3,6 +3,7 @@
 
   python tools/bench_ops.py warp_corr [--batch 1] [--variants 0,8,9]   (0 shipped policy, 8 v7, 9 v6)
   python tools/bench_ops.py twopoint                                  (pivlfn_twopoint_accumulate against its HBM and fp64 bounds)
+  python tools/bench_ops.py spectrum                                  (pivlfn_spectrum_accumulate, and the same sums from snapshot_project + torch)
 Times N back-to-back launches between two events on the current stream (so each figure includes one ~1.5 us
 kernel boundary) and checks that all variants agree.
 """
@@ -418,9 +419,65 @@ def bench_twopoint(args):
               flush=True)
 
 
+def bench_spectrum(args):
+    """pivlfn_spectrum_accumulate (csrc/spectrum.hip): one segment call at L = 256 with all 129 frequencies of the Hann basis, at
+    N = --size squared and at N = 256 squared vectors, on the production library; and the same sums formed from
+    pivlfn_snapshot_project (the [L, 2K] basis as weights, 64 columns per call) plus torch for the squares and the accumulation.
+    Beside each median two bounds: the ring read once and acc read and written once at the HBM peak, and the contract's
+    4 K L N products and as many additions at the fp64 vector peak (the contract forbids fma, so half of it is the most a kernel
+    can reach).  The torch arm has no validity rule: it times the arithmetic alone."""
+    from pivlfn import _lib
+    from pivlfn.spectrum import basis
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream(dev).cuda_stream
+    L, K = 256, 129
+    b = torch.from_numpy(basis(L, "hann", "constant", K)).to(dev)
+    wt = b.reshape(2 * K, L).t().contiguous()                                 # [L, 2K]: column 2k is C_k, column 2k+1 is S_k
+    for S in (args.size, 256):
+        N = S * S
+        g = torch.Generator().manual_seed(3)
+        ring = torch.randn(L, 2 * N, generator=g).to(dev)
+        acc = torch.zeros(K, 4, N, dtype=torch.float64, device=dev)
+        count = torch.zeros(N, dtype=torch.int32, device=dev)
+        out = torch.empty(64, 2 * N, dtype=torch.float64, device=dev)
+
+        def fused():
+            _lib.check(lib.pivlfn_spectrum_accumulate(ring.data_ptr(), L, 0, N, 2 * N, b.data_ptr(), K, acc.data_ptr(), count.data_ptr(), st),
+                       "spectrum_accumulate")
+
+        def pieced():
+            for c0 in range(0, 2 * K, 64):
+                w = wt[:, c0:c0 + 64].contiguous()
+                n = w.size(1)
+                _lib.check(lib.pivlfn_snapshot_project(ring.data_ptr(), L, 2 * N, 2 * N, w.data_ptr(), n, out.data_ptr(), st), "snapshot_project")
+                cu, su, cv, sv = out[0:n:2, :N], out[1:n:2, :N], out[0:n:2, N:], out[1:n:2, N:]
+                a = acc[c0 // 2:c0 // 2 + n // 2]
+                a[:, 0] += cu * cu + su * su
+                a[:, 1] += cv * cv + sv * sv
+                a[:, 2] += cu * cv + su * sv
+                a[:, 3] += cu * sv - su * cv
+            count.add_(1)
+
+        fused()
+        one = acc.clone()
+        acc.zero_()
+        pieced()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(one.view(torch.int64), acc.view(torch.int64)))
+        hbm = (L * 2 * N * 4 + 2 * K * 4 * N * 8) / HBM_BYTES_PER_S * 1e6
+        alu = 8.0 * K * L * N / FP64_VECTOR_FLOP_PER_S * 1e6
+        for name, fn in (("spectrum_accumulate", fused), ("snapshot_project + torch", pieced)):
+            tmin, tmed = time_it(fn, n=5, rounds=7)
+            print(f"{name:24s} L={L} K={K} N={S}x{S}: min {tmin:10.1f} us  med {tmed:10.1f} us  HBM bound {hbm:8.1f} us = {100 * hbm / tmed:5.2f} %  "
+                  f"fp64 bound {alu:8.1f} us = {100 * alu / tmed:5.2f} % of the time", flush=True)
+        print(f"  the two arms give {'the same bits' if same else 'different bits'} from a zero acc at N={S}x{S}", flush=True)
+        del ring, acc, count, out, one
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate", "twopoint"])
+    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate", "twopoint", "spectrum"])
     ap.add_argument("--once", action="store_true", help="preproc: one launch per shape, for a kernel trace")
     ap.add_argument("--filter", default="")
     ap.add_argument("--tune3", type=int, default=0, help="ablation mask of the fp16 conv kernel (pivlfn_tune(3, mask))")
@@ -434,4 +491,4 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=8, help="interleaved timing rounds per variant (warp_corr)")
     a = ap.parse_args()
     {"conv_stamps": bench_conv_stamps, "warp_corr": bench_warp_corr, "wc_ablate": bench_wc_ablate, "conv": bench_conv, "head": bench_head,
-     "preproc": bench_preproc, "evaluate": bench_evaluate, "twopoint": bench_twopoint}[a.what](a)
+     "preproc": bench_preproc, "evaluate": bench_evaluate, "twopoint": bench_twopoint, "spectrum": bench_spectrum}[a.what](a)
