@@ -595,6 +595,86 @@ int pivlfn_twopoint_accumulate(const float *flow, const unsigned char *mask, con
 int pivlfn_spectrum_accumulate(const float *X, int L, int first, long N, long ldx, const double *basis, int K, double *acc, int *count,
                                void *stream);
 
+/* ---- pressure from a time-resolved planar flow SEQUENCE: the pressure gradient of the in-plane incompressible momentum equation in
+ * lattice units (px, frame),  grad p* = g = -(du/dt + u du/dx + v du/dy) + nu* lap u,  from three consecutive flows, and its least-squares
+ * integration over the valid nodes: the graph-Laplacian Poisson problem with the natural Neumann boundary on any mask shape, solved by
+ * Jacobi-preconditioned conjugate gradients.  Units (p = rho (calib/dt)^2 p*, nu* = nu dt/calib^2) are the caller's.  Added without an ABI
+ * bump (additive).
+ * Every entry point launches only on `stream`, allocates nothing, never synchronises the host, uses no atomics and can be captured into a
+ * graph as one linear chain of kernels.  There is no grid-wide barrier, no persistent kernel, no spin wait and no cooperative launch: a
+ * seam between two phases is a kernel boundary, and every loop of a kernel has a bound known at launch.
+ * All arithmetic is fp64, every operation rounded on its own (no fma; (double) of a float is exact; divisions are IEEE).  A node is
+ * (j, i) = (row, column) of an h x w lattice, node index j*w + i; "left / right" are columns i-1 / i+1, "up / down" rows j-1 / j+1.
+ *
+ * T(.), the sum over a frame: the root of the binary tree t[i] = t[2i] + t[2i+1] whose leaves are the N = h*w per-node values in
+ *   row-major order, padded with +0.0 to the next power of two >= N: the tree of pivlfn_twopoint_accumulate's row sum, taken over the
+ *   whole lattice of one frame.  No value depends on how workgroups cut the tree.
+ *
+ * pivlfn_pressure_gradient -- flows [B,2,h,w] fp32, B >= 3 consecutive flows;  s: lattice spacing, px per node;  nu: nu*;  g [B-2,2,h,w]
+ *   fp64 and valid [B-2,h,w] bytes, both written completely.  Output frame f uses flows f, f+1 and f+2.  One launch.
+ *   validity: node (j,i) of frame f is valid iff 1 <= j <= h-2 and 1 <= i <= w-2 and both components of all seven vectors -- the centre and
+ *     its four neighbours in flow f+1, the centre in flows f and f+2 -- satisfy |x| <= 1e9f (the rule of pivlfn_vortex_gamma: NaN is
+ *     invalid, and so is the 1e10 of an unknown vector).
+ *   per component a in {u, v}, c the centre, l, r, u, d the neighbours in flow f+1, prev / next the centre in flows f / f+2:
+ *     at  = (a_next - a_prev) * 0.5
+ *     ax  = (a_r - a_l) / (2.0*s);   ay = (a_d - a_u) / (2.0*s)
+ *     lap = ((((a_l + a_r) + a_u) + a_d) - 4.0*a_c) / (s*s)
+ *     g_a = (-(at + (u_c*ax + v_c*ay))) + nu*lap
+ *   An invalid node gets g = +0.0 in both components and valid = 0; its products are not formed.
+ *
+ * pivlfn_pressure_setup -- g [F,2,h,w], valid [F,h,w] (nonzero = valid), s as above;  fills the workspace: 8-byte aligned, at least
+ *   pivlfn_pressure_workspace_bytes(F,h,w) bytes (0 for arguments out of range), needs no initial contents.  One launch.
+ *   The edge between 4-neighbours a and b is active iff both are valid;  deg(a) = the number of active edges at a.
+ *   For the edge a -> right neighbour b:  e = (0.5*(gx(a) + gx(b))) * s;  for a -> lower neighbour the same with gy.
+ *   b(a) = ((L + R) + U) + D  with  L = +e(left -> a), R = -e(a -> right), U = +e(up -> a), D = -e(a -> down);  an inactive edge is +0.0.
+ *   Initial state: x = +0.0, r = b, z = r/deg (+0.0 where deg = 0), d = z, rho = T(r*z), bb = T(b*b), rr = T(r*r), iterations = 0,
+ *   state = PIVLFN_PRESSURE_RUNNING.
+ *   pivlfn_pressure_workspace_offset(F,h,w,what) gives the byte offset of three arrays a caller may read (0 for arguments out of range):
+ *   PIVLFN_PRESSURE_WS_B: b [F,h,w] fp64;  PIVLFN_PRESSURE_WS_X: x [F,h,w] fp64;  PIVLFN_PRESSURE_WS_ADJ: [F,h,w] bytes, bit 0 / 1 / 2 / 3 =
+ *   the edge to the left / right / upper / lower neighbour is active (deg = the number of these bits), bit 4 = the node is valid.  The
+ *   rest of the layout is the library's.
+ *
+ * pivlfn_pressure_cg -- enqueues `iters` iterations for all F frames in the same launches, two launches per iteration (the frame is a
+ *   grid dimension).  Every frame has its own scalars: a frame's bits are the same alone, in any batch, and however `iters` is cut into
+ *   calls.  One iteration of one frame:
+ *     1. if state != RUNNING, do nothing.
+ *     2. if rr <= (tol*tol)*bb and bb > 0, set state = CONVERGED and change nothing else.  (With bb = 0, that is b = 0, rule 4 decides.)
+ *     3. q(a) = deg(a)*d(a) - (((d_l + d_r) + d_u) + d_d), an inactive edge contributing +0.0;  sigma = T(d*q).
+ *     4. if !(sigma > 0), set state = BREAKDOWN and change nothing else (b = 0, where x = 0 is the solution, ends here; so does a NaN).
+ *     5. alpha = rho/sigma;  x = x + alpha*d;  r = r - alpha*q;  z = r/deg (+0.0 where deg = 0);  rho' = T(r*z);  rr = T(r*r);
+ *        beta = rho'/rho;  d = z + beta*d;  rho = rho';  iterations += 1.
+ *   All nodes take part in every formula, the invalid ones with deg = 0 and b = +0.0.  Every workgroup derives the frozen-or-running
+ *   decision from the same reduced scalars; no flag is written by one workgroup and read by another within a launch.
+ *   Because z = r/deg, x has zero DEGREE-WEIGHTED mean on every connected component of the valid nodes, exactly in exact arithmetic and
+ *   to rounding here:  sum over the component of deg*x = 0.  The plain mean is not zero, and the levels of disconnected components are
+ *   unrelated; re-reference p as the application needs.
+ *   iters == 0 succeeds and launches nothing.
+ *
+ * pivlfn_pressure_read -- p [F,h,w] fp64: x where deg > 0, a quiet NaN elsewhere;  flag [F,h,w] bytes: 0 = ok, PIVLFN_PRESSURE_INVALID,
+ *   PIVLFN_PRESSURE_ISOLATED (valid with deg = 0);  status [F,4] fp64: state, iterations, rr, bb of each frame.  One launch.  The workspace
+ *   is not changed: iterating can go on afterwards.
+ *
+ * Errors (PIVLFN_ERR_ARG, before any launch, the message names the problem): a null pointer;  B < 3;  F < 1;  h or w < 1;  F*h*w >= 2^31
+ * (F = B-2 for the gradient);  s or tol not finite and positive;  nu not finite;  iters < 0;  a workspace that is misaligned or smaller
+ * than the query;  gradient: g or valid overlapping flows or each other;  setup: the workspace overlapping g or valid;  read: p, flag or
+ * status overlapping the workspace or each other. */
+#define PIVLFN_PRESSURE_RUNNING   1
+#define PIVLFN_PRESSURE_CONVERGED 2
+#define PIVLFN_PRESSURE_BREAKDOWN 3
+#define PIVLFN_PRESSURE_INVALID   1
+#define PIVLFN_PRESSURE_ISOLATED  2
+#define PIVLFN_PRESSURE_WS_B      0
+#define PIVLFN_PRESSURE_WS_X      1
+#define PIVLFN_PRESSURE_WS_ADJ    2
+int pivlfn_pressure_gradient(const float *flows, int B, int h, int w, double s, double nu, double *g, unsigned char *valid, void *stream);
+size_t pivlfn_pressure_workspace_bytes(int F, int h, int w);
+size_t pivlfn_pressure_workspace_offset(int F, int h, int w, int what);
+int pivlfn_pressure_setup(const double *g, const unsigned char *valid, int F, int h, int w, double s, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int pivlfn_pressure_cg(void *workspace, size_t workspace_bytes, int F, int h, int w, double tol, int iters, void *stream);
+int pivlfn_pressure_read(const void *workspace, size_t workspace_bytes, int F, int h, int w, double *p, unsigned char *flag,
+                         double *status, void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

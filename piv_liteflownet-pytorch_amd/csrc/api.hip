@@ -250,6 +250,32 @@ int pivlfn_spectrum_accumulate(const float *X, int L, int first, long N, long ld
     return launch_spectrum_accumulate(X, L, first, N, ldx, basis, K, acc, count, (hipStream_t)stream);
 }
 
+int pivlfn_pressure_gradient(const float *flows, int B, int h, int w, double s, double nu, double *g, unsigned char *valid, void *stream)
+{
+    return launch_pressure_gradient(flows, B, h, w, s, nu, g, valid, (hipStream_t)stream);
+}
+
+size_t pivlfn_pressure_workspace_bytes(int F, int h, int w) { return pressure_workspace_bytes(F, h, w); }
+
+size_t pivlfn_pressure_workspace_offset(int F, int h, int w, int what) { return pressure_workspace_offset(F, h, w, what); }
+
+int pivlfn_pressure_setup(const double *g, const unsigned char *valid, int F, int h, int w, double s, void *workspace,
+                          size_t workspace_bytes, void *stream)
+{
+    return launch_pressure_setup(g, valid, F, h, w, s, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int pivlfn_pressure_cg(void *workspace, size_t workspace_bytes, int F, int h, int w, double tol, int iters, void *stream)
+{
+    return launch_pressure_cg(workspace, workspace_bytes, F, h, w, tol, iters, (hipStream_t)stream);
+}
+
+int pivlfn_pressure_read(const void *workspace, size_t workspace_bytes, int F, int h, int w, double *p, unsigned char *flag,
+                         double *status, void *stream)
+{
+    return launch_pressure_read(workspace, workspace_bytes, F, h, w, p, flag, status, (hipStream_t)stream);
+}
+
 int pivlfn_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, void *stream)
 {
     return launch_flow_maxrad(flow, mask, maxrad, B, H, W, (hipStream_t)stream);

@@ -324,6 +324,14 @@ int launch_twopoint_accumulate(const float *flow, const unsigned char *mask, con
 int launch_spectrum_accumulate(const float *X, int L, int first, long N, long ldx, const double *basis, int K, double *acc, int *count,
                                hipStream_t st);
 
+// ---- pressure from PIV (pressure.hip): material acceleration of three consecutive flows, least-squares integration by Jacobi-CG ----------
+int launch_pressure_gradient(const float *flows, int B, int h, int w, double s, double nu, double *g, unsigned char *valid, hipStream_t st);
+size_t pressure_workspace_bytes(int F, int h, int w);
+size_t pressure_workspace_offset(int F, int h, int w, int what);
+int launch_pressure_setup(const double *g, const unsigned char *valid, int F, int h, int w, double s, void *ws, size_t ws_bytes, hipStream_t st);
+int launch_pressure_cg(void *ws, size_t ws_bytes, int F, int h, int w, double tol, int iters, hipStream_t st);
+int launch_pressure_read(const void *ws, size_t ws_bytes, int F, int h, int w, double *p, unsigned char *flag, double *status, hipStream_t st);
+
 // ---- image pre-processing (preproc.hip): [n,H,W,3] uint8 frames -> background minimum [H,W,3], network input [n,3,H,W] fp32 --------
 int launch_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, hipStream_t st);
 int launch_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W, int k, int floor,

@@ -1,0 +1,544 @@
+// Pressure from time-resolved planar PIV (gfx950): the pressure gradient g of the momentum equation from three consecutive flows
+// (pressure_gradient_kernel), its least-squares integration over the valid nodes -- the graph-Laplacian Poisson problem with the natural
+// Neumann boundary -- by Jacobi-preconditioned conjugate gradients (pressure_setup_kernel, two kernels per iteration), and the read-out.
+// Arithmetic contract: include/pivlfn.h.
+//
+// No grid-wide barrier, no persistent kernel, no flag that one workgroup writes and another reads in the same launch: the seam between two
+// phases of an iteration is a kernel boundary, and every scalar of the recurrence (rho, sigma, rr, alpha, beta, the state) is derived by
+// EVERY workgroup of a frame from the same block partials and the same record of the launch before, so all of them take the same
+// frozen-or-running decision.  The record of a frame ping-pongs between two copies (recA is read by the first kernel of an iteration, which
+// writes recB; the second reads recB and writes recA; one thread of the frame's first workgroup writes), and so does the search direction
+// d, whose new value a neighbouring workgroup needs while the old one is still being read.
+//
+// The tree of the contract over the N = h*w leaves of a frame: a thread owns four consecutive leaves (levels 0, 1), the six levels above
+// cross the lanes of a wave (partner lane ^ 1 .. ^ 32; an addition commutes, so both lanes hold the node), two more cross the four waves
+// in LDS: a chunk of 1024 leaves.  A workgroup walks `chunks` consecutive chunks (1 up to 2^21 nodes, a power of two beyond) and combines
+// their roots with a binary counter, which is the tree's order again, into ONE partial; a frame has at most 2048 partials, and each
+// workgroup of the next launch finishes the tree over them in LDS by itself.  Padding is +0.0 and x + (+0.0) = x for every x but -0.0;
+// the leaves r*z and r*r are never negative zero, and of sigma = T(d*q) only `sigma > 0` and rho/sigma for such a sigma are used, so
+// levels that add padding above a root change no bit of any result.
+//
+// What an iteration moves per node: the first kernel reads z and d (the four neighbours of each from cache) and the adjacency byte and
+// writes d and q; the second reads d, q, x, r and the byte and writes x, r, z: 11 doubles and 2 bytes, 90 bytes.
+//
+// Step 5 of the contract's iteration is split over the boundary: the second kernel of iteration k leaves x, r, z and the partials of
+// r*z and r*r (phase PENDING); beta, d, rho = rho' and the iteration count are completed by the first kernel of iteration k + 1, which
+// may belong to a later call, or -- the count and rr -- by the read-out.  d is no output, so where the stopping rule fires first the
+// last d is never formed.
+#include <cmath>
+#include "common.h"
+
+namespace pivlfn {
+
+constexpr int PR_THREADS = 256, PR_OWN = 4, PR_CHUNK = PR_THREADS * PR_OWN, PR_MAX_PART = 2048;
+constexpr int PR_FRESH = 0, PR_PENDING = 1, PR_MID = 2;    // what the record and the partials hold: setup's, a half-finished step 5, d*q
+
+struct PrRec {                                 // 64 bytes per frame
+    double rho, rr, bb;
+    int state, iters, phase, dsel;             // dsel: which of the two d buffers holds the current direction
+    double unused[3];
+};
+
+// field by field, so that a record lives in registers and not in a scratch copy
+__device__ __forceinline__ PrRec pr_load(const PrRec *src)
+{
+    PrRec r;
+    r.rho = src->rho, r.rr = src->rr, r.bb = src->bb;
+    r.state = src->state, r.iters = src->iters, r.phase = src->phase, r.dsel = src->dsel;
+    r.unused[0] = r.unused[1] = r.unused[2] = 0.0;
+    return r;
+}
+
+__device__ __forceinline__ void pr_store(PrRec *dst, const PrRec &r)
+{
+    dst->rho = r.rho, dst->rr = r.rr, dst->bb = r.bb;
+    dst->state = r.state, dst->iters = r.iters, dst->phase = r.phase, dst->dsel = r.dsel;
+}
+
+struct PrWs {
+    PrRec *recA, *recB;                        // [F]
+    double *prz, *prr, *pdq;                   // [F][NB] block partials of r*z, r*r, d*q
+    double *b, *x, *r, *z, *d[2], *q;          // [F][N]
+    unsigned char *adj;                        // [F][N]: bit 0 left, 1 right, 2 up, 3 down edge active; bit 4 the node is valid
+    unsigned N;
+    int w, chunks, NB;                         // chunks per workgroup, partials per frame
+};
+
+struct PrLayout {
+    PrWs ws;
+    size_t off_b, off_x, off_adj, bytes;
+};
+
+// N >= 1.  Offsets are multiples of 8 from an 8-byte aligned base; adj comes last.
+static PrLayout pr_layout(void *base, int F, int h, int w)
+{
+    PrLayout L;
+    const size_t N = (size_t)h * w;
+    size_t P2 = 1;
+    while (P2 < N) P2 <<= 1;
+    const size_t chunks = P2 > (size_t)PR_CHUNK * PR_MAX_PART ? P2 / ((size_t)PR_CHUNK * PR_MAX_PART) : 1;
+    const size_t tile = chunks * PR_CHUNK, NB = (N + tile - 1) / tile;
+    unsigned char *p = static_cast<unsigned char *>(base);
+    size_t at = 0;
+    auto take = [&](size_t bytes) { size_t o = at; at += (bytes + 7) & ~(size_t)7; return o; };
+    L.ws.recA = reinterpret_cast<PrRec *>(p + take(sizeof(PrRec) * F));
+    L.ws.recB = reinterpret_cast<PrRec *>(p + take(sizeof(PrRec) * F));
+    L.ws.prz = reinterpret_cast<double *>(p + take(8 * NB * F));
+    L.ws.prr = reinterpret_cast<double *>(p + take(8 * NB * F));
+    L.ws.pdq = reinterpret_cast<double *>(p + take(8 * NB * F));
+    L.off_b = take(8 * N * F);
+    L.ws.b = reinterpret_cast<double *>(p + L.off_b);
+    L.off_x = take(8 * N * F);
+    L.ws.x = reinterpret_cast<double *>(p + L.off_x);
+    L.ws.r = reinterpret_cast<double *>(p + take(8 * N * F));
+    L.ws.z = reinterpret_cast<double *>(p + take(8 * N * F));
+    L.ws.d[0] = reinterpret_cast<double *>(p + take(8 * N * F));
+    L.ws.d[1] = reinterpret_cast<double *>(p + take(8 * N * F));
+    L.ws.q = reinterpret_cast<double *>(p + take(8 * N * F));
+    L.off_adj = take(N * F);
+    L.ws.adj = p + L.off_adj;
+    L.ws.N = (unsigned)N;
+    L.ws.w = w;
+    L.ws.chunks = (int)chunks;
+    L.ws.NB = (int)NB;
+    L.bytes = at;
+    return L;
+}
+
+static bool pr_shape_ok(int F, int h, int w) { return F >= 1 && h >= 1 && w >= 1 && (size_t)F * h * w < ((size_t)1 << 31); }
+
+size_t pressure_workspace_bytes(int F, int h, int w) { return pr_shape_ok(F, h, w) ? pr_layout(nullptr, F, h, w).bytes : 0; }
+
+size_t pressure_workspace_offset(int F, int h, int w, int what)
+{
+    if (!pr_shape_ok(F, h, w)) return 0;
+    const PrLayout L = pr_layout(nullptr, F, h, w);
+    return what == PIVLFN_PRESSURE_WS_B ? L.off_b : what == PIVLFN_PRESSURE_WS_X ? L.off_x : what == PIVLFN_PRESSURE_WS_ADJ ? L.off_adj : 0;
+}
+
+// ---- the tree ---------------------------------------------------------------------------------------------------------------------------
+// v[k]: the sum of a thread's four leaves, as (l0 + l1) + (l2 + l3).  Afterwards every thread holds the root of the workgroup's 1024
+// leaves.  Called by whole workgroups; sw is [K][4].
+template <int K>
+__device__ __forceinline__ void pr_chunk_root(double (&v)[K], double (*sw)[4])
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1)
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] = v[k] + __shfl_xor(v[k], m);
+    __syncthreads();                                                           // the last chunk's sums have been read
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) sw[k][wave] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = (sw[k][0] + sw[k][1]) + (sw[k][2] + sw[k][3]);
+}
+
+// The binary counter over the chunks of a workgroup: up[k] waits for its right sibling at level k above a chunk's root.
+// Written without a break so that every index is static and the counter stays in registers.
+struct PrCounter {
+    double up[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    __device__ __forceinline__ double add(double root, int c)
+    {
+#pragma clang fp contract(off)
+        bool carry = true;                                                     // still climbing: every lower bit of c was set
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {
+            const bool bit = (c >> k) & 1;
+            const double sum = up[k] + root;
+            up[k] = (carry && !bit) ? root : up[k];
+            root = (carry && bit) ? sum : root;
+            carry = carry && bit;
+        }
+        return root;                                                           // after the last of 2^n chunks: their root
+    }
+};
+
+// The roots of the trees over a frame's NB <= 2048 partials, K trees at once, in every thread: the partials are the leaves of one or two
+// chunks, reduced like the nodes' (the padding above a root of fewer than 1024 partials adds +0.0, which changes no result -- see the
+// head of the file).  sw is [K][4].
+template <int K>
+__device__ __forceinline__ void pr_finish(const double *const (&part)[K], int NB, double (*sw)[4], double (&out)[K])
+{
+#pragma clang fp contract(off)
+    for (int c = 0; c * PR_CHUNK < NB; ++c) {
+        const int base = c * PR_CHUNK + (int)threadIdx.x * PR_OWN;
+        double v[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            double l[PR_OWN];
+#pragma unroll
+            for (int j = 0; j < PR_OWN; ++j) l[j] = base + j < NB ? part[k][base + j] : 0.0;
+            v[k] = (l[0] + l[1]) + (l[2] + l[3]);
+        }
+        pr_chunk_root<K>(v, sw);
+#pragma unroll
+        for (int k = 0; k < K; ++k) out[k] = c ? out[k] + v[k] : v[k];
+    }
+}
+
+__device__ __forceinline__ double pr_deg(unsigned a) { return (double)__popc(a & 15u); }
+
+// ---- the gradient -----------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool pr_known(float a, float b) { return fabsf(a) <= 1e9f && fabsf(b) <= 1e9f; }      // NaN fails
+
+// one thread per node of an output frame; 32-bit node index over all frames (the host checks (B-2)*h*w < 2^31)
+__global__ __launch_bounds__(PR_THREADS) void pressure_gradient_kernel(const float *flows, int F, int h, int w, double s, double nu, double *g,
+                                                                       unsigned char *valid)
+{
+#pragma clang fp contract(off)
+    const unsigned N = (unsigned)h * (unsigned)w, total = (unsigned)F * N;
+    const unsigned t = blockIdx.x * (unsigned)PR_THREADS + threadIdx.x;
+    if (t >= total) return;
+    const unsigned f = t / N, i = t - f * N;
+    const int y = (int)(i / (unsigned)w), x = (int)(i - (unsigned)y * (unsigned)w);
+    const float *prev = flows + (size_t)f * 2 * N, *cur = prev + 2 * (size_t)N, *next = cur + 2 * (size_t)N;
+    double gx = 0.0, gy = 0.0;
+    bool ok = y >= 1 && y <= h - 2 && x >= 1 && x <= w - 2;
+    if (ok)
+        ok = pr_known(cur[i], cur[N + i]) && pr_known(cur[i - 1], cur[N + i - 1]) && pr_known(cur[i + 1], cur[N + i + 1]) &&
+             pr_known(cur[i - w], cur[N + i - w]) && pr_known(cur[i + w], cur[N + i + w]) && pr_known(prev[i], prev[N + i]) &&
+             pr_known(next[i], next[N + i]);
+    if (ok) {
+        const double uc = (double)cur[i], vc = (double)cur[N + i];
+        double out[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const float *cp = cur + (size_t)a * N;
+            const double ac = (double)cp[i], al = (double)cp[i - 1], ar = (double)cp[i + 1], au = (double)cp[i - w], ad = (double)cp[i + w];
+            const double at = ((double)next[(size_t)a * N + i] - (double)prev[(size_t)a * N + i]) * 0.5;
+            const double ax = (ar - al) / (2.0 * s), ay = (ad - au) / (2.0 * s);
+            const double lap = ((((al + ar) + au) + ad) - 4.0 * ac) / (s * s);
+            out[a] = (-(at + (uc * ax + vc * ay))) + nu * lap;
+        }
+        gx = out[0];
+        gy = out[1];
+    }
+    g[(size_t)f * 2 * N + i] = gx;
+    g[(size_t)f * 2 * N + N + i] = gy;
+    valid[t] = ok ? 1 : 0;
+}
+
+// ---- setup ------------------------------------------------------------------------------------------------------------------------------
+// blockIdx.x = frame * NB + the workgroup's tile of the frame
+__global__ __launch_bounds__(PR_THREADS) void pressure_setup_kernel(const double *g, const unsigned char *valid, double s, const PrWs ws)
+{
+#pragma clang fp contract(off)
+    __shared__ double sw[2][4];
+    const unsigned N = ws.N, f = blockIdx.x / (unsigned)ws.NB, blk = blockIdx.x - f * (unsigned)ws.NB;
+    const int tid = threadIdx.x, w = ws.w;
+    const size_t fo = (size_t)f * N;
+    const double *gx = g + 2 * fo, *gy = gx + N;
+    const unsigned char *va = valid + fo;
+    PrCounter crz, crr;
+    double root_rz = 0.0, root_rr = 0.0;
+    for (int c = 0; c < ws.chunks; ++c) {
+        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
+        double lrz[PR_OWN], lrr[PR_OWN];
+#pragma unroll
+        for (int j = 0; j < PR_OWN; ++j) {
+            lrz[j] = lrr[j] = 0.0;
+            if (base + j < N) {
+                const unsigned i = (unsigned)(base + j);
+                const unsigned col = i % (unsigned)w;
+                const bool me = va[i] != 0;
+                const bool eL = me && col > 0 && va[i - 1] != 0, eR = me && col + 1 < (unsigned)w && va[i + 1] != 0;
+                const bool eU = me && i >= (unsigned)w && va[i - w] != 0, eD = me && i + (unsigned)w < N && va[i + w] != 0;
+                const unsigned a = (eL ? 1u : 0u) | (eR ? 2u : 0u) | (eU ? 4u : 0u) | (eD ? 8u : 0u);
+                const double L = eL ? (0.5 * (gx[i - 1] + gx[i])) * s : 0.0;
+                const double R = eR ? -((0.5 * (gx[i] + gx[i + 1])) * s) : 0.0;
+                const double U = eU ? (0.5 * (gy[i - w] + gy[i])) * s : 0.0;
+                const double D = eD ? -((0.5 * (gy[i] + gy[i + w])) * s) : 0.0;
+                const double b = ((L + R) + U) + D;
+                const double z = a ? b / pr_deg(a) : 0.0;
+                ws.adj[fo + i] = (unsigned char)(a | (me ? 16u : 0u));
+                ws.b[fo + i] = b;
+                ws.x[fo + i] = 0.0;
+                ws.r[fo + i] = b;
+                ws.z[fo + i] = z;
+                lrz[j] = b * z;
+                lrr[j] = b * b;
+            }
+        }
+        double v[2] = {(lrz[0] + lrz[1]) + (lrz[2] + lrz[3]), (lrr[0] + lrr[1]) + (lrr[2] + lrr[3])};
+        pr_chunk_root<2>(v, sw);
+        root_rz = crz.add(v[0], c);
+        root_rr = crr.add(v[1], c);
+    }
+    if (tid == 0) {
+        ws.prz[(size_t)f * ws.NB + blk] = root_rz;
+        ws.prr[(size_t)f * ws.NB + blk] = root_rr;
+        if (blk == 0) {
+            PrRec rec = {0.0, 0.0, 0.0, PIVLFN_PRESSURE_RUNNING, 0, PR_FRESH, 0, {0.0, 0.0, 0.0}};
+            pr_store(ws.recA + f, rec);
+        }
+    }
+}
+
+// ---- one iteration: two kernels -----------------------------------------------------------------------------------------------------------
+// First kernel: finish rho' and rr, apply the stopping rule, d = z + beta d, q = A d, the partials of d*q.  recA -> recB.
+__global__ __launch_bounds__(PR_THREADS) void pressure_cg_dq_kernel(const PrWs ws, double tol)
+{
+#pragma clang fp contract(off)
+    __shared__ double sw[2][4];
+    const unsigned N = ws.N, f = blockIdx.x / (unsigned)ws.NB, blk = blockIdx.x - f * (unsigned)ws.NB;
+    const int tid = threadIdx.x, w = ws.w;
+    const PrRec in = pr_load(ws.recA + f);
+    const bool writer = blk == 0 && tid == 0;
+    if (in.state != PIVLFN_PRESSURE_RUNNING) {                                 // frozen: the record passes through, nothing else moves
+        if (writer) pr_store(ws.recB + f, in);
+        return;
+    }
+    const double *const parts[2] = {ws.prz + (size_t)f * ws.NB, ws.prr + (size_t)f * ws.NB};
+    double top[2];
+    pr_finish<2>(parts, ws.NB, sw, top);
+    PrRec out = in;
+    const bool fresh = in.phase == PR_FRESH;
+    double beta = 0.0;
+    out.rho = top[0];
+    out.rr = top[1];
+    if (fresh) {
+        out.bb = top[1];                                                       // r = b: T(b*b) is T(r*r)
+    } else {
+        beta = top[0] / in.rho;
+        out.iters = in.iters + 1;
+    }
+    out.phase = PR_MID;
+    if (out.bb > 0.0 && out.rr <= (tol * tol) * out.bb) {                      // b = 0 is left to the breakdown rule
+        out.state = PIVLFN_PRESSURE_CONVERGED;
+        if (writer) pr_store(ws.recB + f, out);
+        return;
+    }
+    const size_t fo = (size_t)f * N;
+    const bool odd = (in.dsel & 1) != 0;                                       // a select, not an index: the arguments stay in registers
+    const double *z = ws.z + fo, *dold = (odd ? ws.d[1] : ws.d[0]) + fo;
+    double *dnew = (odd ? ws.d[0] : ws.d[1]) + fo, *q = ws.q + fo;
+    const unsigned char *adj = ws.adj + fo;
+    out.dsel = (in.dsel & 1) ^ 1;
+    PrCounter cnt;
+    double root = 0.0;
+    for (int c = 0; c < ws.chunks; ++c) {
+        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
+        double leaf[PR_OWN];
+#pragma unroll
+        for (int j = 0; j < PR_OWN; ++j) {
+            leaf[j] = 0.0;
+            if (base + j < N) {
+                const unsigned i = (unsigned)(base + j), a = adj[i];
+                // the direction of a node, its own or a neighbour's: an edge is active only where the neighbour exists
+#define PR_D(k) (fresh ? z[k] : z[k] + beta * dold[k])
+                const double dc = PR_D(i);
+                // (the bounds hold for every byte setup writes; they keep a workspace that never saw setup inside itself)
+                const double dl = ((a & 1u) && i > 0) ? PR_D(i - 1) : 0.0, dr = ((a & 2u) && i + 1 < N) ? PR_D(i + 1) : 0.0;
+                const double du = ((a & 4u) && i >= (unsigned)w) ? PR_D(i - w) : 0.0, dd = ((a & 8u) && i + (unsigned)w < N) ? PR_D(i + w) : 0.0;
+#undef PR_D
+                const double qv = pr_deg(a) * dc - (((dl + dr) + du) + dd);
+                dnew[i] = dc;
+                q[i] = qv;
+                leaf[j] = dc * qv;
+            }
+        }
+        double v[1] = {(leaf[0] + leaf[1]) + (leaf[2] + leaf[3])};
+        pr_chunk_root<1>(v, sw);
+        root = cnt.add(v[0], c);
+    }
+    if (tid == 0) {
+        ws.pdq[(size_t)f * ws.NB + blk] = root;
+        if (blk == 0) pr_store(ws.recB + f, out);
+    }
+}
+
+// Second kernel: finish sigma, the breakdown rule, x, r, z and the partials of r*z and r*r.  recB -> recA.
+__global__ __launch_bounds__(PR_THREADS) void pressure_cg_xr_kernel(const PrWs ws)
+{
+#pragma clang fp contract(off)
+    __shared__ double sw[2][4];
+    const unsigned N = ws.N, f = blockIdx.x / (unsigned)ws.NB, blk = blockIdx.x - f * (unsigned)ws.NB;
+    const int tid = threadIdx.x;
+    const PrRec in = pr_load(ws.recB + f);
+    const bool writer = blk == 0 && tid == 0;
+    if (in.state != PIVLFN_PRESSURE_RUNNING) {
+        if (writer) pr_store(ws.recA + f, in);
+        return;
+    }
+    const double *const parts[1] = {ws.pdq + (size_t)f * ws.NB};
+    double top[1];
+    pr_finish<1>(parts, ws.NB, sw, top);
+    const double sigma = top[0];
+    PrRec out = in;
+    if (!(sigma > 0.0)) {                                                      // NaN included
+        out.state = PIVLFN_PRESSURE_BREAKDOWN;
+        if (writer) pr_store(ws.recA + f, out);
+        return;
+    }
+    const double alpha = in.rho / sigma;
+    const size_t fo = (size_t)f * N;
+    const double *d = ((in.dsel & 1) ? ws.d[1] : ws.d[0]) + fo, *q = ws.q + fo;
+    double *x = ws.x + fo, *r = ws.r + fo, *z = ws.z + fo;
+    const unsigned char *adj = ws.adj + fo;
+    PrCounter crz, crr;
+    double root_rz = 0.0, root_rr = 0.0;
+    for (int c = 0; c < ws.chunks; ++c) {
+        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
+        double lrz[PR_OWN], lrr[PR_OWN];
+#pragma unroll
+        for (int j = 0; j < PR_OWN; ++j) {
+            lrz[j] = lrr[j] = 0.0;
+            if (base + j < N) {
+                const unsigned i = (unsigned)(base + j), a = adj[i] & 15u;
+                x[i] = x[i] + alpha * d[i];
+                const double rn = r[i] - alpha * q[i];
+                const double zn = a ? rn / pr_deg(a) : 0.0;
+                r[i] = rn;
+                z[i] = zn;
+                lrz[j] = rn * zn;
+                lrr[j] = rn * rn;
+            }
+        }
+        double v[2] = {(lrz[0] + lrz[1]) + (lrz[2] + lrz[3]), (lrr[0] + lrr[1]) + (lrr[2] + lrr[3])};
+        pr_chunk_root<2>(v, sw);
+        root_rz = crz.add(v[0], c);
+        root_rr = crr.add(v[1], c);
+    }
+    out.phase = PR_PENDING;
+    if (tid == 0) {
+        ws.prz[(size_t)f * ws.NB + blk] = root_rz;
+        ws.prr[(size_t)f * ws.NB + blk] = root_rr;
+        if (blk == 0) pr_store(ws.recA + f, out);
+    }
+}
+
+// ---- read-out ---------------------------------------------------------------------------------------------------------------------------
+// p, flag and the status record; a running frame's rr (and, behind a finished iteration, its count) is completed from the partials.
+__global__ __launch_bounds__(PR_THREADS) void pressure_read_kernel(const PrWs ws, double *p, unsigned char *flag, double *status)
+{
+#pragma clang fp contract(off)
+    __shared__ double sw[1][4];
+    const unsigned N = ws.N, f = blockIdx.x / (unsigned)ws.NB, blk = blockIdx.x - f * (unsigned)ws.NB;
+    const int tid = threadIdx.x;
+    const size_t fo = (size_t)f * N;
+    if (blk == 0) {                                                            // the whole workgroup: pr_finish synchronises it
+        PrRec rec = pr_load(ws.recA + f);
+        if (rec.state == PIVLFN_PRESSURE_RUNNING) {
+            const double *const parts[1] = {ws.prr + (size_t)f * ws.NB};
+            double top[1];
+            pr_finish<1>(parts, ws.NB, sw, top);
+            rec.rr = top[0];
+            if (rec.phase == PR_FRESH) rec.bb = top[0];
+            else rec.iters += 1;
+        }
+        if (tid == 0) {
+            status[4 * (size_t)f + 0] = (double)rec.state;
+            status[4 * (size_t)f + 1] = (double)rec.iters;
+            status[4 * (size_t)f + 2] = rec.rr;
+            status[4 * (size_t)f + 3] = rec.bb;
+        }
+    }
+    for (int c = 0; c < ws.chunks; ++c) {
+        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
+#pragma unroll
+        for (int j = 0; j < PR_OWN; ++j)
+            if (base + j < N) {
+                const size_t i = fo + base + j;
+                const unsigned a = ws.adj[i];
+                p[i] = (a & 15u) ? ws.x[i] : __longlong_as_double(0x7ff8000000000000LL);
+                flag[i] = !(a & 16u) ? PIVLFN_PRESSURE_INVALID : !(a & 15u) ? PIVLFN_PRESSURE_ISOLATED : 0;
+            }
+    }
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------------------
+static bool pr_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
+    return pa < pb + nb && pb < pa + na;
+}
+
+#define PR_SHAPE(fn, F, h, w)                                                                                                   \
+    PIV_REQUIRE(h >= 1 && w >= 1, fn ": bad lattice h=%d w=%d (both must be positive)", h, w);                                   \
+    PIV_REQUIRE((size_t)(F) * h * w < ((size_t)1 << 31), fn ": F*h*w=%zu nodes, must stay below 2^31 (32-bit node index)", (size_t)(F) * h * w)
+
+#define PR_WORKSPACE(fn, F, h, w, ws, ws_bytes)                                                                                 \
+    PIV_REQUIRE(ws != nullptr, fn ": null pointer (the workspace is required)");                                                \
+    PIV_REQUIRE(reinterpret_cast<size_t>(ws) % 8 == 0, fn ": the workspace must be 8-byte aligned");                            \
+    PIV_REQUIRE(ws_bytes >= pressure_workspace_bytes(F, h, w), fn ": workspace of %zu bytes, pivlfn_pressure_workspace_bytes asks for %zu", \
+                (size_t)(ws_bytes), pressure_workspace_bytes(F, h, w))
+
+int launch_pressure_gradient(const float *flows, int B, int h, int w, double s, double nu, double *g, unsigned char *valid, hipStream_t st)
+{
+    PIV_REQUIRE(B >= 3, "pressure_gradient: B=%d flows, a frame needs three consecutive ones", B);
+    PR_SHAPE("pressure_gradient", B - 2, h, w);
+    PIV_REQUIRE(std::isfinite(s) && s > 0.0, "pressure_gradient: s=%g must be finite and positive (pixels per node)", s);
+    PIV_REQUIRE(std::isfinite(nu), "pressure_gradient: nu=%g must be finite", nu);
+    PIV_REQUIRE(flows && g && valid, "pressure_gradient: null pointer (flows, g and valid are required)");
+    const int F = B - 2;
+    const size_t N = (size_t)h * w, in_bytes = (size_t)B * 2 * N * 4, g_bytes = (size_t)F * 2 * N * 8, v_bytes = (size_t)F * N;
+    PIV_REQUIRE(!pr_overlap(g, g_bytes, flows, in_bytes), "pressure_gradient: g overlaps flows");
+    PIV_REQUIRE(!pr_overlap(valid, v_bytes, flows, in_bytes), "pressure_gradient: valid overlaps flows");
+    PIV_REQUIRE(!pr_overlap(valid, v_bytes, g, g_bytes), "pressure_gradient: valid overlaps g");
+    const unsigned total = (unsigned)((size_t)F * N);
+    hipLaunchKernelGGL(pressure_gradient_kernel, dim3((total + PR_THREADS - 1) / PR_THREADS), dim3(PR_THREADS), 0, st, flows, F, h, w, s, nu, g,
+                       valid);
+    PIV_CHECK_HIP(hipGetLastError());
+    return PIVLFN_OK;
+}
+
+int launch_pressure_setup(const double *g, const unsigned char *valid, int F, int h, int w, double s, void *ws, size_t ws_bytes, hipStream_t st)
+{
+    PIV_REQUIRE(F >= 1, "pressure_setup: F=%d frames, must be positive", F);
+    PR_SHAPE("pressure_setup", F, h, w);
+    PIV_REQUIRE(std::isfinite(s) && s > 0.0, "pressure_setup: s=%g must be finite and positive (pixels per node)", s);
+    PIV_REQUIRE(g && valid, "pressure_setup: null pointer (g and valid are required)");
+    PR_WORKSPACE("pressure_setup", F, h, w, ws, ws_bytes);
+    const size_t N = (size_t)h * w, need = pressure_workspace_bytes(F, h, w);
+    PIV_REQUIRE(!pr_overlap(ws, need, g, (size_t)F * 2 * N * 8), "pressure_setup: the workspace overlaps g");
+    PIV_REQUIRE(!pr_overlap(ws, need, valid, (size_t)F * N), "pressure_setup: the workspace overlaps valid");
+    const PrLayout L = pr_layout(ws, F, h, w);
+    hipLaunchKernelGGL(pressure_setup_kernel, dim3((unsigned)F * (unsigned)L.ws.NB), dim3(PR_THREADS), 0, st, g, valid, s, L.ws);
+    PIV_CHECK_HIP(hipGetLastError());
+    return PIVLFN_OK;
+}
+
+int launch_pressure_cg(void *ws, size_t ws_bytes, int F, int h, int w, double tol, int iters, hipStream_t st)
+{
+    PIV_REQUIRE(F >= 1, "pressure_cg: F=%d frames, must be positive", F);
+    PR_SHAPE("pressure_cg", F, h, w);
+    PIV_REQUIRE(std::isfinite(tol) && tol > 0.0, "pressure_cg: tol=%g must be finite and positive", tol);
+    PIV_REQUIRE(iters >= 0, "pressure_cg: iters=%d must not be negative", iters);
+    PR_WORKSPACE("pressure_cg", F, h, w, ws, ws_bytes);
+    if (iters == 0) return PIVLFN_OK;                                          // nothing to enqueue
+    const PrLayout L = pr_layout(ws, F, h, w);
+    const dim3 grid((unsigned)F * (unsigned)L.ws.NB), block(PR_THREADS);
+    for (int it = 0; it < iters; ++it) {
+        hipLaunchKernelGGL(pressure_cg_dq_kernel, grid, block, 0, st, L.ws, tol);
+        hipLaunchKernelGGL(pressure_cg_xr_kernel, grid, block, 0, st, L.ws);
+    }
+    PIV_CHECK_HIP(hipGetLastError());
+    return PIVLFN_OK;
+}
+
+int launch_pressure_read(const void *ws, size_t ws_bytes, int F, int h, int w, double *p, unsigned char *flag, double *status, hipStream_t st)
+{
+    PIV_REQUIRE(F >= 1, "pressure_read: F=%d frames, must be positive", F);
+    PR_SHAPE("pressure_read", F, h, w);
+    PIV_REQUIRE(p && flag && status, "pressure_read: null pointer (p, flag and status are required)");
+    PR_WORKSPACE("pressure_read", F, h, w, ws, ws_bytes);
+    const size_t N = (size_t)h * w, need = pressure_workspace_bytes(F, h, w);
+    const struct { const void *ptr; size_t bytes; const char *name; } outs[] = {{p, (size_t)F * N * 8, "p"}, {flag, (size_t)F * N, "flag"},
+                                                                               {status, (size_t)F * 32, "status"}};
+    for (int a = 0; a < 3; ++a) {
+        PIV_REQUIRE(!pr_overlap(outs[a].ptr, outs[a].bytes, ws, need), "pressure_read: %s overlaps the workspace", outs[a].name);
+        for (int b = a + 1; b < 3; ++b)
+            PIV_REQUIRE(!pr_overlap(outs[a].ptr, outs[a].bytes, outs[b].ptr, outs[b].bytes), "pressure_read: %s overlaps %s", outs[a].name,
+                        outs[b].name);
+    }
+    const PrLayout L = pr_layout(const_cast<void *>(ws), F, h, w);
+    hipLaunchKernelGGL(pressure_read_kernel, dim3((unsigned)F * (unsigned)L.ws.NB), dim3(PR_THREADS), 0, st, L.ws, p, flag, status);
+    PIV_CHECK_HIP(hipGetLastError());
+    return PIVLFN_OK;
+}
+
+}  // namespace pivlfn

@@ -18,6 +18,7 @@ from .flowmap import LOST, OUT, UNDEFINED, FlowMap, FTLEField           # noqa: 
 from .pod import FlowPOD, PODResult                                     # noqa: F401
 from .twopoint import TwoPointResult, TwoPointStats                     # noqa: F401
 from .spectrum import TemporalSpectrum, TemporalSpectrumResult          # noqa: F401
+from .pressure import PressureField, PressureResult                     # noqa: F401
 from .particles import BAD, PairParticles, ParticleImageGen, ParticleImages, displace_particles, render_particles  # noqa: F401
 from .viz import (PngWriter, color_wheel_image, decimate_flow, field_absmax, flow_maxrad, flow_to_color, motion_to_color,  # noqa: F401
                   quiver_plot, scalar_to_color, vorticity_image, write_png, write_png_gray, GrayPngWriter)
@@ -28,5 +29,5 @@ __all__ = ["FunctionCorrelation", "ModuleCorrelation", "LiteFlowNet", "LiteFlowN
            "flow_maxrad", "scalar_to_color", "field_absmax", "vorticity_image", "decimate_flow", "quiver_plot", "color_wheel_image",
            "write_png", "PngWriter", "write_png_gray", "GrayPngWriter", "match_quality", "MatchQuality", "FEW", "FLAT", "NO_PEAK", "CENTRE_OUT",
            "vortex_gamma", "VortexField", "FlowMap", "FTLEField", "OUT", "LOST", "UNDEFINED", "FlowPOD", "PODResult", "TwoPointStats", "TwoPointResult",
-           "TemporalSpectrum", "TemporalSpectrumResult",
+           "TemporalSpectrum", "TemporalSpectrumResult", "PressureField", "PressureResult",
            "ParticleImageGen", "ParticleImages", "PairParticles", "displace_particles", "render_particles", "BAD"]

@@ -71,6 +71,13 @@ SIGNATURES = {
     "pivlfn_twopoint_accumulate": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
     "pivlfn_spectrum_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,
                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pivlfn_pressure_gradient": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_double] * 2 + [ctypes.c_void_p] * 3),
+    "pivlfn_pressure_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "pivlfn_pressure_workspace_offset": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "pivlfn_pressure_setup": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t,
+                                                                                          ctypes.c_void_p]),
+    "pivlfn_pressure_cg": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 3 + [ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
+    "pivlfn_pressure_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4),
     "pivlfn_snapshot_gram_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_long]),
     "pivlfn_snapshot_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_size_t, ctypes.c_void_p]),

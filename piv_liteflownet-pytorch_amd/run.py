@@ -9,6 +9,8 @@
                 [--ftle [SPACING] [--ftle-steps T] [--ftle-image [--ftle-max X]]]
                 [--twopoint [R] [--twopoint-step S] [--twopoint-mean FILE]]
                 [--spectrum [L] [--spectrum-overlap O] [--spectrum-cell C] [--spectrum-fps F] [--spectrum-image]]
+                [--pressure [CELL] [--pressure-rho R] [--pressure-nu NU] [--pressure-dt DT] [--pressure-calib C] [--pressure-tol T]
+                 [--pressure-image]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -59,6 +61,15 @@ Differences, all deliberate:
     segments and the pairs left over); with `--spectrum-image` <save>/spectrum_peak.png, the dominant-frequency map in gray on
     0..the highest frequency kept, vectors without a segment red; with --validate flag|mask a rejected vector drops the segments
     it sits in;
+  * `--pressure [CELL]` integrates the pressure field of every flow of an input directory that has both neighbours in time; the
+    directory must be a time-resolved frame sequence (not -p).  On the device (pivlfn.pressure.PressureField): the flows are averaged
+    over CELL x CELL blocks (default 4), the material acceleration is taken by central differences over three consecutive flows and
+    the pressure gradient is integrated in the least-squares sense by conjugate gradients.  `--pressure-rho R`, `--pressure-nu NU`,
+    `--pressure-dt DT` (time per pair) and `--pressure-calib C` (length per pixel) give the units, all default to lattice units (1, 0, 1,
+    1); `--pressure-tol T` is the relative residual to reach (default 1e-8).  Per centred pair <name>_pres.flo with the bands p and
+    |grad p| on the lattice (1e10 where a node has no value; the first and the last pair of a directory get none), the parameters and
+    per-pair summaries in <save>/pressure.json, with `--pressure-image` <name>_pres.png (blue - white - red on a symmetric range);
+    with --validate flag|mask the rejected vectors are left out of the block means.  A single process, not with -b/-c;
   * `--pod K` decomposes the flows of every input directory after it has been processed (pivlfn.pod.FlowPOD, snapshot POD: the
     Gram matrix of the flows in float64 on the device, its eigenvectors on the host): the first K modes, the mean, the coefficients
     and the energy fractions go to <save>/pod.npz, one line per mode is printed, and with --color the modes are drawn as
@@ -104,6 +115,8 @@ from pivlfn.imagemod import mod_name                     # noqa: E402
 from pivlfn.inference import estimate                    # noqa: E402
 from pivlfn.pipeline import PairLoader, stream_pairs     # noqa: E402
 from pivlfn.pod import FlowPOD                           # noqa: E402
+from pivlfn.pressure import PressureField                # noqa: E402
+from pivlfn.pressure import check_params as check_pressure               # noqa: E402
 from pivlfn.postpro import FlowStats                     # noqa: E402
 from pivlfn.preproc import FrameBackground, Preprocessor                 # noqa: E402
 from pivlfn.spectrum import TemporalSpectrum             # noqa: E402
@@ -248,6 +261,19 @@ parser.add_argument("--spectrum-fps", type=float, default=None, metavar="F",
 parser.add_argument("--spectrum-image", action="store_true",
                     help="with --spectrum: also <save>/spectrum_peak.png, the dominant-frequency map in gray, vectors without a segment in red")
 PREP_FLAGS = ("background", "minmax", "minmax_floor")
+parser.add_argument("--pressure", type=int, nargs="?", const=4, default=None, metavar="CELL",
+                    help="integrate the pressure field of every flow that has both neighbours in time (pivlfn.pressure.PressureField; not a "
+                         "reference flag; not with -p or -b/-c, single process only) on the means over CELL x CELL blocks of vectors "
+                         "(default 4): <name>_pres.flo with the bands p and |grad p|, the summaries in <save>/pressure.json")
+parser.add_argument("--pressure-rho", type=float, default=None, metavar="R", help="with --pressure: the density (default 1)")
+parser.add_argument("--pressure-nu", type=float, default=None, metavar="NU", help="with --pressure: the kinematic viscosity (default 0)")
+parser.add_argument("--pressure-dt", type=float, default=None, metavar="DT", help="with --pressure: the time between two pairs (default 1)")
+parser.add_argument("--pressure-calib", type=float, default=None, metavar="C", help="with --pressure: the length of a pixel (default 1)")
+parser.add_argument("--pressure-tol", type=float, default=None, metavar="T",
+                    help="with --pressure: the relative residual at which the conjugate gradients stop (default 1e-8)")
+parser.add_argument("--pressure-image", action="store_true",
+                    help="with --pressure: also <name>_pres.png, p in blue - white - red on a symmetric range, nodes without a value black")
+PRESSURE_FLAGS = ("pressure", "pressure_rho", "pressure_nu", "pressure_dt", "pressure_calib", "pressure_tol", "pressure_image")
 SPECTRUM_FLAGS = ("spectrum", "spectrum_overlap", "spectrum_cell", "spectrum_fps", "spectrum_image")
 TWOPOINT_FLAGS = ("twopoint", "twopoint_step", "twopoint_mean")
 POD_FLAGS = ("pod", "pod_cell")
@@ -256,7 +282,7 @@ QUALITY_BAD_RGB = (255, 0, 0)
 VORTEX_FLAGS = ("vortex", "vortex_spacing", "vortex_image")
 PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
 FTLE_FLAGS = ("ftle", "ftle_steps", "ftle_image", "ftle_max")
-VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + SPECTRUM_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + SPECTRUM_FLAGS + PRESSURE_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -555,6 +581,75 @@ class Spectrum(Stage):
             rgb = viz.scalar_to_color(torch.from_numpy(f[None]).to(self.spectrum.device), 0.0, float(res.freq[-1]), cmap="gray",
                                       bad=QUALITY_BAD_RGB)
             viz.write_png(self.image_file, rgb[0].cpu().numpy())
+
+
+def pressure_params(args):
+    """(cell, calib, dt, rho, nu, tol) of the --pressure flags with the defaults filled in."""
+    pick = lambda v, d: d if v is None else v            # noqa: E731
+    return (args.pressure, pick(args.pressure_calib, 1.0), pick(args.pressure_dt, 1.0), pick(args.pressure_rho, 1.0),
+            pick(args.pressure_nu, 0.0), pick(args.pressure_tol, 1e-8))
+
+
+class Pressure(Stage):
+    """Feeds every batch of flows to a PressureField, created at the first batch's size and fed like Stats: after "flag" and "mask"
+    the raw flow with the flags as the mask, otherwise the written flow.  A frame is centred on every pair that has both neighbours, so
+    the results of a batch belong to pairs one earlier; they stay on the device until finish() writes the files."""
+
+    def __init__(self, params, image, flowdir, file):
+        self.params, self.image, self.flowdir, self.file = params, image, flowdir, file
+        self.field, self.mode, self.results = None, None, []
+
+    def __call__(self, batch):
+        flow, flag = batch.masked()
+        if self.field is None:
+            cell, calib, dt, rho, nu, tol = self.params
+            try:
+                self.field = PressureField(flow.size(2), flow.size(3), cell, calib, dt, rho, nu, tol, device=flow.device)
+            except ValueError as e:
+                raise SystemExit(f"run.py: --pressure: {e}")
+            self.mode = batch.mode
+        self.results.append(self.field.update(flow, flag))
+
+    def finish(self, names, ctx):
+        """<flow dir>/<name>_pres.flo (bands p and |grad p| on the lattice, float32, 1e10 where the node is not ok) for every pair
+        but the first and the last, with `image` the picture beside it, and <save>/pressure.json."""
+        cell, calib, dt, rho, nu, tol = self.params
+        doc = {"cell": cell, "calib": calib, "dt": dt, "rho": rho, "nu": nu, "tol": tol, "validation": self.mode,
+               "max_iter": None if self.field is None else self.field.max_iter,
+               "lattice": None if self.field is None else [self.field.ch, self.field.cw], "pairs": {}, "unconverged": 0}
+        centred = names[1:-1]
+        assert sum(len(r) for r in self.results) == len(centred)
+        at = 0
+        with FloWriter() as writer, viz.PngWriter() as pictures:
+            for res in self.results:
+                if len(res) == 0:
+                    continue
+                summary = res.summary()
+                doc["unconverged"] += summary["unconverged"]
+                for f in range(len(res)):
+                    name = centred[at]
+                    at += 1
+                    doc["pairs"][os.path.basename(flowname_modifier(name, self.flowdir, ext="", pair=False))] = summary["frames"][f]
+                    writer.submit(pressure_bands(res.p[f], res.grad[f], res.flag[f]), flowname_modifier(name, self.flowdir, ext="_pres.flo", pair=False))
+                    if self.image:
+                        top = max(abs(summary["frames"][f]["p_min"] or 0.0), abs(summary["frames"][f]["p_max"] or 0.0)) or 1.0
+                        p = torch.from_numpy(np.ascontiguousarray(res.p[f][None])).to(res.p_star.device)
+                        rgb = viz.scalar_to_color(p, -top, top, cmap="bwr")
+                        pictures.submit(rgb[0].cpu().numpy(), flowname_modifier(name, self.flowdir, ext="_pres.png", pair=False))
+        write_json(self.file, json_strict(doc), allow_nan=False)
+        print(f"Pressure of {len(centred)} pairs on {doc['lattice']} nodes: {doc['unconverged']} not converged -> '{self.file}'")
+
+
+def pressure_bands(p, grad, flag):
+    """[ch,cw,2] float32: p and |grad p|, 1e10 where the node is not ok."""
+    ok = flag == 0
+    mag = np.sqrt(grad[0] * grad[0] + grad[1] * grad[1])
+    return np.stack([np.where(ok, p, 1e10), np.where(ok, mag, 1e10)], axis=2).astype(np.float32)
+
+
+def check_pressure_pairs(pairs, inputdir):
+    if pairs < 3:
+        raise SystemExit(f"run.py: --pressure: '{inputdir}' has {pairs} pairs, fewer than the 3 a pressure field is centred in")
 
 
 def check_spectrum_pairs(pairs, segment, inputdir):
@@ -929,6 +1024,8 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
     if args.spectrum is not None:
         check_spectrum_pairs(len(Run(root=inputdir, is_pair=args.is_pair, n_images=args.num_images, start_at=args.start)), args.spectrum,
                              inputdir)
+    if args.pressure is not None:
+        check_pressure_pairs(len(Run(root=inputdir, is_pair=args.is_pair, n_images=args.num_images, start_at=args.start)), inputdir)
     if args.validate is not None:
         stages.append(Validate(args.validate, args.validate_radius, args.validate_spacing, args.validate_eps, args.validate_thresh,
                                layout.sibling("validation.json")))
@@ -941,6 +1038,8 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
         stages.append(Spectrum(args.spectrum, args.spectrum_overlap, args.spectrum_cell or 1, 1.0 if args.spectrum_fps is None else args.spectrum_fps,
                                args.spectrum_image, layout.sibling("spectrum.npz"), layout.sibling("spectrum.json"),
                                layout.sibling("spectrum_peak.png")))
+    if args.pressure is not None:
+        stages.append(Pressure(pressure_params(args), args.pressure_image, layout.flow, layout.sibling("pressure.json")))
     if args.truth is not None:
         lo, hi = shard_bounds(len(truth_paths), rank, world)
         stages.append(Truth(net, truth_paths[lo:hi], args.truth_levels, layout.sibling("errors.json"), layout.sibling("error_maps.npz"),
@@ -1101,7 +1200,8 @@ def args_lines(args) -> List[str]:
                     (args.truth is None and k in TRUTH_FLAGS) or (not pictures and k in PICTURE_FLAGS) or
                     (args.quality is None and k in QUALITY_FLAGS) or (args.vortex is None and k in VORTEX_FLAGS) or
                     (args.pod is None and k in POD_FLAGS) or (args.ftle is None and k in FTLE_FLAGS) or
-                    (args.twopoint is None and k in TWOPOINT_FLAGS) or (args.spectrum is None and k in SPECTRUM_FLAGS))]
+                    (args.twopoint is None and k in TWOPOINT_FLAGS) or (args.spectrum is None and k in SPECTRUM_FLAGS) or
+                    (args.pressure is None and k in PRESSURE_FLAGS))]
 
 
 def load_weights(args) -> Tuple[dict, str]:
@@ -1147,6 +1247,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         refuse_sharded("--spectrum", "a spectrum follows the pairs of a directory in order, on one device")
         checked("--spectrum: ", check_spectrum, args.spectrum, args.spectrum_overlap, "hann", "constant",
                 1 if args.spectrum_cell is None else args.spectrum_cell, 1.0 if args.spectrum_fps is None else args.spectrum_fps)
+    if _used(args, PRESSURE_FLAGS[1:]) and args.pressure is None:
+        raise SystemExit("run.py: --pressure-rho, --pressure-nu, --pressure-dt, --pressure-calib, --pressure-tol and --pressure-image need "
+                         "--pressure")
+    if args.pressure is not None:
+        refuse_mods(args, "--pressure is")
+        if args.is_pair:
+            raise SystemExit("run.py: --pressure is not available with -p (the pairs of a pair folder are not a time series)")
+        refuse_sharded("--pressure", "a pressure field follows the pairs of a directory in order, on one device")
+        checked("--pressure: ", check_pressure, *pressure_params(args))
     if args.pod_cell is not None and args.pod is None:
         raise SystemExit("run.py: --pod-cell needs --pod")
     if args.pod is not None:

@@ -4,6 +4,7 @@
   python tools/bench_ops.py warp_corr [--batch 1] [--variants 0,8,9]   (0 shipped policy, 8 v7, 9 v6)
   python tools/bench_ops.py twopoint                                  (pivlfn_twopoint_accumulate against its HBM and fp64 bounds)
   python tools/bench_ops.py spectrum                                  (pivlfn_spectrum_accumulate, and the same sums from snapshot_project + torch)
+  python tools/bench_ops.py pressure                                  (pivlfn_pressure_cg: us per iteration at 256^2 x 8 and 1024^2 x 1)
 Times N back-to-back launches between two events on the current stream (so each figure includes one ~1.5 us
 kernel boundary) and checks that all variants agree.
 """
@@ -475,9 +476,78 @@ def bench_spectrum(args):
         del ring, acc, count, out, one
 
 
+def bench_pressure(args):
+    """pivlfn_pressure_cg (csrc/pressure.hip): microseconds per conjugate-gradient iteration at 256 x 256 nodes x 8 frames and at
+    1024 x 1024 x 1, on the production library.  A timed call is setup + n iterations at a tolerance that never stops a frame (a
+    stopped frame's launches return at once); the time of an iteration is the difference between n = 200 and n = 100, over 100, so
+    the set-up and the first launch cancel.  Beside it the bound: the 90 bytes per node an iteration moves (11 doubles and 2 bytes, see
+    the head of the kernel file) at the HBM peak, the figure bench.py quotes its rooflines against.  Then bench_pressure_wall."""
+    from pivlfn import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream(dev).cuda_stream
+    for F, S in ((8, 256), (1, 1024)):
+        gen = torch.Generator().manual_seed(4)
+        flows = torch.randn(F + 2, 2, S, S, generator=gen).to(dev)
+        g = torch.empty(F, 2, S, S, dtype=torch.float64, device=dev)
+        valid = torch.empty(F, S, S, dtype=torch.uint8, device=dev)
+        nws = lib.pivlfn_pressure_workspace_bytes(F, S, S)
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        status = torch.empty(F, 4, dtype=torch.float64, device=dev)
+        p, flag = torch.empty(F, S, S, dtype=torch.float64, device=dev), torch.empty(F, S, S, dtype=torch.uint8, device=dev)
+        _lib.check(lib.pivlfn_pressure_gradient(flows.data_ptr(), F + 2, S, S, 4.0, 0.01, g.data_ptr(), valid.data_ptr(), st), "gradient")
+
+        def fn(n):
+            _lib.check(lib.pivlfn_pressure_setup(g.data_ptr(), valid.data_ptr(), F, S, S, 4.0, ws.data_ptr(), nws, st), "setup")
+            _lib.check(lib.pivlfn_pressure_cg(ws.data_ptr(), nws, F, S, S, 1e-200, n, st), "cg")
+        t100, t200 = time_it(lambda: fn(100), n=3, rounds=7)[1], time_it(lambda: fn(200), n=3, rounds=7)[1]
+        _lib.check(lib.pivlfn_pressure_read(ws.data_ptr(), nws, F, S, S, p.data_ptr(), flag.data_ptr(), status.data_ptr(), st), "read")
+        running = int((status[:, 0] == 1).sum())
+        per = (t200 - t100) / 100.0
+        hbm = 90.0 * F * S * S / HBM_BYTES_PER_S * 1e6
+        print(f"pressure_cg F={F} {S}x{S}: setup + 100 it {t100:9.1f} us, + 200 it {t200:9.1f} us -> {per:7.2f} us per iteration (2 launches); "
+              f"HBM bound {hbm:6.2f} us = {100 * hbm / per:5.1f} % of the time; {running} of {F} frames still running after 200", flush=True)
+        del flows, g, valid, ws, p, flag
+    bench_pressure_wall(dev)
+
+
+def bench_pressure_wall(dev):
+    """Wall time of pivlfn.PressureField.update per frame at 1024 x 1024 flows, cell 4 (256 x 256 nodes), tol 1e-8: decaying vortices of
+    wavelength 256 px plus noise of 0.05 px; a host timer around update() and a synchronisation.  Ten flows in one update() (eight
+    frames share their launches), three times -- the first includes the warm-up --, then one flow per update()."""
+    import time
+
+    import numpy as np
+    from pivlfn import PressureField
+    H = W = 1024
+    y, x = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    k = 2 * np.pi / 256
+    flows = np.stack([np.stack([2 * np.sin(k * x) * np.cos(k * y), -2 * np.cos(k * x) * np.sin(k * y)]) * np.exp(-0.01 * n) for n in range(10)])
+    flows = torch.from_numpy((flows + np.random.default_rng(0).normal(0, 0.05, flows.shape)).astype(np.float32)).to(dev)
+    for sync_every in (64, None):
+        for _ in range(3):
+            pf = PressureField(H, W, 4, tol=1e-8, sync_every=sync_every, device=dev)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            res = pf.update(flows)
+            it = res.iterations                       # copies the status back: synchronises
+            dt = time.perf_counter() - t
+            print(f"sync_every={sync_every}: {len(res)} frames in one update, {dt * 1e3:.1f} ms = {dt * 1e3 / len(res):.2f} ms per frame; "
+                  f"iterations {it.min()}..{it.max()} of max_iter {pf.max_iter}; converged {int(res.converged.sum())}; residual max "
+                  f"{res.residual.max():.2e}", flush=True)
+        pf = PressureField(H, W, 4, tol=1e-8, sync_every=sync_every, device=dev)
+        pf.update(flows[:2])
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for n in range(2, 10):
+            _ = pf.update(flows[n:n + 1]).iterations
+        dt = time.perf_counter() - t
+        print(f"sync_every={sync_every}: one frame per update, {dt * 1e3 / 8:.2f} ms per frame", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate", "twopoint", "spectrum"])
+    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate", "twopoint", "spectrum", "pressure"])
     ap.add_argument("--once", action="store_true", help="preproc: one launch per shape, for a kernel trace")
     ap.add_argument("--filter", default="")
     ap.add_argument("--tune3", type=int, default=0, help="ablation mask of the fp16 conv kernel (pivlfn_tune(3, mask))")
@@ -491,4 +561,4 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=8, help="interleaved timing rounds per variant (warp_corr)")
     a = ap.parse_args()
     {"conv_stamps": bench_conv_stamps, "warp_corr": bench_warp_corr, "wc_ablate": bench_wc_ablate, "conv": bench_conv, "head": bench_head,
-     "preproc": bench_preproc, "evaluate": bench_evaluate, "twopoint": bench_twopoint, "spectrum": bench_spectrum}[a.what](a)
+     "preproc": bench_preproc, "evaluate": bench_evaluate, "twopoint": bench_twopoint, "spectrum": bench_spectrum, "pressure": bench_pressure}[a.what](a)
