@@ -675,6 +675,63 @@ int pivlfn_pressure_cg(void *workspace, size_t workspace_bytes, int F, int h, in
 int pivlfn_pressure_read(const void *workspace, size_t workspace_bytes, int F, int h, int w, double *p, unsigned char *flag,
                          double *status, void *stream);
 
+/* ---- stereo calibration: what produces the coefficients pivlfn_stereo_2d3c reads.  Template matching of a calibration target
+ * (stereo/matching.py:32-56, OpenCV's TM_CCOEFF_NORMED), marker centres from the correlation map (matching.py:49-75: threshold,
+ * cv2.blur (2, 2), ndimage.label, centre of mass) and the image dewarp (stereo/dewarp.py:196-270, warp / nl_trans).  The fit of the
+ * coefficients themselves is host code (pivlfn/calibrate.py).  Added without an ABI bump (additive).  Every entry point launches on
+ * `stream` only, allocates nothing, does not synchronise and can be captured into a graph; the workspaces need no initial contents.
+ *
+ * pivlfn_template_match -- images [B,H,W] bytes, templ [th,tw] bytes (th and tw odd, th*tw <= 65025), r [B,H,W] fp32.  The template is
+ *   centred on each pixel of the image zero-padded by (th-1)/2 rows and (tw-1)/2 columns (template_matching's pad_gray).  With the sums
+ *   over the window, N = th*tw:
+ *       num = N*sum(I*T) - sum(I)*sum(T);   a = N*sum(T*T) - sum(T)^2;   b = N*sum(I*I) - sum(I)^2          (integers, exact)
+ *       r = (float)((double)num / sqrt((double)a * (double)b)),   r = +0.0 where a == 0 or b == 0 (flat template or flat window).
+ *   The window sums fit 32 bits unsigned (255^2 * 65025 < 2^32), num, a and b are below 2^53 in magnitude: the conversions are exact
+ *   and the product, the root and the quotient are each rounded once (no fma).  The result does not depend on the tiling or on B.
+ *   workspace: 4-byte aligned, pivlfn_template_match_workspace_bytes(th, tw) bytes (0 for arguments out of range).  Two launches.
+ *   A workgroup stages (15 + th) rows of 64 + 4*ceil(tw/4) bytes: a template for which that exceeds 160 KiB (255 x 255 fits) is refused.
+ *
+ * pivlfn_target_points -- r [B,H,W] fp32 -> labels [B,H,W] int32, count [B] int32, rec [B,cap,4] int64.
+ *   1. q = (integer) rint(min((double)r, 8192.0) * 65536.0) where r > threshold (strict, compared in fp32; a NaN is not kept), else 0.
+ *      q <= 2^29 whatever r holds (+inf included), so the sum of four below is at most 2^31.
+ *   2. w(y,x) = q(y-1,x-1) + q(y-1,x) + q(y,x-1) + q(y,x), index -1 reflected to +1 (to 0 on an axis of length 1): the window of
+ *      cv2.blur(res, (2, 2)) at its default anchor (BORDER_REFLECT_101) without the division by 4.  An exact 32-bit integer.
+ *   3. labels: the 4-connected components of w > 0 (ndimage.label's default structure); a pixel's label is the smallest row-major
+ *      index y*W + x of its component, -1 where w == 0.
+ *   4. count[b] = the number of components, whatever cap is.  rec[b][k] for k < min(count[b], cap) belongs to the component with the
+ *      k-th smallest label: (sum w, sum w*x, sum w*y, number of pixels) as 64-bit integers (sums modulo 2^64; r <= 1 stays far from
+ *      that).  rec[b][k] for count[b] <= k < cap is zero.  Integer atomics: the bits do not depend on the order of arrival.
+ *   The centre of mass of findLocalMax is (rec[1]/rec[0], rec[2]/rec[0]); it carries the (+0.5, +0.5) of the one-sided window.
+ *   workspace: 4-byte aligned, pivlfn_target_points_workspace_bytes(B, H, W) bytes;  rec 8-byte aligned;  1 <= cap <= 2^24.  Six launches.
+ *
+ * pivlfn_dewarp_frames -- frames, out [B,H,W] bytes (is_f32 = 0) or fp32 (is_f32 = 1); A: HOST, 24 doubles, read during the call.
+ *   For output pixel (x, y), u = x - x0, v = y - y0, all in fp64, each operation rounded on its own, in numpy's order for nl_trans:
+ *       P(k) = ((((A[k]*u + A[k+1]*v) + A[k+2]) + A[k+3]*(u*u)) + A[k+4]*(v*v)) + (A[k+5]*u)*v
+ *       sx = P(0)/P(6) + x0;   sy = P(12)/P(18) + y0.
+ *   PIVLFN_DEWARP_NEAREST: (rx, ry) = rint of each (half to even, np.round); out = frames[ry][rx] if 0 <= rx <= W-1 and 0 <= ry <= H-1,
+ *   else fill.  PIVLFN_DEWARP_BILINEAR: fx = floor(sx), fy = floor(sy), ax = sx - fx, ay = sy - fy; if the four taps (fx, fy) ..
+ *   (fx+1, fy+1) all lie inside the image,
+ *       top = (1-ax)*I[fy][fx] + ax*I[fy][fx+1];  bot = (1-ax)*I[fy+1][fx] + ax*I[fy+1][fx+1];  val = (1-ay)*top + ay*bot
+ *   (fp64), stored as (float)val or as rint(val) clamped to 0..255; else fill.  A non-finite source position gives fill.
+ *   fill: (float)fill, finite and within the fp32 range or a NaN; for bytes an integer 0..255.  One launch.  out must not be frames.
+ *   On a square image whose sources all fall inside, NEAREST is the reference's warp (dewarp.py:196-252).  Two deliberate differences:
+ *   the reference swaps width and height on non-square images (`width, height = gray_img.shape`), and it maps out-of-range sources to
+ *   the LAST pixel (dewarp.py:235-236) although its comment says they are painted black; here they get `fill`.
+ *
+ * Errors (PIVLFN_ERR_ARG, before any launch): a null pointer;  B outside 1..65535;  H or W < 1;  H*W >= 2^31 - 256;  an even or
+ * oversized template;  cap out of range;  a NaN threshold;  a misaligned or short workspace;  a non-finite coefficient or origin;  a
+ * fill that the frame type cannot hold;  an unknown mode. */
+#define PIVLFN_DEWARP_NEAREST  0
+#define PIVLFN_DEWARP_BILINEAR 1
+size_t pivlfn_template_match_workspace_bytes(int th, int tw);
+int pivlfn_template_match(const unsigned char *images, const unsigned char *templ, float *r, int B, int H, int W, int th, int tw,
+                          void *workspace, size_t workspace_bytes, void *stream);
+size_t pivlfn_target_points_workspace_bytes(int B, int H, int W);
+int pivlfn_target_points(const float *r, int B, int H, int W, float threshold, int cap, int *labels, int *count, long long *rec,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int pivlfn_dewarp_frames(const void *frames, void *out, int is_f32, int B, int H, int W, const double *A, double x0, double y0,
+                         int mode, double fill, void *stream);
+
 /* ---- network: replaces LiteFlowNet.__init__ + load_state_dict (src/models.py:39-317, 736-738, 762-764).
  * Uploads and repacks the weights once (this is the only call that allocates device memory).
  * starting_scale / lowest_level / rgb_mean as in the factories src/models.py:729-730, 754-755. */

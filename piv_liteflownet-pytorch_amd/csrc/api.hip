@@ -316,6 +316,28 @@ int pivlfn_snapshot_project(const float *X, int n, long P, long ldx, const doubl
     return launch_snapshot_project(X, n, P, ldx, Wt, K, out, (hipStream_t)stream);
 }
 
+size_t pivlfn_template_match_workspace_bytes(int th, int tw) { return template_match_workspace_bytes(th, tw); }
+
+int pivlfn_template_match(const unsigned char *images, const unsigned char *templ, float *r, int B, int H, int W, int th, int tw,
+                          void *workspace, size_t workspace_bytes, void *stream)
+{
+    return launch_template_match(images, templ, r, B, H, W, th, tw, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t pivlfn_target_points_workspace_bytes(int B, int H, int W) { return target_points_workspace_bytes(B, H, W); }
+
+int pivlfn_target_points(const float *r, int B, int H, int W, float threshold, int cap, int *labels, int *count, long long *rec,
+                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    return launch_target_points(r, B, H, W, threshold, cap, labels, count, rec, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int pivlfn_dewarp_frames(const void *frames, void *out, int is_f32, int B, int H, int W, const double *A, double x0, double y0,
+                         int mode, double fill, void *stream)
+{
+    return launch_dewarp_frames(frames, out, is_f32, B, H, W, A, x0, y0, mode, fill, (hipStream_t)stream);
+}
+
 int pivlfn_create(const pivlfn_tensor *tensors, int n_tensors, float starting_scale, int lowest_level,
                   const float rgb_mean[6], pivlfn_net **out)
 {

@@ -332,6 +332,16 @@ int launch_pressure_setup(const double *g, const unsigned char *valid, int F, in
 int launch_pressure_cg(void *ws, size_t ws_bytes, int F, int h, int w, double tol, int iters, hipStream_t st);
 int launch_pressure_read(const void *ws, size_t ws_bytes, int F, int h, int w, double *p, unsigned char *flag, double *status, hipStream_t st);
 
+// ---- stereo calibration (calibrate.hip): template matching, marker centres of the correlation map, image dewarp -------------------------
+size_t template_match_workspace_bytes(int th, int tw);
+int launch_template_match(const unsigned char *images, const unsigned char *templ, float *r, int B, int H, int W, int th, int tw,
+                          void *ws, size_t ws_bytes, hipStream_t st);
+size_t target_points_workspace_bytes(int B, int H, int W);
+int launch_target_points(const float *r, int B, int H, int W, float threshold, int cap, int *labels, int *count, long long *rec,
+                         void *ws, size_t ws_bytes, hipStream_t st);
+int launch_dewarp_frames(const void *frames, void *out, int is_f32, int B, int H, int W, const double *A, double x0, double y0, int mode,
+                         double fill, hipStream_t st);
+
 // ---- image pre-processing (preproc.hip): [n,H,W,3] uint8 frames -> background minimum [H,W,3], network input [n,3,H,W] fp32 --------
 int launch_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, hipStream_t st);
 int launch_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W, int k, int floor,

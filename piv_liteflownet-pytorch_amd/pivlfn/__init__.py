@@ -19,6 +19,8 @@ from .pod import FlowPOD, PODResult                                     # noqa: 
 from .twopoint import TwoPointResult, TwoPointStats                     # noqa: F401
 from .spectrum import TemporalSpectrum, TemporalSpectrumResult          # noqa: F401
 from .pressure import PressureField, PressureResult                     # noqa: F401
+from .calibrate import (calibrate_camera, dewarp_frames, find_markers, fit_mapping, gen_template, index_lattice,  # noqa: F401
+                        target_points, template_match, write_coeff)
 from .particles import BAD, PairParticles, ParticleImageGen, ParticleImages, displace_particles, render_particles  # noqa: F401
 from .viz import (PngWriter, color_wheel_image, decimate_flow, field_absmax, flow_maxrad, flow_to_color, motion_to_color,  # noqa: F401
                   quiver_plot, scalar_to_color, vorticity_image, write_png, write_png_gray, GrayPngWriter)
@@ -30,4 +32,5 @@ __all__ = ["FunctionCorrelation", "ModuleCorrelation", "LiteFlowNet", "LiteFlowN
            "write_png", "PngWriter", "write_png_gray", "GrayPngWriter", "match_quality", "MatchQuality", "FEW", "FLAT", "NO_PEAK", "CENTRE_OUT",
            "vortex_gamma", "VortexField", "FlowMap", "FTLEField", "OUT", "LOST", "UNDEFINED", "FlowPOD", "PODResult", "TwoPointStats", "TwoPointResult",
            "TemporalSpectrum", "TemporalSpectrumResult", "PressureField", "PressureResult",
-           "ParticleImageGen", "ParticleImages", "PairParticles", "displace_particles", "render_particles", "BAD"]
+           "gen_template", "template_match", "target_points", "find_markers", "index_lattice", "fit_mapping", "dewarp_frames", "calibrate_camera",
+           "write_coeff", "ParticleImageGen", "ParticleImages", "PairParticles", "displace_particles", "render_particles", "BAD"]

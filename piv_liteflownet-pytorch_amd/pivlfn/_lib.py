@@ -83,6 +83,13 @@ SIGNATURES = {
                                             ctypes.c_size_t, ctypes.c_void_p]),
     "pivlfn_snapshot_project": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_int,
                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "pivlfn_template_match_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "pivlfn_template_match": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "pivlfn_target_points_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "pivlfn_target_points": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 4
+                             + [ctypes.c_size_t, ctypes.c_void_p]),
+    "pivlfn_dewarp_frames": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_double)]
+                             + [ctypes.c_double] * 2 + [ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
     "pivlfn_create": (ctypes.c_int, [ctypes.POINTER(Tensor), ctypes.c_int, ctypes.c_float, ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_void_p)]),
     "pivlfn_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "pivlfn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_void_p] + [ctypes.c_int] * 3),

@@ -5,6 +5,7 @@
   python tools/bench_ops.py twopoint                                  (pivlfn_twopoint_accumulate against its HBM and fp64 bounds)
   python tools/bench_ops.py spectrum                                  (pivlfn_spectrum_accumulate, and the same sums from snapshot_project + torch)
   python tools/bench_ops.py pressure                                  (pivlfn_pressure_cg: us per iteration at 256^2 x 8 and 1024^2 x 1)
+  python tools/bench_ops.py calibrate                                 (pivlfn_template_match, _target_points, _dewarp_frames at --size squared)
 Times N back-to-back launches between two events on the current stream (so each figure includes one ~1.5 us
 kernel boundary) and checks that all variants agree.
 """
@@ -545,9 +546,59 @@ def bench_pressure_wall(dev):
         print(f"sync_every={sync_every}: one frame per update, {dt * 1e3 / 8:.2f} ms per frame", flush=True)
 
 
+INT_MAC_PER_S = 256 * 4 * 32 * 4 * 2.4e9      # 1024 SIMDs x 32 lanes per cycle x 4 MACs of a v_dot4_u32_u8 x 2.4 GHz
+
+
+def bench_calibrate(args):
+    """The three entry points of csrc/calibrate.hip at 1 x --size squared (DESIGN quotes --size 2048) with the 25 x 25 cross
+    template, on the production library.  template_match against the integer-MAC bound 3 N H W (I.T, I.I and I.1 per tap) at the
+    v_dot4_u32_u8 rate; dewarp_frames against its byte bound (one read and one write of the frame) at the HBM peak; target_points (six
+    launches) on the correlation map of a rendered cross lattice, as a time alone."""
+    import ctypes
+    import numpy as np
+    from pivlfn import _lib, calibrate as cal
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    S = args.size
+    templ = cal.gen_template(11, 25, 25)
+    yy, xx = np.meshgrid(np.arange(S), np.arange(S), indexing="ij")
+    dx, dy = (xx % 48) - 24, (yy % 48) - 24
+    image = np.where(((abs(dx) <= 12) & (abs(dy) <= 5)) | ((abs(dx) <= 5) & (abs(dy) <= 12)), 255, 0).astype(np.uint8)
+    img, t = torch.from_numpy(image[None]).to(dev), torch.from_numpy(templ).to(dev)
+    r = torch.empty(1, S, S, device=dev)
+    nws = lib.pivlfn_template_match_workspace_bytes(25, 25)
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    n, med = time_it(lambda: _lib.check(lib.pivlfn_template_match(img.data_ptr(), t.data_ptr(), r.data_ptr(), 1, S, S, 25, 25, ws.data_ptr(), nws, st)),
+                     n=20, rounds=7)
+    bound = 3.0 * 625 * S * S / INT_MAC_PER_S * 1e6
+    print(f"template_match 1x{S}x{S}, 25x25: min {n:8.1f} us, median {med:8.1f} us (2 launches); integer-MAC bound {bound:7.1f} us = "
+          f"{100 * bound / med:5.1f} % of the time", flush=True)
+    cap = 4096
+    nws2 = lib.pivlfn_target_points_workspace_bytes(1, S, S)
+    ws2 = torch.empty(nws2, dtype=torch.uint8, device=dev)
+    labels, count = torch.empty(1, S, S, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    rec = torch.empty(1, cap, 4, dtype=torch.int64, device=dev)
+    n, med = time_it(lambda: _lib.check(lib.pivlfn_target_points(r.data_ptr(), 1, S, S, 0.7, cap, labels.data_ptr(), count.data_ptr(), rec.data_ptr(),
+                                                                 ws2.data_ptr(), nws2, st)), n=20, rounds=7)
+    print(f"target_points 1x{S}x{S}: min {n:8.1f} us, median {med:8.1f} us (6 launches); {int(count[0])} components", flush=True)
+    A = np.zeros(24)
+    A[[0, 8, 13, 20]] = 1.0
+    A[[1, 6, 7, 12, 18, 19]] = (0.02, 2e-5, -1e-5, -0.015, 1e-5, 2e-5)
+    a_c = (ctypes.c_double * 24)(*A.tolist())
+    for f32, mode in ((0, 0), (0, 1), (1, 0), (1, 1)):
+        src = torch.rand(1, S, S, device=dev) if f32 else img
+        out = torch.empty_like(src)
+        n, med = time_it(lambda: _lib.check(lib.pivlfn_dewarp_frames(src.data_ptr(), out.data_ptr(), f32, 1, S, S, a_c, S / 2.0, S / 2.0, mode, 0.0, st)),
+                         n=20, rounds=7)
+        bound = 2.0 * S * S * (4 if f32 else 1) / HBM_BYTES_PER_S * 1e6
+        print(f"dewarp_frames 1x{S}x{S} {'f32' if f32 else 'u8 '} {'bilinear' if mode else 'nearest '}: min {n:8.1f} us, median {med:8.1f} us; "
+              f"byte bound {bound:6.2f} us = {100 * bound / med:5.1f} % of the time", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate", "twopoint", "spectrum", "pressure"])
+    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate", "twopoint", "spectrum", "pressure", "calibrate"])
     ap.add_argument("--once", action="store_true", help="preproc: one launch per shape, for a kernel trace")
     ap.add_argument("--filter", default="")
     ap.add_argument("--tune3", type=int, default=0, help="ablation mask of the fp16 conv kernel (pivlfn_tune(3, mask))")
@@ -561,4 +612,5 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=8, help="interleaved timing rounds per variant (warp_corr)")
     a = ap.parse_args()
     {"conv_stamps": bench_conv_stamps, "warp_corr": bench_warp_corr, "wc_ablate": bench_wc_ablate, "conv": bench_conv, "head": bench_head,
-     "preproc": bench_preproc, "evaluate": bench_evaluate, "twopoint": bench_twopoint, "spectrum": bench_spectrum, "pressure": bench_pressure}[a.what](a)
+     "preproc": bench_preproc, "evaluate": bench_evaluate, "twopoint": bench_twopoint, "spectrum": bench_spectrum, "pressure": bench_pressure,
+     "calibrate": bench_calibrate}[a.what](a)
