@@ -1,0 +1,266 @@
+"""The host-side launch plans of the analysis kernels, restated, and the shapes at which they change.  A helper, not a test:
+tests/test_analysis_plans.py holds it to the sources (the constexpr values below are read back out of the .hip text) and shows that every
+case crosses the branch it is named for; the tests/test_gpu_*.py of each op take their large shapes from the lists at the end.
+
+Every analysis entry point of include/pivlfn.h, the size steps of its launcher, and the test that reaches each.  A later kernel gets a
+line here, and a case where its plan has a step.
+
+  pivlfn_pressure_gradient        none: one thread per node, a flat grid.
+  pivlfn_pressure_setup / _cg / _read   NB = ceil(N / (chunks * 1024)) block partials per frame; NB > 256 puts partials into a second wave
+                                  of pr_finish, NB > 1024 into its second chunk, N > 2^21 starts the PrCounter (chunks = 2), N > 2^22
+                                  carries in it (chunks = 4).  PRESSURE_CASES, test_gpu_pressure.py::test_bits_where_the_partials_plan_changes.
+  pivlfn_template_match           none in H, W (64 x 16 tiles, a flat 3-D grid); the template steps the packed row length and, from
+                                  64 KiB of LDS on, the opt-in attribute: test_gpu_calibrate.py::test_match_reaches_the_32_bit_headroom
+                                  (255 x 255) and the 25 x 25 / 5 x 5 cases of test_match_bits_of_the_restatement.
+  pivlfn_target_points            nblk = ceil(HW / 256) blocks; tp_scan_kernel gives per = ceil(nblk / 256) of them to a thread:
+                                  per = 2 from HW > 65536.  TARGET_POINTS_CASES, test_gpu_calibrate.py::test_points_where_the_scan_plan_changes.
+  pivlfn_dewarp_frames            none: one thread per pixel, grid (ceil(HW / 256), B), no cap.
+  pivlfn_twopoint_accumulate      slots = ceil((R + 1) / (4 z)) separations per wave, z = min(ceil(4096 / H), ceil((R + 1) / 4)):
+                                  slots = 2 from H = 66 at R = 255; chunks = 2^levels / 256 of a row: 4 from W = 513, 64 at W = 16384.
+                                  TWOPOINT_CASES, test_gpu_twopoint.py::test_bits_where_the_plan_changes.
+  pivlfn_spectrum_accumulate      bounded domain (L <= 1024, K <= 513): ceil(L / 128) staged chunks, ceil((K // 8) / 8) rounds, K % 8
+                                  singles.  SPECTRUM_CASES (the corner L = 1024, K = 513) in test_gpu_spectrum.py::test_bits_of_the_restatement.
+  pivlfn_vortex_gamma             vortex_stage_kernel: grid min(ceil(HW / 256), max(16384 / B, 64)) per frame, a grid-stride loop above;
+                                  vortex_window_kernel: flat.  VORTEX_CASES, test_gpu_vortex.py::test_bits_where_the_stage_grid_is_capped.
+  pivlfn_match_quality            quality_warp_kernel: the same cap as the vortex stage; quality_window_kernel: flat.  QUALITY_CASES,
+                                  test_gpu_quality.py::test_bits_where_the_warp_grid_is_capped.
+  pivlfn_stereo_2d3c              the same cap.  STEREO_CASES in test_gpu_stereo.py::test_kernel_matches_restatement_random (its
+                                  1024 x 1024 case has 4096 blocks, below the cap of 16384).
+  pivlfn_field_absmax             grid min(ceil(HW / 256), 256) per image.  VIZ_ABSMAX_CASES, test_gpu_viz.py::test_field_absmax_where_the_grid_is_capped.
+  pivlfn_flow_maxrad              grid min(ceil(ceil(HW / 4) / 256), 256) per image.  VIZ_MAXRAD_CASES,
+                                  test_gpu_viz.py::test_flow_maxrad_and_its_picture_where_the_grid_is_capped.
+  pivlfn_flow_to_color, pivlfn_scalar_to_color   grid min(ceil(ceil(B HW / 4) / 256), VZ_MAX_BLOCKS) over the batch.  VIZ_COLOR_CASES,
+                                  test_gpu_viz.py::test_pictures_and_cell_means_where_the_grid_is_capped.
+  pivlfn_flow_decimate            grid min(ceil(cells / 256), VZ_MAX_BLOCKS) over the batch.  VIZ_COLOR_CASES at cell 1, the same test.
+  pivlfn_particles_displace       none: one thread per particle, a flat grid.
+  pivlfn_particles_render         tiles = B ceil(H / 16) ceil(W / 16); particles_offsets_kernel: a wave prefix (> 64 tiles: a second wave,
+                                  > 256: a second workgroup) and one atomic cursor; a tile's list beyond REN_CAP is ordered window by
+                                  window.  PARTICLES_CASES, test_gpu_particles.py::test_seedings_of_many_tiles.
+  pivlfn_flowmap_advect / _seed / _ftle   none: one thread per particle or node, flat grids
+                                  (test_gpu_flowmap.py::test_particle_lists has 257 particles: a second block).
+  pivlfn_snapshot_gram            n = 1985 is the first n whose plan walks all slabs in one workgroup:
+                                  test_gpu_pod.py::test_gram_of_many_snapshots_adds_its_slabs_itself.
+  pivlfn_snapshot_project         none in P (flat); K picks the kernel: K <= 4, <= 16, <= 64.  test_gpu_pod.py::
+                                  test_project_equals_the_sequential_loop has K = 1, 3 | 5, 16 | 17, 64 (PROJECT_CASES adds 5 and 16).
+  pivlfn_flow_fields, pivlfn_flow_stats_accumulate(_masked), pivlfn_flow_validate, pivlfn_frames_preprocess (scale),
+  pivlfn_error_stats_accumulate   the cap max(16384 / B, 64) (16384 for the accumulators) of blocks of 256 pixels per frame.  Their largest
+                                  cases are 1024 x 1024 at B <= 5: 4096 blocks (1024 for the vectorised pre-processing), which is BELOW the cap of
+                                  16384 / 3 = 5461, so their grid-stride loops run once in every test so far.  Not part of this list yet.
+  pivlfn_frames_background_min, pivlfn_frames_preprocess (min-max), pivlfn_flow_errors, pivlfn_level_errors   tiles, flat grids; the second
+                                  pass of pivlfn_flow_errors from 32 x 32 tiles: test_gpu_evaluate.py, the 1024 x 1024 cases.
+"""
+import os
+import re
+from collections import namedtuple
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "piv_liteflownet-pytorch_amd", "csrc")
+
+# the constexpr values the formulas below depend on, per source file; tests/test_analysis_plans.py reads them back out of the text
+CONSTANTS = {
+    "pressure.hip": {"PR_THREADS": 256, "PR_OWN": 4, "PR_CHUNK": 1024, "PR_MAX_PART": 2048},
+    "calibrate.hip": {"TP_BLOCK": 256},
+    "twopoint.hip": {"TP_WAVES": 4, "TP_CHUNK": 256, "TP_SLOT": 16},
+    "viz.hip": {"VZ_THREADS": 256, "VZ_MAX_BLOCKS": 4096},
+    "particles.hip": {"REN_TILE": 16, "REN_CAP": 2048},
+    "spectrum.hip": {"SP_TC": 128, "SP_KG": 8, "SP_WAVES": 8, "SP_TILE": 64},
+}
+PR_THREADS, PR_OWN, PR_CHUNK, PR_MAX_PART = (CONSTANTS["pressure.hip"][k] for k in ("PR_THREADS", "PR_OWN", "PR_CHUNK", "PR_MAX_PART"))
+TP_BLOCK = CONSTANTS["calibrate.hip"]["TP_BLOCK"]
+TP_WAVES, TP_CHUNK, TP_SLOT = (CONSTANTS["twopoint.hip"][k] for k in ("TP_WAVES", "TP_CHUNK", "TP_SLOT"))
+VZ_THREADS, VZ_MAX_BLOCKS = CONSTANTS["viz.hip"]["VZ_THREADS"], CONSTANTS["viz.hip"]["VZ_MAX_BLOCKS"]
+REN_TILE, REN_CAP = CONSTANTS["particles.hip"]["REN_TILE"], CONSTANTS["particles.hip"]["REN_CAP"]
+SP_TC, SP_KG, SP_WAVES, SP_TILE = (CONSTANTS["spectrum.hip"][k] for k in ("SP_TC", "SP_KG", "SP_WAVES", "SP_TILE"))
+
+
+def source_constants(name):
+    """Every `constexpr int|unsigned NAME = <integer expression of literals and earlier names>` of csrc/<name>, evaluated."""
+    text = open(os.path.join(CSRC, name)).read()
+    found = {}
+    for stmt in re.findall(r"^constexpr\s+(?:int|unsigned)\s+([^;{]+);", text, re.M):
+        for part in stmt.split(","):
+            m = re.fullmatch(r"\s*(\w+)\s*=\s*([\w\s*+\-/()]+?)\s*", part)
+            if not m:
+                continue
+            try:
+                found[m.group(1)] = int(eval(m.group(2).replace("/", "//"), {"__builtins__": {}}, dict(found)))       # noqa: S307
+            except (NameError, SyntaxError):
+                pass                                       # defined by a macro of the header: not one this module uses
+    return found
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def pow2_at_least(n):
+    p = 1
+    while p < n:
+        p *= 2
+    return p
+
+
+# ---- the plans ------------------------------------------------------------------------------------------------------------------------
+def pressure(h, w):
+    """pr_layout of csrc/pressure.hip: chunks per workgroup and block partials per frame."""
+    N = h * w
+    P2 = pow2_at_least(N)
+    chunks = P2 // (PR_CHUNK * PR_MAX_PART) if P2 > PR_CHUNK * PR_MAX_PART else 1
+    tile = chunks * PR_CHUNK
+    return {"N": N, "chunks": chunks, "NB": cdiv(N, tile)}
+
+
+def pressure_offset_b(F, h, w):
+    """What pivlfn_pressure_workspace_offset(F, h, w, PIVLFN_PRESSURE_WS_B) returns: two 64-byte records and three partials per frame."""
+    return 128 * F + 24 * pressure(h, w)["NB"] * F
+
+
+def tp_scan(H, W):
+    """tp_scan_kernel of csrc/calibrate.hip: blocks of the image, blocks per thread, and the threads whose range is short or empty."""
+    nblk = cdiv(H * W, TP_BLOCK)
+    per = cdiv(nblk, 256)
+    ranges = [(min(t * per, nblk), min(min(t * per, nblk) + per, nblk)) for t in range(256)]
+    return {"nblk": nblk, "per": per, "short": [t for t, (lo, hi) in enumerate(ranges) if 0 < hi - lo < per],
+            "empty": [t for t, (lo, hi) in enumerate(ranges) if hi == lo]}
+
+
+def twopoint(H, W, R):
+    """launch_twopoint_accumulate of csrc/twopoint.hip."""
+    levels = 0
+    while (1 << levels) < W:
+        levels += 1
+    chunks = (1 << levels) // TP_CHUNK if (1 << levels) > TP_CHUNK else 1
+    z = min(cdiv(4096, H), cdiv(R + 1, TP_WAVES))
+    slots = cdiv(R + 1, TP_WAVES * z)
+    return {"levels": levels, "chunks": chunks, "z": z, "slots": slots, "lds": TP_WAVES * slots * TP_SLOT * 8}
+
+
+def capped_frame_grid(B, H, W):
+    """vortex_stage_kernel, quality_warp_kernel and stereo_2d3c_kernel: blocks of 256 pixels per frame, capped at max(16384 / B, 64)."""
+    g = cdiv(H * W, 256)
+    cap = max(16384 // B, 64)
+    return {"blocks": g, "cap": cap, "grid": min(g, cap), "visits": cdiv(g, min(g, cap))}
+
+
+def viz_blocks(items):
+    g = cdiv(items, VZ_THREADS)
+    return min(g, VZ_MAX_BLOCKS) if g else 1
+
+
+def viz_absmax(H, W):
+    g = cdiv(H * W, VZ_THREADS)
+    return {"blocks": g, "grid": min(viz_blocks(H * W), 256), "sweep": min(viz_blocks(H * W), 256) * VZ_THREADS}
+
+
+def viz_maxrad(H, W):
+    groups = cdiv(H * W, 4)
+    return {"blocks": cdiv(groups, VZ_THREADS), "grid": min(viz_blocks(groups), 256), "sweep": min(viz_blocks(groups), 256) * VZ_THREADS * 4}
+
+
+def viz_color(B, H, W):
+    """flow_to_color and scalar_to_color (groups of four pixels over the batch) and flow_decimate at cell 1 (one cell a thread)."""
+    npix = B * H * W
+    groups = cdiv(npix, 4)
+    return {"blocks": cdiv(groups, VZ_THREADS), "grid": viz_blocks(groups), "sweep": viz_blocks(groups) * VZ_THREADS * 4,
+            "decimate_blocks": cdiv(npix, VZ_THREADS), "decimate_grid": viz_blocks(npix)}
+
+
+def particles_tiles(B, H, W):
+    tiles = B * cdiv(H, REN_TILE) * cdiv(W, REN_TILE)
+    return {"tiles": tiles, "waves": cdiv(tiles, 64), "workgroups": cdiv(tiles, 256)}
+
+
+def spectrum(L, K):
+    nfull, nsingle = K // SP_KG, K % SP_KG
+    return {"chunks": cdiv(L, SP_TC), "groups": nfull, "singles": nsingle, "rounds": cdiv(nfull, SP_WAVES) if nfull else 1}
+
+
+# ---- the cases ------------------------------------------------------------------------------------------------------------------------
+# shape: what the GPU test is parametrised with; branch: why the case exists; crosses: the plan of `shape` -> whether it is there
+Case = namedtuple("Case", "shape branch plan crosses")
+
+
+def _case(shape, branch, plan, crosses):
+    return Case(shape, branch, plan, crosses)
+
+
+PRESSURE_CASES = [          # (h, w), one frame; three iterations each (the restatement of 2048 x 2049 takes about a second an iteration)
+    _case((513, 512), "NB = 257: a partial in the second wave of pr_finish", pressure, lambda p: p["NB"] == 257 and p["chunks"] == 1),
+    _case((1024, 1025), "NB = 1025: the second chunk of pr_finish holds one partial", pressure,
+          lambda p: p["NB"] == PR_CHUNK + 1 and p["chunks"] == 1),
+    _case((2048, 1025), "chunks = 2: PrCounter level 0", pressure, lambda p: p["chunks"] == 2 and p["NB"] == 1025 and p["NB"] <= PR_MAX_PART),
+    _case((2048, 2049), "chunks = 4: a carry in PrCounter", pressure, lambda p: p["chunks"] == 4 and p["NB"] == 1025 and p["NB"] <= PR_MAX_PART),
+]
+
+TARGET_POINTS_CASES = [     # (H, W)
+    _case((257, 256), "per = 2, only thread 128 has a short range", tp_scan,
+          lambda p: p["nblk"] == 257 and p["per"] == 2 and p["per"] * 256 > p["nblk"] and p["short"] == [128] and p["empty"][0] == 129),
+    _case((349, 513), "per = 3, threads from 234 on are empty", tp_scan,
+          lambda p: p["nblk"] == 700 and p["per"] == 3 and p["per"] * 256 > p["nblk"] and p["short"] == [233] and p["empty"][0] == 234),
+    _case((1024, 1280), "the workload's size: per = 20", tp_scan, lambda p: p["nblk"] == 5120 and p["per"] == 20 and not p["empty"]),
+]
+
+TWOPOINT_CASES = [          # (H, W, R, step), B = 2
+    _case((66, 300, 255, 1), "slots = 2", lambda H, W, R, s: twopoint(H, W, R), lambda p: p["slots"] == 2 and p["z"] == 63),
+    _case((4096, 5, 255, 1), "z = 1, slots = 64: the largest LDS request", lambda H, W, R, s: twopoint(H, W, R),
+          lambda p: p["z"] == 1 and p["slots"] == 64 and p["lds"] == 32768),
+    _case((1024, 40, 64, 1), "the workload's z = 4, slots = 5", lambda H, W, R, s: twopoint(H, W, R), lambda p: p["z"] == 4 and p["slots"] == 5),
+    _case((5, 520, 8, 1), "4 chunks: counter level 1", lambda H, W, R, s: twopoint(H, W, R), lambda p: p["chunks"] == 4),
+    _case((3, 1030, 8, 3), "8 chunks: counter level 2", lambda H, W, R, s: twopoint(H, W, R), lambda p: p["chunks"] == 8),
+    _case((2, 16384, 4, 1), "64 chunks: every counter register", lambda H, W, R, s: twopoint(H, W, R), lambda p: p["chunks"] == 64 and p["levels"] == 14),
+]
+
+_over_the_cap = lambda p: p["blocks"] > p["cap"] and p["grid"] == p["cap"] and p["visits"] == 2      # noqa: E731
+VORTEX_CASES = [            # (B, H, W, radius, spacing)
+    _case((260, 130, 128, 2, 1), "65 blocks a frame, capped at 64", lambda B, H, W, r, s: capped_frame_grid(B, H, W),
+          lambda p: _over_the_cap(p) and p["cap"] == 64 and p["blocks"] == 65),
+    _case((1, 2049, 2048, 1, 1), "16392 blocks, capped at 16384", lambda B, H, W, r, s: capped_frame_grid(B, H, W),
+          lambda p: _over_the_cap(p) and p["cap"] == 16384),
+]
+QUALITY_CASES = [           # (B, H, W, radius)
+    _case((260, 130, 128, 1), "65 blocks a frame, capped at 64", lambda B, H, W, r: capped_frame_grid(B, H, W),
+          lambda p: _over_the_cap(p) and p["cap"] == 64),
+]
+STEREO_CASES = [            # (B, h, w)
+    _case((260, 130, 128), "65 blocks a pair, capped at 64", capped_frame_grid, lambda p: _over_the_cap(p) and p["cap"] == 64),
+    _case((1, 2049, 2048), "16392 blocks, capped at 16384", capped_frame_grid, lambda p: _over_the_cap(p) and p["cap"] == 16384),
+]
+
+VIZ_ABSMAX_CASES = [        # (B, H, W)
+    _case((1, 257, 256), "257 blocks, capped at 256: one block comes round again", lambda B, H, W: viz_absmax(H, W),
+          lambda p: p["blocks"] == 257 and p["grid"] == 256),
+    _case((2, 1024, 1024), "4096 blocks an image on a grid of 256: sixteen visits", lambda B, H, W: viz_absmax(H, W),
+          lambda p: p["blocks"] == 16 * p["grid"] and p["grid"] == 256),
+]
+VIZ_MAXRAD_CASES = [        # (B, H, W)
+    _case((1, 513, 512), "257 blocks of 4-pixel groups, capped at 256", lambda B, H, W: viz_maxrad(H, W),
+          lambda p: p["blocks"] == 257 and p["grid"] == 256),
+]
+VIZ_COLOR_CASES = [         # (B, H, W)
+    _case((5, 1024, 1024), "5120 blocks over the batch, capped at VZ_MAX_BLOCKS", viz_color,
+          lambda p: p["blocks"] == 5120 and p["grid"] == VZ_MAX_BLOCKS and p["decimate_blocks"] > p["decimate_grid"] == VZ_MAX_BLOCKS),
+    _case((1, 2049, 2048), "4098 blocks, two over VZ_MAX_BLOCKS", viz_color,
+          lambda p: p["blocks"] == VZ_MAX_BLOCKS + 2 and p["grid"] == VZ_MAX_BLOCKS and p["decimate_grid"] == VZ_MAX_BLOCKS),
+]
+
+PARTICLES_CASES = [         # (B, H, W), about 0.05 particles per pixel
+    _case((1, 16, 1040), "65 tiles: a second wave of the offsets", particles_tiles, lambda p: p["tiles"] == 65 and p["waves"] == 2 and p["workgroups"] == 1),
+    _case((1, 16, 4112), "257 tiles: a second workgroup of the offsets", particles_tiles, lambda p: p["tiles"] == 257 and p["workgroups"] == 2),
+    _case((2, 272, 256), "544 tiles over two images: three workgroups", particles_tiles, lambda p: p["tiles"] == 544 and p["workgroups"] == 3),
+]
+
+SPECTRUM_CASES = [          # (L, N, K, first, pad)
+    _case((1024, 65, 513, 1000, 1), "the corner of the domain: 8 chunks re-staged in each of 8 rounds, one single", lambda L, N, K, f, p: spectrum(L, K),
+          lambda p: p == {"chunks": 8, "groups": 64, "singles": 1, "rounds": 8}),
+    _case((1000, 64, 501, 0, 0), "a short last chunk, a ragged last round, five singles", lambda L, N, K, f, p: spectrum(L, K),
+          lambda p: p["chunks"] == 8 and 1000 % SP_TC and p["groups"] == 62 and p["groups"] % SP_WAVES and p["singles"] == 5 and p["rounds"] == 8),
+]
+
+PROJECT_CASES = [(9, 5, 70), (9, 16, 300)]              # (n, K, P): the first and the last K of project_kernel<16>
+
+ALL_CASES = {"pressure": PRESSURE_CASES, "target_points": TARGET_POINTS_CASES, "twopoint": TWOPOINT_CASES, "vortex": VORTEX_CASES,
+             "quality": QUALITY_CASES, "stereo": STEREO_CASES, "field_absmax": VIZ_ABSMAX_CASES, "flow_maxrad": VIZ_MAXRAD_CASES,
+             "viz_color": VIZ_COLOR_CASES, "particles": PARTICLES_CASES, "spectrum": SPECTRUM_CASES}
+
+
+def shapes(cases):
+    return [c.shape for c in cases]

@@ -190,6 +190,50 @@ def test_more_components_than_cap(dev):
     assert cr.same_bits(got[2][1], full[2][1, :5])                               # the first cap records are the first of all
 
 
+def marker_map(H, W, seed, n):
+    """A quiet map with n blobs of 3 x 3 to 5 x 5 pixels above 0.7 at random places, one long thin component (a row and a column that
+    cross) through many blocks of 256 pixels, and a single pixel in the last row: a component whose root lies in the last block."""
+    rng = np.random.default_rng(seed)
+    r = (0.5 * rng.random((H, W))).astype(np.float32)
+    for _ in range(n):
+        s = int(rng.integers(3, 6))
+        y, x = int(rng.integers(0, H - s + 1)), int(rng.integers(0, W - s + 1))
+        r[y:y + s, x:x + s] = (0.75 + 0.2 * rng.random((s, s))).astype(np.float32)
+    r[H // 2, 3:W - 3] = 0.9
+    r[5:H - 5, W // 3] = 0.85
+    r[H - 3:, W - 10:W - 1] = 0.1
+    r[H - 1, W - 6] = 0.9
+    return r
+
+
+def _scan_shapes():
+    import analysis_plans as ap
+    return ap.shapes(ap.TARGET_POINTS_CASES)
+
+
+@pytest.mark.parametrize("H,W", _scan_shapes())
+def test_points_where_the_scan_plan_changes(H, W, dev):
+    """More than 256 blocks of 256 pixels: a thread of tp_scan_kernel sums and prefixes `per` >= 2 of them.  257 x 256: per = 2 and only
+    thread 128 has a short range (the last block, which holds a root); 349 x 513: per = 3, threads from 234 on are empty; 1024 x 1280,
+    the size of a camera image: per = 20.  Two maps a call (the second upside down: its single pixel lies in the first row), a few hundred components each, with
+    `cap` below and above their number: the prefix decides which record a component lands in and which ones `cap` cuts off."""
+    import analysis_plans as ap
+    plan = ap.tp_scan(H, W)
+    assert plan["per"] >= 2 and _lib.load().pivlfn_target_points_workspace_bytes(1, H, W) == (2 * H * W + plan["nblk"]) * 4
+    r = np.stack([marker_map(H, W, H + W, 150 + H * W // 8000), marker_map(H, W, H + W + 1, 190 + H * W // 8000)[::-1]])
+    for cap in (40, 1024):
+        want = cr.target_points(r, 0.7, cap)
+        n = want[1]
+        assert 100 <= n.min() and n.max() < 1024 and n[0] != n[1]
+        assert want[0][0].max() >= (plan["nblk"] - 1) * 256, "no root in the last block"
+        big = np.bincount(want[0][0][want[0][0] >= 0]).max()
+        assert big >= H + W - 20 and (cap < n[0] or want[2][0, :, 3].max() == big)        # the long component and its record
+        got = gpu_points(r, 0.7, cap, dev)
+        assert _same_points(got, want), f"{H}x{W} cap={cap}"
+        assert np.all(got[2][:, :min(cap, n.min()), 3] >= 1)
+    assert _same_points(gpu_points(r[1:], 0.7, 1024, dev, dirty=False), [w[1:] for w in want])       # alone, clean workspace
+
+
 # ---- (c) dewarp --------------------------------------------------------------------------------------------------------------------------------
 def gpu_dewarp(frames, A, origin, mode, fill, dev):
     lib = _lib.load()

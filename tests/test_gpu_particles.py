@@ -160,6 +160,34 @@ def test_seedings_against_the_restatement(H, W, ppp, R, dev):
     _against_the_restatement(dev, pos, diam, amp, H, W, R, what=f"{H} x {W} {ppp} ppp R={R}")
 
 
+def _tile_shapes():
+    import analysis_plans as ap
+    return ap.shapes(ap.PARTICLES_CASES)
+
+
+@pytest.mark.parametrize("B,H,W", _tile_shapes())
+def test_seedings_of_many_tiles(B, H, W, dev):
+    """More tiles than one wave (65), than one workgroup (257) and than two (544 over two images) of particles_offsets_kernel, whose
+    wave prefixes and atomic cursor decide where a tile's list lies; 0.05 ppp, and 2100 particles more, interleaved with the others,
+    inside the middle of the LAST tile of the last image: a list longer than REN_CAP in the last workgroup's tiles.  The image does not
+    depend on where a list lands (the ascending-index rule): the header's bound against the restatement, and equal bits twice."""
+    import analysis_plans as ap
+    plan = ap.particles_tiles(B, H, W)
+    assert plan["waves"] >= 2
+    extra = ap.REN_CAP + 52
+    N = int(0.05 * (H + 32) * (W + 32)) + extra
+    pos, diam, amp = seeding(B, N, H, W, 3 * H + W)
+    rng = np.random.default_rng(W)
+    here = rng.permutation(N)[:extra]
+    x0, y0 = (W - 1) // 16 * 16 + 8, (H - 1) // 16 * 16 + 8                         # the footprint (R = 4) stays inside that tile
+    assert x0 + 6 <= W and y0 + 6 <= H
+    pos[-1, 0, here], pos[-1, 1, here] = x0 + rng.random(extra), y0 + rng.random(extra)
+    intensity, image = _against_the_restatement(dev, pos, diam, amp, H, W, what=f"{B} x {H} x {W}, {plan['tiles']} tiles")
+    assert image[-1, y0, x0] == 255 and intensity[-1, y0, x0] > 1e5 and (image[0] < 255).any() and (image[0, :, :16] > 0).any()
+    again = _render(dev, pos, diam, amp, H, W, ws_fill="ff")
+    assert np.array_equal(again[0].view(np.int32), intensity.view(np.int32)) and np.array_equal(again[1], image)
+
+
 def test_thousands_of_particles_on_one_pixel(dev):
     """3000 particles inside pixel (30, 20) of 37 x 53 and 2000 spread over the image, interleaved: the lists of two tiles are longer
     than the LDS holds and are ordered window by window; the pixel saturates at 255."""

@@ -165,8 +165,14 @@ def test_rows_off_16_bytes_give_the_same_bits(dev, planted, planted_gram):
 
 
 # ---- project --------------------------------------------------------------------------------------------------------------------------
+def _project_cases():
+    """K = 5 and K = 16: the first and the last K of project_kernel<16>, which the cases before it (K <= 4 and K >= 17) pass by."""
+    import analysis_plans as ap
+    return list(ap.PROJECT_CASES)
+
+
 @pytest.mark.parametrize("pad", [0, 3])
-@pytest.mark.parametrize("n,K,P", [(1, 1, 1), (37, 3, 234), (5, 64, 1029), (70, 17, 300)])
+@pytest.mark.parametrize("n,K,P", [(1, 1, 1), (37, 3, 234), (5, 64, 1029), (70, 17, 300)] + _project_cases())
 def test_project_equals_the_sequential_loop(n, K, P, pad, dev):
     X = _data(n, P, 200 + n)
     Wt = np.random.default_rng(300 + K).normal(0, 1, (n, K))

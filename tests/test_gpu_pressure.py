@@ -2,7 +2,8 @@
 Every operation of the contract is a correctly rounded fp64 operation in a fixed order, so g, valid, b, the adjacency (hence deg), p,
 flag and the status record are compared bit for bit, every element, after 0, 1, 2, 3, 10 and 40 iterations and at convergence.
 Lattices: 1 x 1 and 3 x 3 (nothing to solve), 3 x 4 and 5 x 7, 19 x 23 with a hole that splits it, 33 x 65 just over a power of two,
-70 x 131 with several workgroups' leaves.  Then a batch against its frames alone, how the iterations are cut into calls, the class, the
+70 x 131 with several workgroups' leaves; and, for three iterations, the four lattices of tests/analysis_plans.py at which the plan of
+the block partials changes (257 and 1025 partials, two and four chunks a workgroup).  Then a batch against its frames alone, how the iterations are cut into calls, the class, the
 stream and capture contract as tests/test_gpu_op_streams.py holds the other entry points to it (its helpers, imported), guarded
 buffers, the refusals and run.py --pressure."""
 import json
@@ -157,6 +158,79 @@ def test_bits_of_the_restatement(h, w, dev):
     assert final[0] == (pr.CONVERGED if kept > 1 else pr.BREAKDOWN) and final[1] == total
     if h * w >= 400:
         assert total > 40 and states[40]["status"][0, 0] == pr.RUNNING
+
+
+# ---- where the plan of the block partials changes (tests/analysis_plans.py) -----------------------------------------------------------
+LARGE_COUNTS = (0, 1, 2, 3)
+
+
+def _large_reference(h, w, s, nu, tol, keep=False):
+    """As _reference, for the counts of LARGE_COUNTS only: pr.tree() is the contract's full binary tree and knows nothing of chunks.
+    Kept for a second test only where `keep` says so: the states of 2048 x 2049 are 300 MB."""
+    key = ("large", h, w, s, nu, tol)
+    if key not in _cases:
+        flows = _flows(h, w, 100 * h + w)
+        g, valid = pr.gradient(flows, s, nu)
+        fr, states, done = pr.Frame(g[0], valid[0], s), {}, 0
+        for count in LARGE_COUNTS:
+            fr.run(tol, count - done)
+            done = count
+            states[count] = _state(g, valid, [fr])
+        assert fr.state == pr.RUNNING and fr.iterations == 3
+        if not keep:
+            return flows, states
+        _cases[key] = (flows, states)
+    return _cases[key]
+
+
+def _plan_holds(h, w, F=1):
+    """The library's own NB, from where b lies in the workspace, is the one tests/analysis_plans.py restates and its case is named for."""
+    import analysis_plans as ap
+    from pivlfn import _lib
+    assert _lib.load().pivlfn_pressure_workspace_offset(F, h, w, 0) == 128 * F + 24 * ap.pressure(h, w)["NB"] * F
+    return ap.pressure(h, w)
+
+
+def _pressure_shapes():
+    import analysis_plans as ap
+    return ap.shapes(ap.PRESSURE_CASES)
+
+
+@pytest.mark.parametrize("h,w", _pressure_shapes())
+def test_bits_where_the_partials_plan_changes(h, w, dev):
+    """One frame, s, nu* and tol as test_bits_of_the_restatement, after setup and after 1, 2 and 3 iterations (no run to convergence:
+    the host's share of an iteration at 2048 x 2049 is about a second).  513 x 512: 257 partials, one in the second wave of pr_finish;
+    1024 x 1025: 1025, one in its second chunk; 2048 x 1025 and 2048 x 2049: two and four chunks per workgroup, PrCounter and its carry."""
+    s, nu, tol = 2.0, 0.1, 1e-9
+    plan = _plan_holds(h, w)
+    assert plan["NB"] > 256
+    flows, states = _large_reference(h, w, s, nu, tol, keep=(h, w) == (1024, 1025))
+    kept = int(states[0]["valid"].sum())
+    assert h * w - kept > 2 * (h + w) - 4 and kept > h * w // 2, "unknown vectors must take nodes out beside the border"
+    d = Device(dev, flows, s, nu)
+    for count in LARGE_COUNTS:
+        d.setup().cg(tol, count)
+        _compare(d.read(), states[count], f"{h}x{w} after {count} iterations")
+    assert states[3]["status"][0, 0] == pr.RUNNING and states[3]["status"][0, 1] == 3
+
+
+def test_cuts_and_batches_change_no_bit_with_a_second_chunk_of_partials(dev):
+    """1024 x 1025 (NB = 1025): 3 iterations in one call against 1 + 2; and the frame as the second of a batch of two (its partials
+    start at 1025, no multiple of anything) has the bits it has alone, as has the frame in front of it."""
+    h, w, s, nu, tol = 1024, 1025, 2.0, 0.1, 1e-9
+    assert _plan_holds(h, w, 2)["NB"] == 1025
+    flows, states = _large_reference(h, w, s, nu, tol, keep=True)
+    d = Device(dev, flows, s, nu).cg(tol, 1).cg(tol, 2)
+    alone = d.read()
+    _compare(alone, states[3], "cuts 1 + 2")
+    del d
+    before = _flows(h, w, 31)[:1]
+    four = np.concatenate([before, flows])
+    both = Device(dev, four, s, nu).cg(tol, 3).read()
+    _compare({k: v[1:2] for k, v in both.items()}, alone, "the frame as the second of two")
+    first = Device(dev, four[:3], s, nu).cg(tol, 3).read()
+    _compare({k: v[0:1] for k, v in both.items()}, first, "the frame in front of it")
+    assert not pr.same_bits(first["p"], alone["p"])
 
 
 def test_reading_does_not_disturb_the_iteration(dev):

@@ -136,6 +136,40 @@ def test_a_batch_equals_its_pairs_one_at_a_time(dev):
     assert torch.equal(whole.corrected(fl)[0, :, 5, 5], (fl + whole.residual)[0, :, 5, 5])
 
 
+def _capped_shapes():
+    import analysis_plans as ap
+    return ap.shapes(ap.QUALITY_CASES)
+
+
+@pytest.mark.parametrize("B,H,W,r", _capped_shapes())
+def test_bits_where_the_warp_grid_is_capped(B, H, W, r, dev):
+    """quality_warp_kernel has at most max(16384 / B, 64) workgroups a pair and strides over the rest: 260 pairs of 130 x 128 are 65
+    blocks of 256 pixels on a grid of 64.  Eight particle pairs, each shifted along x by another number of columns for every further
+    pair (rendering 260 takes the host 12 s).  The first, the middle and the last pair against the restatement; sixteen pairs against
+    the same pair in a call of its own, whose grid is not capped."""
+    from pivlfn import match_quality
+    import analysis_plans as ap
+    plan = ap.capped_frame_grid(B, H, W)
+    assert plan["blocks"] > plan["cap"] == plan["grid"]
+    base = _case(8, H, W, 1, 700)
+    img1, img2, flow = (np.stack([np.roll(x[b % 8], b // 8, axis=-1) for b in range(B)]) for x in base)
+    mask = qr.speckle_mask(B, H, W, 9, 2 * r + 4)
+    i1, i2, fl, mk = (torch.from_numpy(x).to(dev) for x in (img1, img2, flow, mask))
+    whole = match_quality(i1, i2, fl, r, mk)
+    seen = 0
+    for b in sorted({0, B // 2, B - 1}):
+        want = qr.batch_quality(img1[b:b + 1], img2[b:b + 1], flow[b:b + 1], r, mask[b:b + 1])
+        got = (whole.c[b:b + 1].cpu().numpy(), whole.residual[b:b + 1].cpu().numpy(), whole.flag[b:b + 1].cpu().numpy())
+        _compare(got, want, f"pair {b} of {B} x {H}x{W} r={r}")
+        seen |= int(np.bitwise_or.reduce(want[1], axis=None))
+        assert np.any(want[1] & 7 == 0), "no fitted pixel in the expected values"
+    assert seen & (FEW | NO_PEAK | CENTRE_OUT) == FEW | NO_PEAK | CENTRE_OUT
+    for b in [0, 1, 2, 63, 64, 65, 127, 128, 129, 130, 191, 192, 255, 256, 258, 259]:
+        one = match_quality(i1[b:b + 1], i2[b:b + 1], fl[b:b + 1], r, mk[b:b + 1])
+        assert same_bits(one.c, whole.c[b:b + 1]) and same_bits(one.residual, whole.residual[b:b + 1]), b
+        assert torch.equal(one.flag, whole.flag[b:b + 1]), b
+
+
 def _call(lib, ins, outs, ws, B, C, H, W, r, stream, ws_bytes=None):
     i1, i2, fl, mk = ins
     return lib.pivlfn_match_quality(i1.data_ptr(), i2.data_ptr(), C, fl.data_ptr(), mk.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(),

@@ -56,11 +56,20 @@ CASES = [(2, 1, 2, 0, 0), (5, 63, 3, 3, 1), (33, 65, 17, 20, 0), (64, 257, 33, 6
          (256, 300, 129, 128, 0)]
 
 
-@pytest.mark.parametrize("L,N,K,first,pad", CASES)
+def _corner_cases():
+    """The corner of the domain, L = 1024 with K = 513, and its ragged neighbour: tests/analysis_plans.py says what each reaches."""
+    import analysis_plans as ap
+    return ap.shapes(ap.SPECTRUM_CASES)
+
+
+@pytest.mark.parametrize("L,N,K,first,pad", CASES + _corner_cases())
 def test_bits_of_the_restatement(L, N, K, first, pad, dev):
     """From a non-zero acc and count.  2 x 1: the shortest segment, one lane; 5 x 63 and 33 x 65: one lane short of a wave and one past
     it, odd lengths, strides of 127 and 130 floats; 64 x 257 at K = 33: four full frequency groups and a single, the last sample first;
-    12 x 1030: 17 tiles; 1024 x 70: eight staged chunks per round; 256 x 300 at K = 129: the default segment, two chunks, three rounds."""
+    12 x 1030: 17 tiles; 1024 x 70: eight staged chunks per round; 256 x 300 at K = 129: the default segment, two chunks, three rounds;
+    1024 x 65 at K = 513, the corner of the domain: 64 frequency groups and one single over 8 waves, the eight chunks staged again in
+    each of the 8 rounds, a second tile of one vector; 1000 x 64 at K = 501: a last chunk of 104 samples, 62 groups (the last round
+    has six) and five singles."""
     X, basis, acc0, count0 = _case(L, N, K, pad, 1000 * L + N)
     want = sr.accumulate(X, first, N, basis, acc0, count0)
     _compare(_run(dev, X, first, N, basis, acc0, count0), want, f"L={L} N={N} K={K} first={first}")

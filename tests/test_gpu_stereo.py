@@ -50,7 +50,14 @@ def test_kernel_matches_reference_fixture(dev):
         assert same_bits(got[0].cpu().numpy(), g[f"{tag}_out"]), tag
 
 
-@pytest.mark.parametrize("B,h,w", [(1, 37, 23), (3, 37, 23), (3, 100, 76), (1, 1024, 1024)])
+def _capped_shapes():
+    """Where the grid of stereo_2d3c_kernel is capped at max(16384 / B, 64) workgroups a pair and strides (tests/analysis_plans.py):
+    260 pairs of 130 x 128 and one of 2049 x 2048.  The 1024 x 1024 case has 4096 workgroups, below the cap."""
+    import analysis_plans as ap
+    return ap.shapes(ap.STEREO_CASES)
+
+
+@pytest.mark.parametrize("B,h,w", [(1, 37, 23), (3, 37, 23), (3, 100, 76), (1, 1024, 1024)] + _capped_shapes())
 @pytest.mark.parametrize("calib", [None, 0.05])
 def test_kernel_matches_restatement_random(dev, B, h, w, calib):
     rng = np.random.default_rng(B * 1000 + h + (7 if calib else 0))

@@ -1,7 +1,8 @@
 """GPU: pivlfn_twopoint_accumulate (csrc/twopoint.hip) against the NumPy restatement of its contract (tests/twopoint_restatement.py).
 Every operation of the contract is a correctly rounded fp64 operation in a fixed order, so the accumulators are compared bit for bit,
 every element of them, and the counts exactly.  Shapes: rows of one pixel and images smaller than most separations, widths just over a
-power of two (the tree is mostly padding) and over one 256-column pass of a wave, separations past half the row and past the edge.
+power of two (the tree is mostly padding) and over one 256-column pass of a wave, separations past half the row and past the edge;
+the shapes of tests/analysis_plans.py with several separations a wave and with 4, 8 and 64 chunks a row.
 Then how a sequence is cut into calls, the stream and capture contract as tests/test_gpu_op_streams.py holds the other entry points to
 it (its helpers, imported), guarded buffers, the refusals, TwoPointStats on the DNS fixture and run.py --twopoint."""
 import json
@@ -82,6 +83,46 @@ def test_bits_of_the_restatement(H, W, R, step, with_mask, with_mean, dev):
     gone = fresh[:, :, 0].sum(-1) == 0
     if gone.any():                                                          # separations without a pair: every term stays what it was
         assert np.array_equal(got[gone].view(np.int64), acc0[gone].view(np.int64))
+
+
+def _plan_shapes():
+    import analysis_plans as ap
+    return ap.shapes(ap.TWOPOINT_CASES)
+
+
+@pytest.mark.parametrize("with_mean", [False, True], ids=["nomean", "mean"])
+@pytest.mark.parametrize("with_mask", [False, True], ids=["nomask", "mask"])
+@pytest.mark.parametrize("H,W,R,step", _plan_shapes())
+def test_bits_where_the_plan_changes(H, W, R, step, with_mask, with_mean, dev):
+    """B = 2 in one call from a non-zero acc, at the shapes of tests/analysis_plans.py.  66 x 300 at R = 255: two separations a wave in
+    LDS; 4096 x 5: 64 of them, the largest LDS request, and one workgroup per row and direction; 1024 x 40 at R = 64: z = 4 and 5 slots
+    as at 1024 x 1024; rows of 520, 1030 and 16384 columns: 4, 8 and 64 chunks of 256, joined by the counter up to its last register."""
+    import analysis_plans as ap
+    plan = ap.twopoint(H, W, R)
+    assert plan["slots"] >= 2 or plan["chunks"] >= 4
+    flow, mask, mean = _case(2, H, W, 100 * H + W + R)
+    mask, mean = mask if with_mask else None, mean if with_mean else None
+    acc0 = np.random.default_rng(5).normal(0, 50, (2, R + 1, 15, H))
+    want = tr.accumulate(flow, mask, mean, acc0, R, step)
+    got = _run(dev, flow, mask, mean, acc0, R, step)
+    _compare(got, want, f"{H}x{W} R={R} step={step}")
+    pairs = (want[:, :, 0] - acc0[:, :, 0]).sum(-1)                               # about the number of pairs of a separation
+    assert pairs[0, 0] < 2 * H * W - 0.5 and pairs[0, min(R, (W - 1) // step)] > 0.5, "the case must exclude some pairs and keep some"
+    gone = (want[:, :, 0] == acc0[:, :, 0]).all(-1)
+    assert np.array_equal(got[gone].view(np.int64), acc0[gone].view(np.int64))      # separations without a pair: as they were
+    if plan["slots"] >= 2:
+        assert not gone[0, :min(R, (W - 1) // step) + 1].any() and not gone[1, :min(R, (H - 1) // step) + 1].any()
+
+
+def test_cutting_the_sequence_changes_no_bit_with_two_slots_a_wave(dev):
+    """66 x 300 at R = 255 (two separations a wave kept in LDS across the frames of a call): B = 2 in one call and in two."""
+    H, W, R, step = 66, 300, 255, 1
+    flow, mask, mean = _case(2, H, W, 78)
+    flow[1] += np.float32(5.0)
+    acc0 = np.random.default_rng(6).normal(0, 50, (2, R + 1, 15, H))
+    whole = _run(dev, flow, mask, mean, acc0, R, step)
+    _compare(_run(dev, flow, mask, mean, acc0, R, step, [1, 1]), whole, "cuts [1, 1]")
+    _compare(whole, tr.accumulate(flow, mask, mean, acc0, R, step), "66x300 R=255")
 
 
 def test_minus_zero_survives_where_the_tree_has_no_padding_to_add(dev):

@@ -86,6 +86,98 @@ def test_maxima_and_cell_means_match_restatement(dev, B, H, W):
     assert all(torch.equal(viz.flow_maxrad(_t(holed[b:b + 1], dev)), per[b:b + 1]) for b in range(B))
 
 
+# ---- where the grids are capped and the kernels stride (tests/analysis_plans.py) -------------------------------------------------------
+def _plan_shapes(name):
+    import analysis_plans as ap
+    return ap.shapes(getattr(ap, name))
+
+
+def _planted(H, W, sweep):
+    """Where the maximum of the LAST image is planted: its last pixel, and a pixel that only a second stride visit of a capped grid
+    reaches (`sweep` pixels are one visit of the whole grid)."""
+    assert sweep + 5 < H * W - 1
+    return [divmod(H * W - 1, W), divmod(sweep + 5, W)]
+
+
+def _speckles(rng, B, H, W):
+    return (rng.random((B, H, W)) < 0.1).astype(np.uint8) * 5
+
+
+@pytest.mark.parametrize("B,H,W", _plan_shapes("VIZ_ABSMAX_CASES"))
+def test_field_absmax_where_the_grid_is_capped(dev, B, H, W):
+    """field_absmax has at most 256 workgroups an image: 257 x 256 is one block over, 1024 x 1024 sixteen visits.  float32 and float64,
+    NaN and inf among the values, with and without a mask; a larger value in pixel 0 of the last image is masked."""
+    import analysis_plans as ap
+    plan = ap.viz_absmax(H, W)
+    assert plan["blocks"] > plan["grid"] == 256
+    rng = np.random.default_rng(B * 100000 + H * 1000 + W)
+    mask = _speckles(rng, B, H, W)
+    for dtype in (np.float32, np.float64):
+        base = rng.normal(0, 2, (B, H, W)).astype(dtype)
+        base.reshape(-1)[::7], base.reshape(-1)[3::11] = np.nan, (np.inf, -np.inf)[dtype == np.float64]
+        for y, x in _planted(H, W, plan["sweep"]):
+            field = base.copy()
+            field[-1, y, x], field[-1, 0, 0], mask[-1, y, x], mask[-1, 0, 0] = -1234.5, 5000.0, 0, 5
+            for m in (None, mask):
+                got = viz.field_absmax(_t(field, dev), None if m is None else _t(m, dev)).cpu().numpy()
+                assert _same_bits(got, vr.field_absmax(field, m)), (dtype, y, x, got)
+                assert got[-1] == (5000.0 if m is None else 1234.5) and (B == 1 or 0 < got[0] < 20)
+
+
+@pytest.mark.parametrize("B,H,W", _plan_shapes("VIZ_MAXRAD_CASES"))
+def test_flow_maxrad_and_its_picture_where_the_grid_is_capped(dev, B, H, W):
+    """flow_maxrad has at most 256 workgroups of 4-pixel groups an image: 513 x 512 is one block over.  The maximum in the last pixel
+    and in one of the second visit, unknown and masked vectors as in the small cases; the picture normalised by it within one level."""
+    import analysis_plans as ap
+    plan = ap.viz_maxrad(H, W)
+    assert plan["blocks"] > plan["grid"] == 256
+    rng = np.random.default_rng(B * 100000 + H * 1000 + W)
+    holed, mask = _holes(rng, B, H, W)
+    for y, x in _planted(H, W, plan["sweep"]):
+        flow = holed.copy()
+        flow[-1, :, y, x], flow[-1, :, 0, 0], mask[-1, y, x], mask[-1, 0, 0] = (30.0, -40.0), (300.0, 400.0), 0, 5
+        for m in (None, mask):
+            ft, mt = _t(flow, dev), None if m is None else _t(m, dev)
+            got = viz.flow_maxrad(ft, mt).cpu().numpy()
+            want = vr.flow_maxrad(flow, m)
+            assert _same_bits(got, want) and got[-1] == (500.0 if m is None else 50.0), (y, x, got, want)
+            pic = viz.flow_to_color(ft, mask=mt).cpu().numpy()
+            assert np.abs(pic.astype(int) - vr.flow_to_color(flow, want, m).astype(int)).max() <= 1, (y, x)
+
+
+@pytest.mark.parametrize("B,H,W", _plan_shapes("VIZ_COLOR_CASES"))
+def test_pictures_and_cell_means_where_the_grid_is_capped(dev, B, H, W):
+    """More than 4 Mi pixels over the batch: flow_to_color and scalar_to_color (groups of four pixels) and flow_decimate at cell 1 (one
+    cell a thread) run on VZ_MAX_BLOCKS workgroups and stride over the rest -- five images of 1024 x 1024, and 2049 x 2048, two blocks
+    over.  The largest vector of the last image lies in its last pixel, which only the second visit reaches."""
+    import analysis_plans as ap
+    plan = ap.viz_color(B, H, W)
+    assert plan["blocks"] > plan["grid"] == ap.VZ_MAX_BLOCKS and plan["decimate_blocks"] > plan["decimate_grid"] and plan["sweep"] < B * H * W
+    rng = np.random.default_rng(B * 100000 + H * 1000 + W)
+    flow, mask = _holes(rng, B, H, W)
+    flow[-1, :, H - 1, W - 1], mask[-1, H - 1, W - 1] = (30.0, -40.0), 0
+    ft, mt = _t(flow, dev), _t(mask, dev)
+    norm = vr.flow_maxrad(flow, mask)
+    assert norm[-1] == 50.0 and _same_bits(viz.flow_maxrad(ft, mt).cpu().numpy(), norm)
+    got = viz.flow_to_color(ft, mask=mt).cpu().numpy()
+    want = vr.flow_to_color(flow, norm, mask)
+    worst = max(int(np.abs(got[b].astype(np.int16) - want[b].astype(np.int16)).max()) for b in range(B))
+    assert worst <= 1 and not got[mask != 0].any() and got[-1, H - 1, W - 1].any()
+    del got, want
+    mean, count = viz.decimate_flow(ft, 1, mt)
+    want_mean, want_count = vr.flow_decimate_planes(flow, 1, mask)           # pinned to vr.flow_decimate's loops by tests/test_viz.py
+    assert _same_bits(count.cpu().numpy(), want_count) and _same_bits(mean.cpu().numpy(), want_mean)
+    assert (want_count == 0).any() and want_count[-1, H - 1, W - 1] == 1
+    del mean, count, want_mean, want_count, ft, flow
+    custom = rng.integers(0, 256, (256, 3), dtype=np.uint8)
+    for dtype in (np.float32, np.float64):
+        field = rng.normal(0, 1, (B, H, W)).astype(dtype)
+        field.reshape(-1)[::13] = np.nan
+        field[-1, H - 1, W - 3:] = (-1.5, 9.0, 1.5 - 3 / 256)
+        got = viz.scalar_to_color(_t(field, dev), -1.5, 1.5, custom, mask=mt, bad=(255, 0, 255)).cpu().numpy()
+        assert np.array_equal(got, vr.scalar_to_color(field, -1.5, 1.5, custom, mask, (255, 0, 255))), dtype
+
+
 def test_flow_to_color_exact_cases(dev, cases):
     """Where no rounding of the arctangent can show: equal to the reference's bytes."""
     for tag in ("signed_zeros", "zeros"):

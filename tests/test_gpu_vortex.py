@@ -90,6 +90,37 @@ def test_every_pair_of_a_batch_equals_itself_alone(dev):
     assert same_bits(again.gamma1, both.gamma1) and same_bits(again.gamma2, both.gamma2)
 
 
+def _capped_shapes():
+    import analysis_plans as ap
+    return ap.shapes(ap.VORTEX_CASES)
+
+
+@pytest.mark.parametrize("B,H,W,r,s", _capped_shapes())
+def test_bits_where_the_stage_grid_is_capped(B, H, W, r, s, dev):
+    """vortex_stage_kernel has at most max(16384 / B, 64) workgroups a frame and strides over the rest: 260 frames of 130 x 128 (65
+    blocks of 256 pixels on a grid of 64: block 0 comes round for the last 256 pixels) and one frame of 2049 x 2048 (16392 on 16384).
+    With a mask.  The first, the middle and the last frame against the restatement; sixteen frames (or the one) against the same frame
+    in a call of its own, whose grid is not capped (65 blocks under a cap of 16384) or, for the one frame, against a second run."""
+    import types
+    import analysis_plans as ap
+    plan = ap.capped_frame_grid(B, H, W)
+    assert plan["blocks"] > plan["cap"] == plan["grid"]
+    flow, mask = vr.random_case(np.random.default_rng(1000 * r + B), B, H, W)
+    v = _run(dev, flow, r, s, mask)
+    frame = lambda b: types.SimpleNamespace(gamma1=v.gamma1[b:b + 1], gamma2=v.gamma2[b:b + 1], flag=v.flag[b:b + 1])       # noqa: E731
+    seen = 0
+    for b in sorted({0, B // 2, B - 1}):
+        want = vr.batch_gamma(flow[b:b + 1], r, s, mask[b:b + 1])
+        _compare(frame(b), want, f"frame {b} of {B} x {H}x{W} r={r} s={s}")
+        seen |= int(np.bitwise_or.reduce(want[1], axis=None))
+        assert not (want[1] & FEW).all()
+    assert seen & FEW and seen & CENTRE_OUT
+    sample = [0, 1, 2, 63, 64, 65, 127, 128, 129, 130, 191, 192, 255, 256, 258, 259] if B > 1 else [0]
+    for b in sample:
+        alone = _run(dev, flow[b:b + 1], r, s, mask[b:b + 1])
+        assert same_bits(alone.gamma1[0], v.gamma1[b]) and same_bits(alone.gamma2[0], v.gamma2[b]) and torch.equal(alone.flag[0], v.flag[b]), b
+
+
 @pytest.mark.parametrize("r,s", [(8, 1), (4, 4)])
 def test_dns_turbulence_fixture(r, s, dev):
     """tests/golden/DNS_turbulence_flow.flo, 256 x 256.  At r = 8 the restatement finds 29 % of the area inside vortex cores."""

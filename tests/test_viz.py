@@ -104,6 +104,27 @@ def test_restatement_leaves_unknown_and_masked_vectors_out():
     assert (mean == np.float32(1e10)).all() and not count.any()
 
 
+def test_the_vectorised_cell_means_are_the_loops():
+    """vr.flow_decimate_planes, which the GPU tests use on images of millions of pixels, against the definition vr.flow_decimate: the
+    shapes and hole patterns of tests/test_gpu_viz.py's small cases, cells 1, 4 and 5, with -0.0 and values of very different size."""
+    for B, H, W in ((1, 1, 1), (1, 1, 9), (1, 9, 1), (3, 13, 17), (1, 67, 131)):
+        rng = np.random.default_rng(B * 100000 + H * 1000 + W)
+        flow = (rng.normal(0, 3, (B, 2, H, W)) * 10.0 ** rng.integers(-3, 4, (B, 2, H, W))).astype(np.float32)
+        vals = (np.nan, 1e10, -np.inf, 2e9, -0.0)
+        n = max(1, H * W // 10)
+        for j, (b, c, y, x) in enumerate(zip(rng.integers(0, B, n), rng.integers(0, 2, n), rng.integers(0, H, n), rng.integers(0, W, n))):
+            flow[b, c, y, x] = vals[j % 5]
+        mask = (rng.random((B, H, W)) < 0.1).astype(np.uint8) * 5
+        gone = flow.copy()
+        gone[-1, 0, :H // 2 + 1] = np.nan
+        for f, m in ((flow, None), (flow, mask), (gone, mask)):
+            for cell in (1, 4, 5):
+                want, got = vr.flow_decimate(f, cell, m), vr.flow_decimate_planes(f, cell, m)
+                for a, b in zip(got, want):
+                    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (B, H, W, cell)
+        assert (vr.flow_decimate(gone, 1, mask)[1] == 0).any()
+
+
 def test_restatement_scalar_map_bins():
     from pivlfn.viz import LUTS
     lut = LUTS["gray"]
