@@ -36,7 +36,7 @@ typedef struct {
 
 const char *pivlfn_last_error(void);
 /* ABI version.  3 (round 6): + pivlfn_conv2d_nhwc_wino_b3, PIVLFN_PRECISION_F32_WINO_MFMA32; - pivlfn_conv2d_nhwc_wino4 (now exported by the tools build only).  2 (round 4): + pivlfn_warp_corr_nhwc_timed, pivlfn_conv2d_nhwc_wino4, pivlfn_conv_create_cat, pivlfn_conv2d_nhwc_cat; since 1 also pivlfn_conv2d_nhwc_wino and PIVLFN_PRECISION_F32_DIRECT
- * (added in round 3 without a bump).  No entry point of version 1 changed its signature or meaning. */
+ * (added in round 3 without a bump); since 3 also the host-only pivlfn_conv2d_nhwc_plan and pivlfn_conv2d_nhwc_kernel_plan.  No entry point of version 1 changed its signature or meaning. */
 int         pivlfn_abi_version(void);
 
 /* The library keeps no process-global mutable state: entry points may be called concurrently from several threads, on
@@ -854,6 +854,34 @@ int pivlfn_conv2d_nhwc_wino(const pivlfn_conv *conv, const float *x, int x_strid
  * (<= 2^-32) or 9 (the exact product of the two fp32 operands).  fp32 x, fp32 y. */
 int pivlfn_conv2d_nhwc_wino_b3(const pivlfn_conv *conv, const float *x, int x_stride, float *y, int y_stride,
                                int B, int H, int W, int leaky, int terms, void *stream);
+/* Which kernel pivlfn_conv2d_nhwc_f16 / _split / _wino / _wino_b3 runs for a layer of this shape (as pivlfn_conv_create packs it) and a
+ * call of this geometry: the entry point's own checks and the launcher's own decision, made on the host -- nothing is launched, no handle
+ * and no GPU is needed.  kernel: PIVLFN_KERNEL_PLAN_F16, _SPLIT, _WINO or _WINO_B3, the entry point asked about.  terms: the split entry
+ * point's (3 or 6) and the wino_b3 one's (6, 8 or 9), ignored by the others; x_is_f16: the f16 entry point's, ignored by the others; the
+ * two Winograd entry points take stride 1 and padding 1 only.  cus: the compute units the wino_b3 kernel's persistent grid is sized for
+ * (the library asks the device; here the caller says, so that the function needs none), >= 1, ignored by the others.
+ *   plan[0]  the kernel, PIVLFN_KERNEL_PLAN_*: for the split entry point _SPLIT (conv_split_kernel) or _SPLIT_BIG (conv_split_big_kernel)
+ *   plan[1]  piece products per product, the kernel's TERMS (split: 3 or 6, 3 for the big kernel; wino_b3: 6, 8 or 9; else 0)
+ *   plan[2]  output rows of one workgroup's tile     (f16, split: 4 * MT; wino: 8 * MB; big, wino_b3: 16)
+ *   plan[3]  output channels of one workgroup's tile (f16, split, big: 32 * NT; wino: 32 * NBW; wino_b3: 64)
+ *   plan[4]  the staging class as 100 * PM + WM (f16, split; else 0)
+ *   plan[5]  the workgroups per CU the kernel is compiled for (its launch bound)
+ *   plan[6]  the split-K shares (1 = not split; only the three-term split kernel splits)
+ *   plan[7]  1 when the big split kernel multiplies the layer's 4-lane tail chunk with its taps folded into K
+ *   plan[8]  1 when the handle runs the batch image by image (split: a batch on a grid small enough for split-K, since the handle's
+ *            scratch holds one image's shares); plan[] is then one image's
+ *   plan[9]  the workgroups of the launch (per image where plan[8] is set; the split-K reduction's launch not counted)
+ * Returns PIVLFN_ERR_ARG, with the same message, for everything the entry point refuses for that geometry (its pointers apart).
+ * Whether a geometry is accepted and the split-K shares never depend on B, nor does the choice between the big and the small split kernel
+ * for a layer with a folded tail; the tile otherwise does, the bits of a sample do not (tests/test_conv_kernel_plans.py,
+ * tests/test_gpu_conv_kernel_tiles.py). */
+#define PIVLFN_KERNEL_PLAN_F16       1   /* conv_f16_kernel<rows / 4, channels / 32, PM, WM> */
+#define PIVLFN_KERNEL_PLAN_SPLIT     2   /* conv_split_kernel<terms, rows / 4, channels / 32, PM, WM, workgroups per CU> */
+#define PIVLFN_KERNEL_PLAN_SPLIT_BIG 3   /* conv_split_big_kernel<channels / 32>: 16 rows, one workgroup per CU, three-term products */
+#define PIVLFN_KERNEL_PLAN_WINO      4   /* conv_wino_kernel<rows / 8, channels / 32> */
+#define PIVLFN_KERNEL_PLAN_WINO_B3   5   /* conv_wino_b3_kernel<terms>: min(tiles, cus) persistent workgroups */
+int pivlfn_conv2d_nhwc_kernel_plan(int kernel, int cout, int cin, int kh, int kw, int B, int H, int W, int stride, int pad_y, int pad_x,
+                                   int terms, int x_is_f16, int x_stride, int y_stride, int cus, int plan[10]);
 #ifdef PIVLFN_TOOLS
 /* Tools build only (tools/libpivlfn_tools.so; the kernel lives in tools/kernels/conv_wino4.hip since round 6): the same layer on the
  * Winograd F(4x4, 3x3) kernel (6 x 6 transforms; relative error ~1e-5 against ~1.4e-6 of F(2x2)).  Measured 0.98x of F(2x2) on

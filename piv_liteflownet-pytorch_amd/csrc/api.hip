@@ -97,6 +97,18 @@ int pivlfn_conv2d_nhwc_plan(int cout, int cin, int kh, int kw, int B, int H, int
     return PIVLFN_OK;
 }
 
+int pivlfn_conv2d_nhwc_kernel_plan(int kernel, int cout, int cin, int kh, int kw, int B, int H, int W, int stride, int pad_y, int pad_x,
+                                   int terms, int x_is_f16, int x_stride, int y_stride, int cus, int plan[10])
+{
+    PIV_REQUIRE(plan && cout > 0 && cin > 0 && kh > 0 && kw > 0, "conv2d_kernel_plan: bad arguments");
+    ConvKernelPlan pl;
+    if (int rc = conv_kernel_plan(kernel, cout, cin, kh, kw, B, H, W, stride, pad_y, pad_x, terms, x_is_f16, x_stride, y_stride, cus, pl))
+        return rc;
+    plan[0] = pl.kernel; plan[1] = pl.terms; plan[2] = pl.rows; plan[3] = pl.chans; plan[4] = pl.staging; plan[5] = pl.occ;
+    plan[6] = pl.ksplit; plan[7] = pl.fold; plan[8] = pl.per_image; plan[9] = pl.blocks;
+    return PIVLFN_OK;
+}
+
 int pivlfn_backwarp(const float *in, const float *flow, float *out, int B, int C, int H, int W, void *stream)
 {
     return launch_backwarp_nchw(in, flow, out, B, C, H, W, (hipStream_t)stream);

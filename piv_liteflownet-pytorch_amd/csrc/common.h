@@ -142,6 +142,28 @@ int launch_conv1_fused(const ConvParams &p, const Conv1Fuse &f, hipStream_t st);
 int launch_touch(const float *p, size_t floats, float *sink, hipStream_t st);     // read-only prefetch pass (ops.hip)
 int launch_splitk_reduce(const ConvParams &p, int nz, hipStream_t st);     // second pass of a split-K layer (also used by conv_split.hip)
 
+// What launch_conv_h / _x / _w / _wb run for a call (pivlfn_conv2d_nhwc_kernel_plan; the fields are plan[0..9] there): the kernel
+// (PIVLFN_KERNEL_PLAN_*) and its template arguments -- piece products per product (split, b3; 0 elsewhere), output rows and channels
+// of a workgroup's tile, the staging class as 100 * PM + WM (f16, split; 0 elsewhere), the workgroups per CU it is compiled for --
+// then the split-K shares, whether the folded 4-lane tail is used, whether the handle runs the batch image by image (set by the
+// entry point's side, conv_layer.hip's conv_call_x; the plan is then one image's), and the workgroups of the launch.
+struct ConvKernelPlan { int kernel, terms, rows, chans, staging, occ, ksplit, fold, per_image, blocks; };
+// Each of those launchers is a choice and a launch.  The choice (choose_conv_*) reads the geometry alone -- no pointer is followed,
+// no device is touched -- and names the instantiation by its launch function and its plan in one statement; launch_conv_* makes the
+// choice and launches what it named.  What the choice cannot see of the caller's pointers it is told: has_scratch, has_wtail.
+template <class P>
+struct ConvChoice {
+    int (*run)(const P &, hipStream_t);
+    ConvKernelPlan pl;
+};
+// L = one instantiation's launcher: L::plan holds its own bounds and its grid, L::run launches it
+template <class L, class P>
+static inline int conv_take(const P &p, ConvChoice<P> &ch)
+{
+    ch.run = &L::run;
+    return L::plan(p, ch.pl);
+}
+
 // ---- fp16-multiplicand variant (conv_f16.hip): optional reduced-precision mode, K chunks of 16 channels ----------------
 struct ConvSegH {
     const void *ptr;    // NHWC base (fp32 or fp16 elements), channel offset already applied
@@ -164,6 +186,7 @@ struct ConvParamsH {
 #endif
     unsigned long long *stamps;   // tools only: per-workgroup phase times (s_memtime ticks), 8 per workgroup; nullptr in production
 };
+int choose_conv_h(const ConvParamsH &p, ConvChoice<ConvParamsH> &ch);
 int launch_conv_h(const ConvParamsH &p, hipStream_t st);
 // ---- fp32 by exact fp16 operand splitting (conv_split.hip): fp32 sources and output, K chunks of 16 channels ------------
 struct ConvParamsX {
@@ -188,6 +211,8 @@ struct ConvParamsX {
     int dbg;            // ablation mask for tools/bench_ops.py (0 in production): 1 no MFMAs, 2 no global loads, 4 no LDS commit
 #endif
 };
+// ch.pl.terms / .ksplit / .fold: what launch_conv_x sets in the parameter block (terms only differ from p.terms under a tools knob)
+int choose_conv_x(const ConvParamsX &p, bool has_scratch, bool has_wtail, ConvChoice<ConvParamsX> &ch);
 int launch_conv_x(const ConvParamsX &p, hipStream_t st);
 bool conv_split_supports(int KH, int KW, int S, int cout_pad, int terms);
 // ---- 3x3 stride-1 layers by Winograd F(2x2, 3x3) on the fp32 matrix cores (conv_wino.hip): fp32 everywhere, K chunks of 8 channels ----
@@ -207,6 +232,13 @@ struct ConvParamsW {
     const void *wpk_b;  // conv_wino_b3.hip: the same U split into three bf16 pieces, [nchunk][cout_pad/64][4][4][2][3][64][8] (pack_conv_wb); nchunk = K steps of 16 channels
     int terms;          // conv_wino_b3.hip: piece products per product, 6 (default), 8 or 9
 };
+int choose_conv_w(const ConvParamsW &p, ConvChoice<ConvParamsW> &ch);
+// conv_wino_b3.hip's grid is sized by the device: its choice takes the CU count, its launch the workgroups the choice planned
+struct ConvChoiceB3 {
+    int (*run)(const ConvParamsW &, int blocks, hipStream_t);
+    ConvKernelPlan pl;
+};
+int choose_conv_wb(const ConvParamsW &p, int cus, ConvChoiceB3 &ch);
 int launch_conv_w(const ConvParamsW &p, hipStream_t st);
 int launch_conv_wb(const ConvParamsW &p, hipStream_t st);      // the same layers with exactly split operands on the bf16 matrix cores (conv_wino_b3.hip)
 bool conv_wino_b3_supports(int cout_pad);

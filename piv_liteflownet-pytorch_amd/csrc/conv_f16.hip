@@ -270,21 +270,66 @@ __global__ __launch_bounds__(256, (MT * NT * 16 + (2 * PM + WM) * 4 + 60 > 240) 
 #undef STAMP
 }
 
+// One instantiation: plan = its bounds and its grid (part of choose_conv_h), run = the launch
 template <int MT, int NT, int PM, int WM>
-static int launch_h(const ConvParamsH &p, hipStream_t st)
+struct launch_h {
+    static constexpr int TH = 4 * MT, BN = NT * 32;
+    static size_t lds_bytes(const ConvParamsH &p)
+    {
+        const int PH = (TH - 1) * p.S + p.KH, PW = 31 * p.S + p.KW;
+        return ((size_t)PH * PW * HPITCH + (size_t)p.KH * p.KW * 2 * BN * 8) * sizeof(_Float16) + BN * sizeof(float);
+    }
+    static dim3 grid(const ConvParamsH &p) { return dim3(cdiv(p.Wo, 32) * cdiv(p.Ho, TH) * p.B, p.cout_pad / BN); }
+    static int plan(const ConvParamsH &p, ConvKernelPlan &pl)
+    {
+        const int PH = (TH - 1) * p.S + p.KH, PW = 31 * p.S + p.KW;
+        const size_t lds = lds_bytes(p);
+        PIV_REQUIRE(lds <= 160 * 1024, "conv_f16: LDS tile of %zu bytes exceeds 160 KiB (k=%dx%d s=%d)", lds, p.KH, p.KW, p.S);
+        PIV_REQUIRE(PH * PW * 2 <= 256 * PM && p.KH * p.KW * 2 * BN <= 256 * WM, "conv_f16: internal staging bound exceeded");
+        const dim3 g = grid(p);
+        pl.kernel = PIVLFN_KERNEL_PLAN_F16; pl.rows = TH; pl.chans = BN; pl.staging = 100 * PM + WM;
+        pl.occ = (MT * NT * 16 + (2 * PM + WM) * 4 + 60 > 240) ? 1 : 2;      // the kernel's launch bound
+        pl.blocks = (int)(g.x * g.y);
+        return PIVLFN_OK;
+    }
+    static int run(const ConvParamsH &p, hipStream_t st)
+    {
+        static LdsAttr attr;
+        if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_f16_kernel<MT, NT, PM, WM>), 160 * 1024)) return rc;
+        hipLaunchKernelGGL((conv_f16_kernel<MT, NT, PM, WM>), grid(p), dim3(256), lds_bytes(p), st, p);
+        PIV_CHECK_HIP(hipGetLastError());
+        return PIVLFN_OK;
+    }
+};
+
+// The choice, from the geometry alone (the sources' pointers are not looked at)
+int choose_conv_h(const ConvParamsH &p, ConvChoice<ConvParamsH> &ch)
 {
-    constexpr int TH = 4 * MT, BN = NT * 32;
-    const int PH = (TH - 1) * p.S + p.KH, PW = 31 * p.S + p.KW;
-    const size_t lds = ((size_t)PH * PW * HPITCH + (size_t)p.KH * p.KW * 2 * BN * 8) * sizeof(_Float16) + BN * sizeof(float);
-    PIV_REQUIRE(lds <= 160 * 1024, "conv_f16: LDS tile of %zu bytes exceeds 160 KiB (k=%dx%d s=%d)", lds, p.KH, p.KW, p.S);
-    PIV_REQUIRE(PH * PW * 2 <= 256 * PM && p.KH * p.KW * 2 * BN <= 256 * WM, "conv_f16: internal staging bound exceeded");
-    static LdsAttr attr;
-    if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_f16_kernel<MT, NT, PM, WM>), 160 * 1024)) return rc;
-    const int tiles = cdiv(p.Wo, 32) * cdiv(p.Ho, TH) * p.B;
-    dim3 grid(tiles, p.cout_pad / BN);
-    hipLaunchKernelGGL((conv_f16_kernel<MT, NT, PM, WM>), grid, dim3(256), lds, st, p);
-    PIV_CHECK_HIP(hipGetLastError());
-    return PIVLFN_OK;
+    ch.run = nullptr;
+    ch.pl = ConvKernelPlan{};
+    ch.pl.ksplit = 1;
+    PIV_REQUIRE(p.nseg >= 1 && p.nseg <= 3 && p.nchunk >= 1, "conv_f16: bad segment description");
+    PIV_REQUIRE(p.cout_pad % 32 == 0 && p.cout_store <= p.cout_pad && p.cout_store % 4 == 0, "conv_f16: bad output channel counts");
+    for (int i = 0; i < p.nseg; ++i)
+        PIV_REQUIRE(p.seg[i].cload % (p.seg[i].f16 ? 8 : 4) == 0 && p.seg[i].stride % (p.seg[i].f16 ? 8 : 4) == 0,
+                    "conv_f16: source %d must be 16-byte granular", i);
+    PIV_REQUIRE(p.Ho > 0 && p.Wo > 0 && p.B > 0, "conv_f16: empty output");
+    const auto take = [&](auto l) { return conv_take<decltype(l)>(p, ch); };
+    const bool s1_3x3 = p.S == 1 && p.KH <= 3 && p.KW <= 3;
+    const int nt = (p.cout_pad % 128 == 0) ? 4 : (p.cout_pad % 64 == 0 ? 2 : 1);
+    const long tiles16 = (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 16) * p.B * (p.cout_pad / (32 * nt));
+    const bool big = tiles16 >= 192;         // enough 16-row tiles to give (almost) every CU one
+    if (s1_3x3) {
+        if (nt == 4) return big ? take(launch_h<4, 4, 5, 9>()) : take(launch_h<2, 4, 5, 9>());
+        // 64 channels: the 8-row tile fits twice per CU (128->64 at 1024^2: 242 us vs 293 us for the 16-row tile)
+        if (nt == 2 && big && (PIV_KNOB(1) & 64)) return take(launch_h<4, 2, 5, 9>());      // tools build only
+        if (nt == 2) return take(launch_h<2, 2, 5, 9>());
+        return big ? take(launch_h<4, 1, 5, 9>()) : take(launch_h<2, 1, 5, 9>());
+    }
+    // everything else (stride 2, 7x7, separable k x 1 / 1 x k): 8-row tiles, the larger staging class
+    if (nt == 4) return take(launch_h<2, 4, 9, 13>());
+    if (nt == 2) return take(launch_h<2, 2, 9, 13>());
+    return take(launch_h<2, 1, 9, 13>());
 }
 
 int launch_conv_h(const ConvParamsH &p_in, hipStream_t st)
@@ -292,26 +337,10 @@ int launch_conv_h(const ConvParamsH &p_in, hipStream_t st)
     ConvParamsH p = p_in;
     PIV_SET_DBG(p, PIV_KNOB(3));
     p.stamps = reinterpret_cast<unsigned long long *>(((unsigned long long)(unsigned)PIV_KNOB(6) << 32) | (unsigned)PIV_KNOB(5));   // tools only
-    PIV_REQUIRE(p.nseg >= 1 && p.nseg <= 3 && p.nchunk >= 1, "conv_f16: bad segment description");
-    PIV_REQUIRE(p.cout_pad % 32 == 0 && p.cout_store <= p.cout_pad && p.cout_store % 4 == 0, "conv_f16: bad output channel counts");
-    for (int i = 0; i < p.nseg; ++i)
-        PIV_REQUIRE(p.seg[i].ptr && p.seg[i].cload % (p.seg[i].f16 ? 8 : 4) == 0 && p.seg[i].stride % (p.seg[i].f16 ? 8 : 4) == 0,
-                    "conv_f16: source %d must be 16-byte granular", i);
-    PIV_REQUIRE(p.Ho > 0 && p.Wo > 0 && p.B > 0, "conv_f16: empty output");
-    const bool s1_3x3 = p.S == 1 && p.KH <= 3 && p.KW <= 3;
-    const int nt = (p.cout_pad % 128 == 0) ? 4 : (p.cout_pad % 64 == 0 ? 2 : 1);
-    const long tiles16 = (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 16) * p.B * (p.cout_pad / (32 * nt));
-    const bool big = tiles16 >= 192;         // enough 16-row tiles to give (almost) every CU one
-    if (s1_3x3) {
-        if (nt == 4) return big ? launch_h<4, 4, 5, 9>(p, st) : launch_h<2, 4, 5, 9>(p, st);
-        // 64 channels: the 8-row tile fits twice per CU (128->64 at 1024^2: 242 us vs 293 us for the 16-row tile)
-        if (nt == 2) return (big && (PIV_KNOB(1) & 64)) ? launch_h<4, 2, 5, 9>(p, st) : launch_h<2, 2, 5, 9>(p, st);
-        return big ? launch_h<4, 1, 5, 9>(p, st) : launch_h<2, 1, 5, 9>(p, st);
-    }
-    // everything else (stride 2, 7x7, separable k x 1 / 1 x k): 8-row tiles, the larger staging class
-    if (nt == 4) return launch_h<2, 4, 9, 13>(p, st);
-    if (nt == 2) return launch_h<2, 2, 9, 13>(p, st);
-    return launch_h<2, 1, 9, 13>(p, st);
+    ConvChoice<ConvParamsH> ch;
+    if (int rc = choose_conv_h(p, ch)) return rc;
+    for (int i = 0; i < p.nseg; ++i) PIV_REQUIRE(p.seg[i].ptr, "conv_f16: source %d must be 16-byte granular", i);
+    return ch.run(p, st);
 }
 
 // OIHW fp32 weights -> fp16 [chunk][tap][k-half][cout_pad][8]; chunk = 16 staged input channels of one source.

@@ -198,10 +198,13 @@ int conv_create(const float *weight, const float *bias, int cout, int cin, int k
     pivlfn_conv *c = nullptr;
     int rc = conv_create_packed(weight, bias, cout, cin, kh, kw, {{cin, rup(cin, 4)}}, &c);
     if (rc) return rc;
-    {   // pivlfn_conv2d_nhwc_plan derives these from the shape alone
+    {   // pivlfn_conv2d_nhwc_plan and pivlfn_conv2d_nhwc_kernel_plan derive these from the shape alone
         const ConvShape sh = conv_shape(cout, cin, kh, kw);
-        if (sh.cout_pad != c->cw.cout_pad || sh.nchunk != c->cw.nchunk || sh.tail != c->cw.tail || sh.col7 != (c->cw.wpk_c != nullptr) ||
-            sh.row7 != (c->cw.wpk_r != nullptr)) {
+        const ConvW &cw = c->cw;
+        if (sh.cout_pad != cw.cout_pad || sh.nchunk != cw.nchunk || sh.tail != cw.tail || sh.col7 != (cw.wpk_c != nullptr) ||
+            sh.row7 != (cw.wpk_r != nullptr) || sh.nchunk_h != cw.nchunk_h || sh.split != (cw.wpk_x != nullptr) ||
+            (sh.split && sh.nchunk_x != cw.nchunk_x) || sh.split_tail != (cw.wtail_x != nullptr) || sh.wino != (cw.wpk_w != nullptr) ||
+            (sh.wino && sh.nchunk_w != cw.nchunk_w) || sh.wino_b3 != (cw.wpk_wb != nullptr) || (sh.wino_b3 && sh.nstep_wb != cw.nstep_wb)) {
             set_error("internal: conv_shape disagrees with pack_conv for %d<-%d %dx%d", cout, cin, kh, kw);
             rc = PIVLFN_ERR_WEIGHTS;
         }
@@ -273,8 +276,26 @@ int conv_forward_choose(const ConvShape &c, int x_stride, int y_stride, const fl
 ConvShape conv_shape(int cout, int cin, int kh, int kw)
 {
     const int cload = rup(cin, 4);
-    return ConvShape{cout, rup(cout, 32), cin, kh, kw, seg_chunks(cload), seg_tail(cload), packs_col7(cout, cin, kh, kw, 1, cload),
-                     packs_row7(cout, cin, kh, kw, 1, cload)};
+    const int cp = rup(cout, 32), nchunk16 = (cload + 15) / 16;
+    const bool split = conv_split_supports(kh, kw, 1, cp, 6), wino = kh == 3 && kw == 3;
+    return ConvShape{cout, cp, cin, kh, kw, seg_chunks(cload), seg_tail(cload), packs_col7(cout, cin, kh, kw, 1, cload),
+                     packs_row7(cout, cin, kh, kw, 1, cload), nchunk16, nchunk16, seg_chunks(cload), std::max(nchunk16, 2),
+                     split, split && wino && cload % 16 == 4, wino, wino && conv_wino_b3_supports(cp)};
+}
+
+// The layer a shape stands for, for the choices made without a handle: where pack_conv would make a packing, a pointer that is
+// never followed
+static ConvW shape_layer(const ConvShape &sh)
+{
+    static float packed = 0.f;
+    ConvW cw;
+    cw.cout = sh.cout; cw.cout_pad = sh.cout_pad; cw.cin = sh.cin; cw.KH = sh.KH; cw.KW = sh.KW; cw.nchunk = sh.nchunk; cw.tail = sh.tail;
+    cw.wpk_h = &packed; cw.nchunk_h = sh.nchunk_h;
+    if (sh.split) { cw.wpk_x = &packed; cw.nchunk_x = sh.nchunk_x; }
+    if (sh.split_tail) cw.wtail_x = &packed;
+    if (sh.wino) { cw.wpk_w = &packed; cw.nchunk_w = sh.nchunk_w; }
+    if (sh.wino_b3) { cw.wpk_wb = &packed; cw.nstep_wb = sh.nstep_wb; }
+    return cw;
 }
 
 int conv_forward(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride, const float *res, int res_stride,
@@ -331,19 +352,59 @@ int conv_head_forward(const pivlfn_conv *c, const float *x, const float *res4, f
     return launch_conv_head(x, c->head, c->hb[0], c->hb[1], res4, out4, B, H, W, c->cw.KH, st);
 }
 
+// ---- the stand-alone entry points of the other four families: conv_call_* holds an entry point's checks, its parameter block and the
+// launcher's choice for a layer cw of cin channels -- a handle's, or a shape's stand-in with null x and y (conv_kernel_plan): nothing in
+// them follows a pointer
+static int conv_call_h(const ConvW &cw, int cin, const void *x, int x_stride, int x_f16, void *y, int y_stride, int y_f16,
+                       int B, int H, int W, int stride, int pad_y, int pad_x, int leaky, ConvParamsH &q, ConvKernelPlan &pl)
+{
+    const int g = x_f16 ? 8 : 4;
+    PIV_REQUIRE(x_stride % g == 0 && x_stride >= rup(cin, g), "conv2d_f16: x_stride=%d must be a multiple of %d and >= %d", x_stride, g, rup(cin, g));
+    PIV_REQUIRE(y_stride % 4 == 0 && y_stride >= cw.cout, "conv2d_f16: y_stride=%d must be a multiple of 4 and >= cout=%d", y_stride, cw.cout);
+    PIV_REQUIRE(stride >= 1 && pad_y >= 0 && pad_x >= 0 && H + 2 * pad_y >= cw.KH && W + 2 * pad_x >= cw.KW, "conv2d_f16: bad geometry");
+    ConvCall call = single_call(cw.cout, cin, g, x, x_stride, y, y_stride, nullptr, 0, leaky, B, H, W, stride, pad_y, pad_x);
+    call.in16 = x_f16 ? 1 : 0;
+    call.out16 = y_f16;
+    q = conv_params_h(cw, call);
+    ConvChoice<ConvParamsH> ch;
+    const int rc = choose_conv_h(q, ch);
+    pl = ch.pl;
+    return rc;
+}
+
 // Standalone layer in the fp16 mode (tests, tools): x / y element types chosen per call.
 int conv_forward_h(const pivlfn_conv *c, const void *x, int x_stride, int x_f16, void *y, int y_stride, int y_f16,
                    int B, int H, int W, int stride, int pad_y, int pad_x, int leaky, hipStream_t st)
 {
     PIV_REQUIRE(c && x && y, "conv2d_f16: null argument");
-    const int g = x_f16 ? 8 : 4;
-    PIV_REQUIRE(x_stride % g == 0 && x_stride >= rup(c->cin, g), "conv2d_f16: x_stride=%d must be a multiple of %d and >= %d", x_stride, g, rup(c->cin, g));
-    PIV_REQUIRE(y_stride % 4 == 0 && y_stride >= c->cw.cout, "conv2d_f16: y_stride=%d must be a multiple of 4 and >= cout=%d", y_stride, c->cw.cout);
-    PIV_REQUIRE(stride >= 1 && pad_y >= 0 && pad_x >= 0 && H + 2 * pad_y >= c->cw.KH && W + 2 * pad_x >= c->cw.KW, "conv2d_f16: bad geometry");
-    ConvCall call = single_call(c->cw.cout, c->cin, g, x, x_stride, y, y_stride, nullptr, 0, leaky, B, H, W, stride, pad_y, pad_x);
-    call.in16 = x_f16 ? 1 : 0;
-    call.out16 = y_f16;
-    return launch_conv_h(conv_params_h(c->cw, call), st);
+    ConvParamsH q;
+    ConvKernelPlan pl;
+    if (int rc = conv_call_h(c->cw, c->cin, x, x_stride, x_f16, y, y_stride, y_f16, B, H, W, stride, pad_y, pad_x, leaky, q, pl)) return rc;
+    return launch_conv_h(q, st);
+}
+
+// pl.per_image: the handle has one image's worth of split-K scratch, so a batch of a grid launch_conv_x may split runs image by image
+// (pl is then one image's plan): the split factor -- hence the summation order and the bits of a sample -- is the same whatever the
+// batch (the invariant launch_conv_x states for the network's own calls)
+static int conv_call_x(const ConvW &cw, int cin, bool has_scratch, const float *x, int x_stride, float *y, int y_stride, int B, int H, int W,
+                       int stride, int pad_y, int pad_x, int leaky, int terms, ConvParamsX &q, ConvKernelPlan &pl)
+{
+    PIV_REQUIRE(terms == 6 || terms == 3, "conv2d_split: terms=%d (6 or 3 partial products per product)", terms);
+    PIV_REQUIRE(cw.wpk_x && conv_split_supports(cw.KH, cw.KW, stride, cw.cout_pad, terms),
+                "conv2d_split: this layer's geometry (k=%dx%d, stride %d, %d-term products) is not covered by the split kernel", cw.KH, cw.KW, stride, terms);
+    PIV_REQUIRE(x_stride % 4 == 0 && x_stride >= rup(cin, 4), "conv2d_split: x_stride=%d must be a multiple of 4 and >= %d", x_stride, rup(cin, 4));
+    PIV_REQUIRE(y_stride % 4 == 0 && y_stride >= cw.cout, "conv2d_split: y_stride=%d must be a multiple of 4 and >= cout=%d", y_stride, cw.cout);
+    PIV_REQUIRE(pad_y >= 0 && pad_x >= 0 && H + 2 * pad_y >= cw.KH && W + 2 * pad_x >= cw.KW, "conv2d_split: bad geometry");
+    q = conv_params_x(cw, single_call(cw.cout, cin, 4, x, x_stride, y, y_stride, nullptr, 0, leaky, B, H, W, stride, pad_y, pad_x), terms);
+    q.scratch_floats = KSPLIT_FLOATS;
+    const bool per_image = B > 1 && (long)cdiv(q.Wo, 32) * cdiv(q.Ho, 4) * (q.cout_pad / 32) <= 256;      // the grids launch_conv_x may split
+    ConvParamsX q1 = q;
+    if (per_image) q1.B = 1;
+    ConvChoice<ConvParamsX> ch;
+    const int rc = choose_conv_x(q1, has_scratch, cw.wtail_x != nullptr, ch);
+    pl = ch.pl;
+    pl.per_image = per_image;
+    return rc;
 }
 
 // Standalone layer on the split-operand kernel (tests, tools): fp32 in, fp32 out.
@@ -351,17 +412,12 @@ int conv_forward_x(const pivlfn_conv *c, const float *x, int x_stride, float *y,
                    int B, int H, int W, int stride, int pad_y, int pad_x, int leaky, int terms, hipStream_t st)
 {
     PIV_REQUIRE(c && x && y, "conv2d_split: null argument");
-    PIV_REQUIRE(terms == 6 || terms == 3, "conv2d_split: terms=%d (6 or 3 partial products per product)", terms);
-    PIV_REQUIRE(c->cw.wpk_x && conv_split_supports(c->cw.KH, c->cw.KW, stride, c->cw.cout_pad, terms),
-                "conv2d_split: this layer's geometry (k=%dx%d, stride %d, %d-term products) is not covered by the split kernel", c->cw.KH, c->cw.KW, stride, terms);
-    PIV_REQUIRE(x_stride % 4 == 0 && x_stride >= rup(c->cin, 4), "conv2d_split: x_stride=%d must be a multiple of 4 and >= %d", x_stride, rup(c->cin, 4));
-    PIV_REQUIRE(y_stride % 4 == 0 && y_stride >= c->cw.cout, "conv2d_split: y_stride=%d must be a multiple of 4 and >= cout=%d", y_stride, c->cw.cout);
-    PIV_REQUIRE(pad_y >= 0 && pad_x >= 0 && H + 2 * pad_y >= c->cw.KH && W + 2 * pad_x >= c->cw.KW, "conv2d_split: bad geometry");
-    ConvParamsX q = conv_params_x(c->cw, single_call(c->cw.cout, c->cin, 4, x, x_stride, y, y_stride, nullptr, 0, leaky, B, H, W, stride, pad_y, pad_x), terms);
-    // one image's worth of split-K scratch: larger batches run image by image, so the split factor -- hence the summation order and
-    // the bits of a sample -- is the same whatever the batch (the invariant launch_conv_x states for the network's own calls)
-    q.scratch = c->scratch; q.scratch_floats = KSPLIT_FLOATS;
-    if (B > 1 && (long)cdiv(q.Wo, 32) * cdiv(q.Ho, 4) * (q.cout_pad / 32) <= 256) {      // the grids launch_conv_x may split
+    ConvParamsX q;
+    ConvKernelPlan pl;
+    if (int rc = conv_call_x(c->cw, c->cin, c->scratch != nullptr, x, x_stride, y, y_stride, B, H, W, stride, pad_y, pad_x, leaky, terms, q, pl))
+        return rc;
+    q.scratch = c->scratch;
+    if (pl.per_image) {
         for (int b = 0; b < B; ++b) {
             ConvParamsX qb = q;
             qb.B = 1;
@@ -391,16 +447,34 @@ int conv_forward_cat(const pivlfn_conv *c, int nsrc, const float *const *x, cons
     return conv(ctx, c->cw, conv_call(sg, nsrc, y, y_stride, cs, nullptr, 0, leaky, B, H, W, 1, c->cw.KH / 2, c->cw.KW / 2), st);
 }
 
+static int conv_call_w(const ConvW &cw, int cin, const float *x, int x_stride, float *y, int y_stride, int B, int H, int W, int leaky,
+                       ConvCall &call)
+{
+    PIV_REQUIRE(cw.wpk_w, "conv2d_wino: the layer is not 3 x 3 (k=%dx%d)", cw.KH, cw.KW);
+    PIV_REQUIRE(x_stride % 4 == 0 && x_stride >= rup(cin, 4), "conv2d_wino: x_stride=%d must be a multiple of 4 and >= %d", x_stride, rup(cin, 4));
+    PIV_REQUIRE(y_stride % 4 == 0 && y_stride >= cw.cout, "conv2d_wino: y_stride=%d must be a multiple of 4 and >= cout=%d", y_stride, cw.cout);
+    call = single_call(cw.cout, cin, 4, x, x_stride, y, y_stride, nullptr, 0, leaky, B, H, W, 1, 1, 1);
+    return PIVLFN_OK;
+}
+
+static int conv_call_wb(const ConvW &cw, int cin, const float *x, int x_stride, float *y, int y_stride, int B, int H, int W, int leaky,
+                        int terms, ConvParamsW &q)
+{
+    PIV_REQUIRE(cw.wpk_wb, "conv2d_wino_b3: the layer is not 3 x 3 with whole 64-channel output groups (k=%dx%d, cout_pad=%d)", cw.KH, cw.KW, cw.cout_pad);
+    PIV_REQUIRE(x_stride % 4 == 0 && x_stride >= rup(cin, 4), "conv2d_wino_b3: x_stride=%d must be a multiple of 4 and >= %d", x_stride, rup(cin, 4));
+    PIV_REQUIRE(y_stride % 4 == 0 && y_stride >= cw.cout, "conv2d_wino_b3: y_stride=%d must be a multiple of 4 and >= cout=%d", y_stride, cw.cout);
+    q = conv_params_w(cw, single_call(cw.cout, cin, 4, x, x_stride, y, y_stride, nullptr, 0, leaky, B, H, W, 1, 1, 1), WINO_B3, terms);
+    return PIVLFN_OK;
+}
+
 // Standalone 3 x 3 / stride 1 / pad 1 layer on the Winograd kernels (tests, tools): fp32 in, fp32 out.  tile = 2: F(2x2, 3x3), 4: F(4x4, 3x3).
 int conv_forward_w(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride, int B, int H, int W, int leaky,
                    hipStream_t st, int tile)
 {
     PIV_REQUIRE(tile == 2 || tile == 4, "conv2d_wino: tile=%d (2 or 4)", tile);
     PIV_REQUIRE(c && x && y, "conv2d_wino: null argument");
-    PIV_REQUIRE(c->cw.wpk_w, "conv2d_wino: the layer is not 3 x 3 (k=%dx%d)", c->cw.KH, c->cw.KW);
-    PIV_REQUIRE(x_stride % 4 == 0 && x_stride >= rup(c->cin, 4), "conv2d_wino: x_stride=%d must be a multiple of 4 and >= %d", x_stride, rup(c->cin, 4));
-    PIV_REQUIRE(y_stride % 4 == 0 && y_stride >= c->cw.cout, "conv2d_wino: y_stride=%d must be a multiple of 4 and >= cout=%d", y_stride, c->cw.cout);
-    const ConvCall call = single_call(c->cw.cout, c->cin, 4, x, x_stride, y, y_stride, nullptr, 0, leaky, B, H, W, 1, 1, 1);
+    ConvCall call;
+    if (int rc = conv_call_w(c->cw, c->cin, x, x_stride, y, y_stride, B, H, W, leaky, call)) return rc;
     if (tile == 4) {
 #ifdef PIVLFN_TOOLS
         PIV_REQUIRE(c->cw.wpk_w4, "conv2d_wino4: the layer object carries no F(4x4) weights");
@@ -417,11 +491,47 @@ int conv_forward_wb(const pivlfn_conv *c, const float *x, int x_stride, float *y
                     int terms, hipStream_t st)
 {
     PIV_REQUIRE(c && x && y, "conv2d_wino_b3: null argument");
-    PIV_REQUIRE(c->cw.wpk_wb, "conv2d_wino_b3: the layer is not 3 x 3 with whole 64-channel output groups (k=%dx%d, cout_pad=%d)", c->cw.KH, c->cw.KW, c->cw.cout_pad);
-    PIV_REQUIRE(x_stride % 4 == 0 && x_stride >= rup(c->cin, 4), "conv2d_wino_b3: x_stride=%d must be a multiple of 4 and >= %d", x_stride, rup(c->cin, 4));
-    PIV_REQUIRE(y_stride % 4 == 0 && y_stride >= c->cw.cout, "conv2d_wino_b3: y_stride=%d must be a multiple of 4 and >= cout=%d", y_stride, c->cw.cout);
-    const ConvCall call = single_call(c->cw.cout, c->cin, 4, x, x_stride, y, y_stride, nullptr, 0, leaky, B, H, W, 1, 1, 1);
-    return launch_conv_wb(conv_params_w(c->cw, call, WINO_B3, terms), st);
+    ConvParamsW q;
+    if (int rc = conv_call_wb(c->cw, c->cin, x, x_stride, y, y_stride, B, H, W, leaky, terms, q)) return rc;
+    return launch_conv_wb(q, st);
+}
+
+// pivlfn_conv2d_nhwc_kernel_plan: what pivlfn_conv2d_nhwc_f16 / _split / _wino / _wino_b3 would launch for a layer of this shape, as
+// pivlfn_conv_create packs it, and a call of this geometry -- through the entry points' own checks and the launchers' own choices.
+int conv_kernel_plan(int kernel, int cout, int cin, int kh, int kw, int B, int H, int W, int stride, int pad_y, int pad_x, int terms,
+                     int x_f16, int x_stride, int y_stride, int cus, ConvKernelPlan &pl)
+{
+    const ConvW cw = shape_layer(conv_shape(cout, cin, kh, kw));
+    switch (kernel) {
+        case PIVLFN_KERNEL_PLAN_F16: {
+            ConvParamsH q;
+            return conv_call_h(cw, cin, nullptr, x_stride, x_f16, nullptr, y_stride, 0, B, H, W, stride, pad_y, pad_x, 1, q, pl);
+        }
+        case PIVLFN_KERNEL_PLAN_SPLIT: {
+            ConvParamsX q;
+            return conv_call_x(cw, cin, true, nullptr, x_stride, nullptr, y_stride, B, H, W, stride, pad_y, pad_x, 1, terms, q, pl);
+        }
+        case PIVLFN_KERNEL_PLAN_WINO: {
+            PIV_REQUIRE(stride == 1 && pad_y == 1 && pad_x == 1, "conv2d_wino: stride 1 and padding 1 only (stride %d, padding %d, %d)", stride, pad_y, pad_x);
+            ConvCall call;
+            if (int rc = conv_call_w(cw, cin, nullptr, x_stride, nullptr, y_stride, B, H, W, 1, call)) return rc;
+            ConvChoice<ConvParamsW> ch;
+            const int rc = choose_conv_w(conv_params_w(cw, call, WINO_F2), ch);
+            pl = ch.pl;
+            return rc;
+        }
+        case PIVLFN_KERNEL_PLAN_WINO_B3: {
+            PIV_REQUIRE(stride == 1 && pad_y == 1 && pad_x == 1, "conv2d_wino_b3: stride 1 and padding 1 only (stride %d, padding %d, %d)", stride, pad_y, pad_x);
+            ConvParamsW q;
+            if (int rc = conv_call_wb(cw, cin, nullptr, x_stride, nullptr, y_stride, B, H, W, 1, terms, q)) return rc;
+            ConvChoiceB3 ch;
+            const int rc = choose_conv_wb(q, cus, ch);
+            pl = ch.pl;
+            return rc;
+        }
+        default: PIV_REQUIRE(false, "conv2d_kernel_plan: kernel=%d (PIVLFN_KERNEL_PLAN_F16, _SPLIT, _WINO or _WINO_B3)", kernel);
+    }
+    return PIVLFN_OK;
 }
 
 }  // namespace pivlfn

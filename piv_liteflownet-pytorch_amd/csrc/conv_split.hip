@@ -305,30 +305,49 @@ __global__ __launch_bounds__(256, OCC) void conv_split_kernel(const ConvParamsX 
     }
 }
 
+// One instantiation: plan = its bounds and its grid for a call whose p.ksplit is set (part of choose_conv_x), run = the launch
 template <int TERMS, int MT, int NT, int PM, int WM, int OCC>
-static int launch_x(const ConvParamsX &p, hipStream_t st)
-{
-    constexpr int TH = 4 * MT, BN = NT * 32, NP = TERMS == 6 ? 3 : 2, XPITCH = NP * 16 + 8;
-    const int PH = (TH - 1) * p.S + p.KH, PW = 31 * p.S + p.KW;
-    const size_t lds = ((size_t)PH * PW * XPITCH + (size_t)p.KW * NP * 2 * BN * 8) * sizeof(_Float16) + BN * sizeof(float);
-    PIV_REQUIRE(lds * OCC <= 160 * 1024, "conv_split: LDS tile of %zu bytes x %d exceeds 160 KiB (k=%dx%d s=%d)", lds, OCC, p.KH, p.KW, p.S);
-    PIV_REQUIRE(PH * PW * 2 <= 256 * PM && p.KW * NP * 2 * BN <= 256 * WM, "conv_split: internal staging bound exceeded");
-    static LdsAttr attr;
-    if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_split_kernel<TERMS, MT, NT, PM, WM, OCC>), 160 * 1024)) return rc;
-    const int tiles = cdiv(p.Wo, 32) * cdiv(p.Ho, TH) * p.B;
-    const int nz = p.ksplit > 1 ? p.ksplit : 1;
-    dim3 grid(tiles, p.cout_pad / BN, nz);
-    hipLaunchKernelGGL((conv_split_kernel<TERMS, MT, NT, PM, WM, OCC>), grid, dim3(256), lds, st, p);
-    PIV_CHECK_HIP(hipGetLastError());
-    if (nz > 1) {       // second pass: the fp32 kernel's reduction (conv_mfma.hip)
-        ConvParams r;
-        memset(&r, 0, sizeof(r));
-        r.scratch = p.scratch; r.bias = p.bias; r.out = p.out; r.out_stride = p.out_stride; r.cout_store = p.cout_store;
-        r.cout_pad = p.cout_pad; r.B = p.B; r.Ho = p.Ho; r.Wo = p.Wo; r.lrelu = p.lrelu;
-        return launch_splitk_reduce(r, nz, st);
+struct launch_x {
+    static constexpr int TH = 4 * MT, BN = NT * 32, NP = TERMS == 6 ? 3 : 2, XPITCH = NP * 16 + 8;
+    static size_t lds_bytes(const ConvParamsX &p)
+    {
+        const int PH = (TH - 1) * p.S + p.KH, PW = 31 * p.S + p.KW;
+        return ((size_t)PH * PW * XPITCH + (size_t)p.KW * NP * 2 * BN * 8) * sizeof(_Float16) + BN * sizeof(float);
     }
-    return PIVLFN_OK;
-}
+    static dim3 grid(const ConvParamsX &p)
+    {
+        const int tiles = cdiv(p.Wo, 32) * cdiv(p.Ho, TH) * p.B;
+        return dim3(tiles, p.cout_pad / BN, p.ksplit > 1 ? p.ksplit : 1);
+    }
+    static int plan(const ConvParamsX &p, ConvKernelPlan &pl)
+    {
+        const int PH = (TH - 1) * p.S + p.KH, PW = 31 * p.S + p.KW;
+        const size_t lds = lds_bytes(p);
+        PIV_REQUIRE(lds * OCC <= 160 * 1024, "conv_split: LDS tile of %zu bytes x %d exceeds 160 KiB (k=%dx%d s=%d)", lds, OCC, p.KH, p.KW, p.S);
+        PIV_REQUIRE(PH * PW * 2 <= 256 * PM && p.KW * NP * 2 * BN <= 256 * WM, "conv_split: internal staging bound exceeded");
+        const dim3 g = grid(p);
+        pl.kernel = PIVLFN_KERNEL_PLAN_SPLIT; pl.terms = TERMS; pl.rows = TH; pl.chans = BN; pl.staging = 100 * PM + WM; pl.occ = OCC;
+        pl.blocks = (int)(g.x * g.y * g.z);
+        return PIVLFN_OK;
+    }
+    static int run(const ConvParamsX &p, hipStream_t st)
+    {
+        static LdsAttr attr;
+        if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_split_kernel<TERMS, MT, NT, PM, WM, OCC>), 160 * 1024)) return rc;
+        const dim3 g = grid(p);
+        const int nz = (int)g.z;
+        hipLaunchKernelGGL((conv_split_kernel<TERMS, MT, NT, PM, WM, OCC>), g, dim3(256), lds_bytes(p), st, p);
+        PIV_CHECK_HIP(hipGetLastError());
+        if (nz > 1) {       // second pass: the fp32 kernel's reduction (conv_mfma.hip)
+            ConvParams r;
+            memset(&r, 0, sizeof(r));
+            r.scratch = p.scratch; r.bias = p.bias; r.out = p.out; r.out_stride = p.out_stride; r.cout_store = p.cout_store;
+            r.cout_pad = p.cout_pad; r.B = p.B; r.Ho = p.Ho; r.Wo = p.Wo; r.lrelu = p.lrelu;
+            return launch_splitk_reduce(r, nz, st);
+        }
+        return PIVLFN_OK;
+    }
+};
 
 // ---- 16-row tile, one workgroup per CU, everything double-buffered (three-term products, 3 x 3 stride 1) ---------------------
 // conv_split_kernel's two workgroups per CU each alternate staging -> barrier -> MFMAs -> barrier: the matrix pipe idles whenever
@@ -621,18 +640,26 @@ __global__ __launch_bounds__(256, 1) void conv_split_big_kernel(const ConvParams
 }
 
 template <int NT>
-static int launch_xbig(const ConvParamsX &p, hipStream_t st)
-{
-    constexpr int BN = NT * 32;
-    const size_t lds = ((size_t)2 * 613 * 40 + (size_t)2 * 3 * 4 * BN * 8) * sizeof(_Float16) + BN * sizeof(float);
-    static LdsAttr attr;
-    if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_split_big_kernel<NT>), 160 * 1024)) return rc;
-    const int tiles = cdiv(p.Wo, 32) * cdiv(p.Ho, 16) * p.B;
-    dim3 grid(tiles, p.cout_pad / BN);
-    hipLaunchKernelGGL((conv_split_big_kernel<NT>), grid, dim3(256), lds, st, p);
-    PIV_CHECK_HIP(hipGetLastError());
-    return PIVLFN_OK;
-}
+struct launch_xbig {
+    static constexpr int BN = NT * 32;
+    static dim3 grid(const ConvParamsX &p) { return dim3(cdiv(p.Wo, 32) * cdiv(p.Ho, 16) * p.B, p.cout_pad / BN); }
+    static int plan(const ConvParamsX &p, ConvKernelPlan &pl)
+    {
+        const dim3 g = grid(p);
+        pl.kernel = PIVLFN_KERNEL_PLAN_SPLIT_BIG; pl.terms = 3; pl.rows = 16; pl.chans = BN; pl.staging = 0; pl.occ = 1;
+        pl.blocks = (int)(g.x * g.y);
+        return PIVLFN_OK;
+    }
+    static int run(const ConvParamsX &p, hipStream_t st)
+    {
+        const size_t lds = ((size_t)2 * 613 * 40 + (size_t)2 * 3 * 4 * BN * 8) * sizeof(_Float16) + BN * sizeof(float);
+        static LdsAttr attr;
+        if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_split_big_kernel<NT>), 160 * 1024)) return rc;
+        hipLaunchKernelGGL((conv_split_big_kernel<NT>), grid(p), dim3(256), lds, st, p);
+        PIV_CHECK_HIP(hipGetLastError());
+        return PIVLFN_OK;
+    }
+};
 
 // Which layers the kernel takes (conv_layer.hip asks before routing): stride 1 with at most 7 taps per kernel row, or 3 x 3 at stride 2
 // with three-term products (4-row tiles: the stride-2 patch of an 8-row tile does not fit twice per CU); 16-byte granular sources.
@@ -647,14 +674,17 @@ bool conv_split_supports(int KH, int KW, int S, int cout_pad, int terms)
     return lds * 2 <= 160 * 1024 && PH * PW * 2 <= 256 * 5 && KW * 6 * bn <= 256 * 11;
 }
 
-int launch_conv_x(const ConvParamsX &p_in, hipStream_t st)
+// The choice: from the geometry, from whether a split-K scratch of p.scratch_floats exists and whether the layer carries a folded
+// tail packing (p.scratch, p.wtail and the sources' pointers are not looked at).
+int choose_conv_x(const ConvParamsX &p_in, bool has_scratch, bool has_wtail, ConvChoice<ConvParamsX> &ch)
 {
     ConvParamsX p = p_in;
-    PIV_SET_DBG(p, PIV_KNOB(3));
+    ch.run = nullptr;
+    ch.pl = ConvKernelPlan{};
     PIV_REQUIRE(p.nseg >= 1 && p.nseg <= 3 && p.nchunk >= 1, "conv_split: bad segment description");
     PIV_REQUIRE(p.cout_pad % 32 == 0 && p.cout_store <= p.cout_pad && p.cout_store % 4 == 0, "conv_split: bad output channel counts");
     for (int i = 0; i < p.nseg; ++i)
-        PIV_REQUIRE(p.seg[i].ptr && p.seg[i].cload % 4 == 0 && p.seg[i].stride % 4 == 0, "conv_split: source %d must be 16-byte granular", i);
+        PIV_REQUIRE(p.seg[i].cload % 4 == 0 && p.seg[i].stride % 4 == 0, "conv_split: source %d must be 16-byte granular", i);
     PIV_REQUIRE(p.Ho > 0 && p.Wo > 0 && p.B > 0, "conv_split: empty output");
     // tools-build knobs (pivlfn_tune(1, .); all zero in libpivlfn.so): 65536 force three terms, 131072 / 262144 no 16-row kernel for
     // 64 / 128 channels, 524288 no 16-row small-kernel tiles for 64 channels
@@ -666,17 +696,20 @@ int launch_conv_x(const ConvParamsX &p_in, hipStream_t st)
     p.ksplit = 1;
     {
         const long blocks1 = (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 4) * (p.cout_pad / 32);
-        if (p.scratch && p.terms == 3 && p.S == 1 && blocks1 <= 256 && p.nchunk >= 2) {
+        if (has_scratch && p.terms == 3 && p.S == 1 && blocks1 <= 256 && p.nchunk >= 2) {
             p.ksplit = (int)std::min<long>(std::min(8, p.nchunk), std::max<long>(1, 1024 / blocks1));
             if ((size_t)p.B * p.Ho * p.Wo * p.cout_pad * p.ksplit > p.scratch_floats) p.ksplit = 1;
         }
     }
-    if (p.S == 2) return p.cout_pad % 64 == 0 ? launch_x<3, 1, 2, 5, 3, 2>(p, st) : launch_x<3, 1, 1, 5, 2, 2>(p, st);
+    ch.pl.terms = p.terms;
+    ch.pl.ksplit = p.ksplit;
+    const auto take = [&](auto l) { return conv_take<decltype(l)>(p, ch); };
+    if (p.S == 2) return p.cout_pad % 64 == 0 ? take(launch_x<3, 1, 2, 5, 3, 2>()) : take(launch_x<3, 1, 1, 5, 2, 2>());
     // small grids (three-term, 3 x 3 or smaller kernels): 4-row tiles while 8-row ones would leave CUs without work
     if (p.terms == 3 && p.KH <= 3 && p.KW <= 3) {
         const long t8 = (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 8) * p.B * p.ksplit;
-        if (p.cout_pad % 64 == 0 && t8 * (p.cout_pad / 64) < 512) return launch_x<3, 1, 2, 2, 3, 4>(p, st);
-        if (p.cout_pad % 64 != 0 && t8 * (p.cout_pad / 32) < 512) return launch_x<3, 1, 1, 2, 2, 4>(p, st);
+        if (p.cout_pad % 64 == 0 && t8 * (p.cout_pad / 64) < 512) return take(launch_x<3, 1, 2, 2, 3, 4>());
+        if (p.cout_pad % 64 != 0 && t8 * (p.cout_pad / 32) < 512) return take(launch_x<3, 1, 1, 2, 2, 4>());
     }
     const bool wide = p.KW > 3;                       // 1 x k / k x k rows of 5 or 7 taps: the larger weight-row class
     const bool tall = (7 + p.KH) * (31 + p.KW) * 2 > 256 * 3;
@@ -692,36 +725,52 @@ int launch_conv_x(const ConvParamsX &p_in, hipStream_t st)
         // A folded tail (p.wtail) only exists for this kernel and sums in another order than the zero-padded tail chunk of the
         // others: for layers that have one, the kernel is chosen from the per-image tile count (a pair's bits must not depend on
         // its batch mates); layers without a tail give the same bits on every kernel and may follow the batch.
-        ConvParamsX pt = p;
-        const bool fold = p.wtail && !(PIV_KNOB(1) & 32);
-        pt.tail = fold ? 1 : 0;
+        const bool fold = has_wtail && !(PIV_KNOB(1) & 32);
         const long t16b = fold ? (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 16) : t16;
         if (p.ksplit == 1 && p.cout_pad % 128 == 0 && p.KH == 3 && p.KW == 3 && t16b * (p.cout_pad / 128) >= 512 &&
-            (p.nchunk >= 6 || (fold && p.nchunk >= 4)) && fits31 && !(PIV_KNOB(1) & 262144))
-            return launch_xbig<4>(pt, st);
+            (p.nchunk >= 6 || (fold && p.nchunk >= 4)) && fits31 && !(PIV_KNOB(1) & 262144)) {
+            ch.pl.fold = fold;
+            return take(launch_xbig<4>());
+        }
         if (p.ksplit == 1 && p.cout_pad % 64 == 0 && p.KH == 3 && p.KW == 3 && t16b * (p.cout_pad / 64) >= 512 && p.nchunk >= 6 && fits31 &&
-            !(PIV_KNOB(1) & 131072))
-            return launch_xbig<2>(pt, st);       // 128->64 at 1024^2: 476 -> 445 us
+            !(PIV_KNOB(1) & 131072)) {
+            ch.pl.fold = fold;
+            return take(launch_xbig<2>());       // 128->64 at 1024^2: 476 -> 445 us
+        }
         // 128-channel tiles unless that leaves fewer than four workgroups per CU (tile shapes never change a result's bits)
         const long t128 = (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 8) * p.B * (p.cout_pad / 128);
-        if (p.cout_pad % 128 == 0 && !wide && !tall && t128 >= 1024) return launch_x<3, 2, 4, 3, 6, 2>(p, st);
+        if (p.cout_pad % 128 == 0 && !wide && !tall && t128 >= 1024) return take(launch_x<3, 2, 4, 3, 6, 2>());
         if (p.cout_pad % 64 == 0) {
-            if (wide) return launch_x<3, 2, 2, 5, 7, 2>(p, st);
+            if (wide) return take(launch_x<3, 2, 2, 5, 7, 2>());
             // 3 x 3 with 64 channels: 16-row tiles (12 LDS operand reads per 24 MFMAs instead of 8 per 12) while four workgroups per
             // CU remain; 128->64 at 1024^2: 478 -> 450 us.  (32-channel layers lose with 16 rows: 157 -> 162 us; 1 x 1: 183 -> 200.)
             const long t16 = (long)cdiv(p.Wo, 32) * cdiv(p.Ho, 16) * p.B * (p.cout_pad / 64);
-            if (p.KH == 3 && p.KW == 3 && t16 >= 1024 && !(PIV_KNOB(1) & 524288)) return launch_x<3, 4, 2, 5, 3, 2>(p, st);
-            return tall ? launch_x<3, 2, 2, 5, 3, 2>(p, st) : launch_x<3, 2, 2, 3, 3, 3>(p, st);
+            if (p.KH == 3 && p.KW == 3 && t16 >= 1024 && !(PIV_KNOB(1) & 524288)) return take(launch_x<3, 4, 2, 5, 3, 2>());
+            return tall ? take(launch_x<3, 2, 2, 5, 3, 2>()) : take(launch_x<3, 2, 2, 3, 3, 3>());
         }
-        if (wide) return launch_x<3, 2, 1, 5, 4, 2>(p, st);
-        return tall ? launch_x<3, 2, 1, 5, 2, 2>(p, st) : launch_x<3, 2, 1, 3, 2, 3>(p, st);
+        if (wide) return take(launch_x<3, 2, 1, 5, 4, 2>());
+        return tall ? take(launch_x<3, 2, 1, 5, 2, 2>()) : take(launch_x<3, 2, 1, 3, 2, 3>());
     }
     if (p.cout_pad % 64 == 0) {
-        if (wide) return launch_x<6, 2, 2, 5, 11, 2>(p, st);
-        return tall ? launch_x<6, 2, 2, 5, 5, 2>(p, st) : launch_x<6, 2, 2, 3, 5, 2>(p, st);
+        if (wide) return take(launch_x<6, 2, 2, 5, 11, 2>());
+        return tall ? take(launch_x<6, 2, 2, 5, 5, 2>()) : take(launch_x<6, 2, 2, 3, 5, 2>());
     }
-    if (wide) return launch_x<6, 2, 1, 5, 6, 2>(p, st);
-    return tall ? launch_x<6, 2, 1, 5, 3, 2>(p, st) : launch_x<6, 2, 1, 3, 3, 2>(p, st);
+    if (wide) return take(launch_x<6, 2, 1, 5, 6, 2>());
+    return tall ? take(launch_x<6, 2, 1, 5, 3, 2>()) : take(launch_x<6, 2, 1, 3, 3, 2>());
+}
+
+// What the choice decided goes into the parameter block here and nowhere else: the products' terms, the split-K shares, the tail's form
+int launch_conv_x(const ConvParamsX &p_in, hipStream_t st)
+{
+    ConvParamsX p = p_in;
+    PIV_SET_DBG(p, PIV_KNOB(3));
+    ConvChoice<ConvParamsX> ch;
+    if (int rc = choose_conv_x(p, p.scratch != nullptr, p.wtail != nullptr, ch)) return rc;
+    for (int i = 0; i < p.nseg; ++i) PIV_REQUIRE(p.seg[i].ptr, "conv_split: source %d must be 16-byte granular", i);
+    p.terms = ch.pl.terms;
+    p.ksplit = ch.pl.ksplit;
+    if (ch.pl.kernel == PIVLFN_KERNEL_PLAN_SPLIT_BIG) p.tail = ch.pl.fold;
+    return ch.run(p, st);
 }
 
 static unsigned short f16_bits(float v);

@@ -420,29 +420,39 @@ bool conv_wino_supports(int KH, int KW, int S, int padY, int padX)
     return KH == 3 && KW == 3 && S == 1 && padY == 1 && padX == 1;
 }
 
+// One instantiation: plan = its bound and its grid (part of choose_conv_w), run = the launch
 template <int MB, int NBW>
-static int launch_w(const ConvParamsW &p, hipStream_t st)
-{
-    constexpr int PH = 8 * MB + 2;
-    size_t lds = std::max<size_t>((size_t)MB * NBW * 32768, (size_t)3 * (PH * WROWQ + WPIXQ) * 16);
+struct launch_w {
+    static long blocks(const ConvParamsW &p) { return (long)p.B * cdiv(p.H, 8 * MB) * cdiv(p.W, 16) * (p.cout_pad / (32 * NBW)); }
+    static int plan(const ConvParamsW &p, ConvKernelPlan &pl)
+    {
+        PIV_REQUIRE(blocks(p) < (1L << 31), "conv_wino: grid too large");
+        pl.kernel = PIVLFN_KERNEL_PLAN_WINO; pl.rows = 8 * MB; pl.chans = 32 * NBW; pl.occ = (MB * NBW <= 2) ? 2 : 1;      // the kernel's launch bound
+        pl.blocks = (int)blocks(p);
+        return PIVLFN_OK;
+    }
+    static int run(const ConvParamsW &p, hipStream_t st)
+    {
+        constexpr int PH = 8 * MB + 2;
+        size_t lds = std::max<size_t>((size_t)MB * NBW * 32768, (size_t)3 * (PH * WROWQ + WPIXQ) * 16);
 #ifdef PIVLFN_TOOLS
-    if (PIV_KNOB(1) & 1048576) lds = 96 * 1024;      // measurement: one workgroup per CU (tools/bench_wino.py --masks 65536)
+        if (PIV_KNOB(1) & 1048576) lds = 96 * 1024;      // measurement: one workgroup per CU (tools/bench_wino.py --masks 65536)
 #endif
-    static LdsAttr attr;
-    if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_wino_kernel<MB, NBW>), (int)lds)) return rc;
-    const long blocks = (long)p.B * cdiv(p.H, 8 * MB) * cdiv(p.W, 16) * (p.cout_pad / (32 * NBW));
-    PIV_REQUIRE(blocks < (1L << 31), "conv_wino: grid too large");
-    hipLaunchKernelGGL((conv_wino_kernel<MB, NBW>), dim3((unsigned)blocks), dim3(256), lds, st, p);
-    PIV_CHECK_HIP(hipGetLastError());
-    return PIVLFN_OK;
-}
+        static LdsAttr attr;
+        if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_wino_kernel<MB, NBW>), (int)lds)) return rc;
+        hipLaunchKernelGGL((conv_wino_kernel<MB, NBW>), dim3((unsigned)blocks(p)), dim3(256), lds, st, p);
+        PIV_CHECK_HIP(hipGetLastError());
+        return PIVLFN_OK;
+    }
+};
 
-int launch_conv_w(const ConvParamsW &p_in, hipStream_t st)
+// The choice, from the geometry alone (no pointer is looked at)
+int choose_conv_w(const ConvParamsW &p, ConvChoice<ConvParamsW> &ch)
 {
-    ConvParamsW p = p_in;
-    p.stamps = reinterpret_cast<unsigned long long *>(((unsigned long long)(unsigned)PIV_KNOB(6) << 32) | (unsigned)PIV_KNOB(5));   // tools only (0 in production)
-    PIV_SET_DBG(p, PIV_KNOB(15));
-    PIV_REQUIRE(p.nseg >= 1 && p.nseg <= 3 && p.wpk && p.bias && p.out, "conv_wino: bad arguments");
+    ch.run = nullptr;
+    ch.pl = ConvKernelPlan{};
+    ch.pl.ksplit = 1;
+    PIV_REQUIRE(p.nseg >= 1 && p.nseg <= 3, "conv_wino: bad arguments");
     PIV_REQUIRE(p.cout_pad % 32 == 0 && p.cout_store <= p.cout_pad && p.cout_store % 4 == 0 && p.out_stride % 4 == 0,
                 "conv_wino: cout_pad=%d cout_store=%d out_stride=%d", p.cout_pad, p.cout_store, p.out_stride);
     PIV_REQUIRE(p.B > 0 && p.H > 0 && p.W > 0 && (long)p.B * p.H * p.W < (1L << 31), "conv_wino: bad shape");
@@ -450,7 +460,7 @@ int launch_conv_w(const ConvParamsW &p_in, hipStream_t st)
         PIV_REQUIRE((long)20 * p.W * p.seg[s].stride * 4 < (1L << 31), "conv_wino: 20 rows of source %d exceed 2 GiB", s);
     int nchunk = 0;
     for (int s = 0; s < p.nseg; ++s) {
-        PIV_REQUIRE(p.seg[s].cload % 4 == 0 && p.seg[s].stride % 4 == 0 && p.seg[s].ptr, "conv_wino: segment %d misaligned", s);
+        PIV_REQUIRE(p.seg[s].cload % 4 == 0 && p.seg[s].stride % 4 == 0, "conv_wino: segment %d misaligned", s);
         nchunk += (p.seg[s].cload + 7) / 8;
     }
     PIV_REQUIRE(nchunk == p.nchunk, "conv_wino: segments hold %d chunks, weights were packed for %d", nchunk, p.nchunk);
@@ -458,25 +468,38 @@ int launch_conv_w(const ConvParamsW &p_in, hipStream_t st)
     const int nb = p.cout_pad / 32;
     const long sp1 = (long)p.B * cdiv(p.H, 8) * cdiv(p.W, 16), sp2 = (long)p.B * cdiv(p.H, 16) * cdiv(p.W, 16);
     int mb = sp2 * nb >= 512 ? 2 : 1;
+    const auto take = [&](auto l) { return conv_take<decltype(l)>(p, ch); };
+#ifdef PIVLFN_TOOLS
+    // A/B of the tile shapes (tools/bench_wino.py --masks): two or four channel blocks per wave halve / quarter the transform's
+    // vector work per MFMA but run one workgroup per CU (16 accumulators) or spill (1 x 2): measured slower, see DESIGN.md
+    const int force = PIV_KNOB(14);
+    if (force == 22 && nb % 2 == 0) return take(launch_w<2, 2>());
+    if (force == 14 && nb % 4 == 0) return take(launch_w<1, 4>());
+    if (force == 21) return take(launch_w<2, 1>());
+    if (force == 11) mb = 1;
+#endif
+    // two channel blocks per wave (half the transform work per MFMA, one weight set) wherever the layer has an even number of
+    // 32-channel blocks: -4...-5 % against 16-row tiles with one block per wave on every such layer of levels 1 and 2
+    if (nb % 2 == 0 && sp1 * (nb / 2) >= 256) return take(launch_w<1, 2>());
+    if (mb == 2) return take(launch_w<2, 1>());
+    return take(launch_w<1, 1>());
+}
+
+int launch_conv_w(const ConvParamsW &p_in, hipStream_t st)
+{
+    ConvParamsW p = p_in;
+    p.stamps = reinterpret_cast<unsigned long long *>(((unsigned long long)(unsigned)PIV_KNOB(6) << 32) | (unsigned)PIV_KNOB(5));   // tools only (0 in production)
+    PIV_SET_DBG(p, PIV_KNOB(15));
+    ConvChoice<ConvParamsW> ch;
+    if (int rc = choose_conv_w(p, ch)) return rc;
+    PIV_REQUIRE(p.wpk && p.bias && p.out, "conv_wino: bad arguments");
+    for (int s = 0; s < p.nseg; ++s) PIV_REQUIRE(p.seg[s].ptr, "conv_wino: segment %d misaligned", s);
 #ifdef PIVLFN_TOOLS
     // Round 5's persistent kernel with specialised waves (conv_wino_ws.hip): same values bit for bit (tests/test_gpu_wino.py), 4-8 % slower than this
     // kernel on the 128-channel layers and up to 24 % on 64 -> 32 / 32 -> 32 (profiles/r05_bench_wino_ws.log) -- compiled into the tools library only, for A/B runs (knob 14 = 31).
     if (PIV_KNOB(14) == 31 && conv_wino_ws_items(p) > 0) return launch_conv_w_ws(p, st);
 #endif
-#ifdef PIVLFN_TOOLS
-    // A/B of the tile shapes (tools/bench_wino.py --masks): two or four channel blocks per wave halve / quarter the transform's
-    // vector work per MFMA but run one workgroup per CU (16 accumulators) or spill (1 x 2): measured slower, see DESIGN.md
-    const int force = PIV_KNOB(14);
-    if (force == 22 && nb % 2 == 0) return launch_w<2, 2>(p, st);
-    if (force == 14 && nb % 4 == 0) return launch_w<1, 4>(p, st);
-    if (force == 21) return launch_w<2, 1>(p, st);
-    if (force == 11) mb = 1;
-#endif
-    // two channel blocks per wave (half the transform work per MFMA, one weight set) wherever the layer has an even number of
-    // 32-channel blocks: -4...-5 % against 16-row tiles with one block per wave on every such layer of levels 1 and 2
-    if (nb % 2 == 0 && sp1 * (nb / 2) >= 256) return launch_w<1, 2>(p, st);
-    if (mb == 2) return launch_w<2, 1>(p, st);
-    return launch_w<1, 1>(p, st);
+    return ch.run(p, st);
 }
 
 }  // namespace pivlfn

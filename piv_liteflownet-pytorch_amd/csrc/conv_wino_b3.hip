@@ -720,26 +720,38 @@ void pack_conv_wb(const float *w, int cout, int cin, const int *creal, const int
 // The layers this kernel takes: whole 64-channel groups (the 32- and 96-channel layers stay on conv_wino.hip)
 bool conv_wino_b3_supports(int cout_pad) { return cout_pad % 64 == 0; }
 
+// One instantiation: plan = its bound and its grid on a device of `cus` compute units (part of choose_conv_wb), run = the launch
+// of pl.blocks workgroups
 template <int TERMS>
-static int launch_b3(const ConvParamsW &p, hipStream_t st)
-{
-    const size_t lds = (size_t)BLDS_QUADS * 16;
-    static LdsAttr attr;
-    if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_wino_b3_kernel<TERMS>), (int)lds)) return rc;
-    const long tiles = (long)p.B * cdiv(p.H, 16) * cdiv(p.W, 16) * (p.cout_pad / 64);
-    PIV_REQUIRE(tiles < (1L << 31), "conv_wino_b3: too many tiles");
-    const long blocks = std::min<long>(tiles, device_cus());      // persistent: one workgroup per CU walks its share of the tiles
-    hipLaunchKernelGGL((conv_wino_b3_kernel<TERMS>), dim3((unsigned)blocks), dim3(256), lds, st, p);
-    PIV_CHECK_HIP(hipGetLastError());
-    return PIVLFN_OK;
-}
+struct launch_b3 {
+    static int plan(const ConvParamsW &p, int cus, ConvKernelPlan &pl)
+    {
+        const long tiles = (long)p.B * cdiv(p.H, 16) * cdiv(p.W, 16) * (p.cout_pad / 64);
+        PIV_REQUIRE(tiles < (1L << 31), "conv_wino_b3: too many tiles");
+        pl.kernel = PIVLFN_KERNEL_PLAN_WINO_B3; pl.terms = TERMS; pl.rows = 16; pl.chans = 64; pl.occ = 1;
+        pl.blocks = (int)std::min<long>(tiles, cus);      // persistent: one workgroup per CU walks its share of the tiles
+        return PIVLFN_OK;
+    }
+    static int run(const ConvParamsW &p, int blocks, hipStream_t st)
+    {
+        const size_t lds = (size_t)BLDS_QUADS * 16;
+        static LdsAttr attr;
+        if (int rc = ensure_dyn_lds(attr, reinterpret_cast<const void *>(conv_wino_b3_kernel<TERMS>), (int)lds)) return rc;
+        hipLaunchKernelGGL((conv_wino_b3_kernel<TERMS>), dim3((unsigned)blocks), dim3(256), lds, st, p);
+        PIV_CHECK_HIP(hipGetLastError());
+        return PIVLFN_OK;
+    }
+};
 
-// p.wpk_b = pack_conv_wb's array, p.nchunk = its K steps of 16 channels, p.terms = 6, 8 or 9 piece products per product
-int launch_conv_wb(const ConvParamsW &p_in, hipStream_t st)
+// The choice, from the geometry and the CU count alone (no pointer is looked at, no device asked).
+// p.nchunk = pack_conv_wb's K steps of 16 channels, p.terms = 6, 8 or 9 piece products per product
+int choose_conv_wb(const ConvParamsW &p, int cus, ConvChoiceB3 &ch)
 {
-    ConvParamsW p = p_in;
-    p.stamps = reinterpret_cast<unsigned long long *>(((unsigned long long)(unsigned)PIV_KNOB(6) << 32) | (unsigned)PIV_KNOB(5));   // tools only (0 in production)
-    PIV_REQUIRE(p.nseg >= 1 && p.nseg <= 3 && p.wpk_b && p.bias && p.out, "conv_wino_b3: bad arguments");
+    ch.run = nullptr;
+    ch.pl = ConvKernelPlan{};
+    ch.pl.ksplit = 1;
+    PIV_REQUIRE(cus >= 1, "conv_wino_b3: %d compute units", cus);
+    PIV_REQUIRE(p.nseg >= 1 && p.nseg <= 3, "conv_wino_b3: bad arguments");
     PIV_REQUIRE(p.cout_pad % 64 == 0 && p.cout_store <= p.cout_pad && p.cout_store % 4 == 0 && p.out_stride % 4 == 0,
                 "conv_wino_b3: cout_pad=%d cout_store=%d out_stride=%d", p.cout_pad, p.cout_store, p.out_stride);
     PIV_REQUIRE(p.B > 0 && p.H > 0 && p.W > 0 && (long)p.B * p.H * p.W < (1L << 31), "conv_wino_b3: bad shape");
@@ -748,19 +760,32 @@ int launch_conv_wb(const ConvParamsW &p_in, hipStream_t st)
     PIV_REQUIRE((long)16 * p.W * p.out_stride * 4 < (1L << 31), "conv_wino_b3: 16 output rows exceed 2 GiB");
     int nstep = 0;
     for (int s = 0; s < p.nseg; ++s) {
-        PIV_REQUIRE(p.seg[s].cload % 4 == 0 && p.seg[s].stride % 4 == 0 && p.seg[s].ptr, "conv_wino_b3: segment %d misaligned", s);
+        PIV_REQUIRE(p.seg[s].cload % 4 == 0 && p.seg[s].stride % 4 == 0, "conv_wino_b3: segment %d misaligned", s);
         nstep += (p.seg[s].cload + 15) / 16;
     }
     nstep = std::max(nstep, 2);
     PIV_REQUIRE(nstep == p.nchunk, "conv_wino_b3: segments hold %d steps, weights were packed for %d", nstep, p.nchunk);
     PIV_REQUIRE((size_t)p.nchunk * (p.cout_pad / 64) * 4 * BWAVE * 16 < ((size_t)1 << 32), "conv_wino_b3: packed weights exceed 4 GiB");
+    const auto take = [&](auto l) { ch.run = &decltype(l)::run; return decltype(l)::plan(p, cus, ch.pl); };
     switch (p.terms) {
-        case 6: return launch_b3<6>(p, st);
-        case 8: return launch_b3<8>(p, st);
-        case 9: return launch_b3<9>(p, st);
+        case 6: return take(launch_b3<6>());
+        case 8: return take(launch_b3<8>());
+        case 9: return take(launch_b3<9>());
         default: PIV_REQUIRE(false, "conv_wino_b3: terms=%d (6, 8 or 9)", p.terms);
     }
     return PIVLFN_OK;
+}
+
+// p.wpk_b = pack_conv_wb's array
+int launch_conv_wb(const ConvParamsW &p_in, hipStream_t st)
+{
+    ConvParamsW p = p_in;
+    p.stamps = reinterpret_cast<unsigned long long *>(((unsigned long long)(unsigned)PIV_KNOB(6) << 32) | (unsigned)PIV_KNOB(5));   // tools only (0 in production)
+    ConvChoiceB3 ch;
+    if (int rc = choose_conv_wb(p, device_cus(), ch)) return rc;
+    PIV_REQUIRE(p.wpk_b && p.bias && p.out, "conv_wino_b3: bad arguments");
+    for (int s = 0; s < p.nseg; ++s) PIV_REQUIRE(p.seg[s].ptr, "conv_wino_b3: segment %d misaligned", s);
+    return ch.run(p, ch.pl.blocks, st);
 }
 
 }  // namespace pivlfn

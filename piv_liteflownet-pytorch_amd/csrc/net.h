@@ -173,8 +173,17 @@ int conv(const ConvCtx &ctx, const ConvW &cw, const ConvCall &c, hipStream_t st)
 ConvParams conv_params(const ConvW &cw, const ConvCall &c);
 
 // A single-source layer's shape as pivlfn_conv_create packs it, and pivlfn_conv2d_nhwc's kernel choice for a call of it
-struct ConvShape { int cout, cout_pad, cin, KH, KW, nchunk, tail; bool col7, row7; };
+// nchunk_h / _x / _w, nstep_wb: the K chunks of the fp16, split and Winograd packings; split, split_tail, wino, wino_b3: whether the layer
+// gets the split packing, its folded 4-lane tail, the Winograd packing, its three-piece bf16 form
+struct ConvShape {
+    int cout, cout_pad, cin, KH, KW, nchunk, tail;
+    bool col7, row7;
+    int nchunk_h, nchunk_x, nchunk_w, nstep_wb;
+    bool split, split_tail, wino, wino_b3;
+};
 ConvShape conv_shape(int cout, int cin, int kh, int kw);
+int conv_kernel_plan(int kernel, int cout, int cin, int kh, int kw, int B, int H, int W, int stride, int pad_y, int pad_x, int terms,
+                     int x_f16, int x_stride, int y_stride, int cus, ConvKernelPlan &pl);
 int conv_forward_choose(const ConvShape &c, int x_stride, int y_stride, const float *res, int B, int H, int W, int stride, int pad_y,
                         int pad_x, int leaky, ConvParams &p, ConvPlan &pl, bool &per_image);
 

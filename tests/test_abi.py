@@ -50,11 +50,12 @@ def test_argument_errors_are_reported_without_a_gpu():
 
 NEW_OPS = ("pivlfn_upconv_nhwc", "pivlfn_backwarp_nhwc", "pivlfn_reg_prep", "pivlfn_reg_tail", "pivlfn_prep_pyramid",
            "pivlfn_conv1_fused_nhwc")
+PLAN_OPS = ("pivlfn_conv2d_nhwc_plan", "pivlfn_conv2d_nhwc_kernel_plan")      # host only: no handle, no stream, nothing launched
 
 
 def test_per_layer_entry_points_are_declared():
     names = _declared()
-    for must in NEW_OPS:
+    for must in NEW_OPS + PLAN_OPS:
         assert must in names
 
 
@@ -109,3 +110,9 @@ def test_per_layer_entry_points_reject_bad_arguments_without_a_gpu():
     refused(lib.pivlfn_conv1_fused_nhwc(*args, 70000, 40000, 64, 1, ctypes.byref(fused), None), "32-bit index range")
     with pytest.raises(ValueError):
         _lib.check(lib.pivlfn_reg_tail(P, 12, P, P, P, 0.0, 0.0, 5, P, P, 1.0, 1, 4, 4, None), "reg_tail")
+    # the launchers' plans: answered on the host, refused like the entry point asked about
+    plan = (ctypes.c_int * 10)()
+    assert lib.pivlfn_conv2d_nhwc_kernel_plan(2, 64, 32, 3, 3, 1, 64, 64, 1, 1, 1, 3, 0, 32, 64, 256, plan) == 0 and plan[0] == 2
+    refused(lib.pivlfn_conv2d_nhwc_kernel_plan(2, 64, 32, 3, 3, 1, 64, 64, 1, 1, 1, 5, 0, 32, 64, 256, plan), "conv2d_split", "terms=5")
+    refused(lib.pivlfn_conv2d_nhwc_kernel_plan(0, 64, 32, 3, 3, 1, 64, 64, 1, 1, 1, 3, 0, 32, 64, 256, plan), "kernel=0")
+    refused(lib.pivlfn_conv2d_nhwc_kernel_plan(2, 64, 32, 3, 3, 1, 64, 64, 1, 1, 1, 3, 0, 32, 64, 256, None), "conv2d_kernel_plan")

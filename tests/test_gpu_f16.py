@@ -16,24 +16,27 @@ import torch.nn.functional as F
 import pivlfn
 import pivlfn_oracle as orc
 from pivlfn import _lib, synth
+from test_conv_kernel_plans import F16, POLICY, inst, kplan
 
 pytestmark = pytest.mark.gpu
 
-# cout, cin, kh, kw, stride, B, H, W
-LAYERS = [(128, 128, 3, 3, 1, 2, 256, 256),    # <4,4> 16-row tiles, one workgroup per CU
-          (128, 128, 3, 3, 1, 1, 64, 96),      # <2,4>
-          (64, 128, 3, 3, 1, 2, 256, 256),     # <4,2>
-          (64, 64, 3, 3, 1, 1, 72, 100),       # <2,2>, ragged edges
-          (32, 64, 3, 3, 1, 4, 256, 256),      # <4,1>
-          (32, 32, 3, 3, 1, 1, 37, 45),        # <2,1>, ragged
-          (128, 130, 3, 3, 1, 1, 64, 64),      # K not a multiple of 16 (the 130-channel Subpixel input)
-          (32, 3, 7, 7, 1, 1, 96, 128),        # NetC.conv1
-          (64, 32, 3, 3, 2, 1, 128, 160),      # stride 2
-          (192, 128, 3, 3, 2, 1, 64, 64),      # stride 2, cout 192 -> two 64-wide... (cout_pad 192: nt=2)
-          (64, 32, 1, 1, 1, 1, 128, 128),      # 1x1 (NetC_ext)
-          (49, 32, 7, 1, 1, 1, 96, 96),        # separable k x 1, cout 49 -> stored as 52 lanes
-          (49, 49, 1, 7, 1, 1, 96, 96),        # 1 x k with a 52-lane source
-          (25, 32, 5, 1, 1, 1, 64, 64)]
+# cout, cin, kh, kw, stride, B, H, W; then the launch_h<MT, NT, PM, WM> instantiation the layer runs on (rows 4 MT, channels 32 NT),
+# asserted on pivlfn_conv2d_nhwc_kernel_plan.  Every instantiation at its edges: tests/test_gpu_conv_kernel_tiles.py
+LAYERS = [(128, 128, 3, 3, 1, 2, 256, 256, (4, 4, 5, 9)),  # 16-row tiles, one workgroup per CU
+          (128, 128, 3, 3, 1, 1, 64, 96, (2, 4, 5, 9)),
+          (64, 128, 3, 3, 1, 2, 256, 256, (2, 2, 5, 9)),   # 64 channels stay on 8-row tiles at any size (16 rows: a tools-build knob)
+          (64, 64, 3, 3, 1, 1, 72, 100, (2, 2, 5, 9)),     # ragged edges
+          (32, 64, 3, 3, 1, 4, 256, 256, (4, 1, 5, 9)),
+          (32, 32, 3, 3, 1, 1, 37, 45, (2, 1, 5, 9)),      # ragged
+          (128, 130, 3, 3, 1, 1, 64, 64, (2, 4, 5, 9)),    # K not a multiple of 16 (the 130-channel Subpixel input)
+          (32, 3, 7, 7, 1, 1, 96, 128, (2, 1, 9, 13)),     # NetC.conv1
+          (64, 32, 3, 3, 2, 1, 128, 160, (2, 2, 9, 13)),   # stride 2
+          (192, 128, 3, 3, 2, 1, 64, 64, (2, 2, 9, 13)),   # stride 2, cout 192: three 64-channel blocks
+          (128, 96, 3, 3, 2, 1, 64, 64, (2, 4, 9, 13)),    # stride 2, 128 channels (NetC.conv5.0)
+          (64, 32, 1, 1, 1, 1, 128, 128, (2, 2, 5, 9)),    # 1x1 (NetC_ext)
+          (49, 32, 7, 1, 1, 1, 96, 96, (2, 2, 9, 13)),     # separable k x 1, cout 49 -> stored as 52 lanes
+          (49, 49, 1, 7, 1, 1, 96, 96, (2, 2, 9, 13)),     # 1 x k with a 52-lane source
+          (25, 32, 5, 1, 1, 1, 64, 64, (2, 1, 9, 13))]
 
 
 def _ref(x16, w16, b, stride, kh, kw, leaky):
@@ -44,12 +47,13 @@ def _ref(x16, w16, b, stride, kh, kw, leaky):
 @pytest.mark.parametrize("layer", LAYERS, ids=[f"{c[0]}x{c[1]}k{c[2]}x{c[3]}s{c[4]}_{c[5]}x{c[6]}x{c[7]}" for c in LAYERS])
 @pytest.mark.parametrize("x_f16,y_f16", [(0, 0), (1, 1)])
 def test_conv_f16_kernel_is_exact_up_to_summation_order(layer, x_f16, y_f16, dev):
-    co, ci, kh, kw, s, B, H, W = layer
+    co, ci, kh, kw, s, B, H, W, launch_h = layer
     g = torch.Generator().manual_seed(co * 1000 + ci * 10 + kh + s + H)
     w = (torch.randn(co, ci, kh, kw, generator=g) / (ci * kh * kw) ** 0.5).contiguous()
     b = torch.randn(co, generator=g).contiguous()
     gran = 8 if x_f16 else 4
     xs = -(-ci // gran) * gran
+    assert inst(kplan(F16, co, ci, kh, kw, s, (kh // 2, kw // 2), H, W, B, x16=x_f16)) == ("launch_h", launch_h), POLICY
     x = torch.randn(B, H, W, xs, generator=g)
     x[..., ci:] = 0.0
     lib = _lib.load()

@@ -26,7 +26,6 @@ from pivlfn.synth import MODEL_CFG
 import net_ops_reference as ref
 from guarded import KINDS, check_guards, check_lanes, guarded, poison, same_bits
 from test_gpu_conv import Conv
-from test_gpu_f16 import _ref as f16_ref
 from test_gpu_net_ops import OP_BAR, WARP_BAR, _nhwc, _within
 from test_gpu_wino import CAT_CASES
 from stereo_restatement import restate
@@ -66,8 +65,14 @@ def _launch(kernel, conv, x, xs, y, ys, B, H, W, s, pad, leaky, dev, res=None, t
     _lib.check(rc, kernel)
 
 
-def _conv_case(kernel, case, dev, terms=6, x16=0):
+def _conv64(x, w, b, s, pad, on):
+    """torch's float64 convolution, on the CPU or -- for the cases that take the CPU many seconds -- on the device"""
+    return F.conv2d(x.double().to(on), w.double().to(on), b.double().to(on), stride=s, padding=pad).cpu()
+
+
+def _conv_case(kernel, case, dev, terms=6, x16=0, ref_on_device=False):
     """case: cout, cin, kh, kw, stride, pad, H, W, B, x lanes past roundup(cin), y lanes past roundup(cout, 4), residual.
+    ref_on_device: the float64 reference is computed by torch on the GPU (the same torch convolution; not the library under test).
     Returns the layer, its inputs and the plain call's result for the tests that go on with them (tests/test_gpu_conv_tiles.py)."""
     co, ci, kh, kw, s, pad, H, W, B, xextra, yextra, with_res = case
     g = torch.Generator().manual_seed(co * 1000 + ci + kh * 7 + H + B + terms + 3 * x16)
@@ -116,11 +121,13 @@ def _conv_case(kernel, case, dev, terms=6, x16=0):
         return yd[..., :co].cpu()
 
     plain = call(None)
+    on = dev if ref_on_device else "cpu"
     if kernel == "f16":
-        want = f16_ref(x.half().float(), w.half().float(), b, s, kh, kw, True)      # fp32 x too is rounded to fp16 when staged
+        assert pad == (kh // 2, kw // 2) and leaky
+        want = F.leaky_relu(_conv64(x.half(), w.half(), b, s, pad, on), 0.1)      # test_gpu_f16.py::_ref; fp32 x too is rounded to fp16 when staged
         bar = 2e-5
     else:
-        want = F.conv2d(x.double(), w.double(), b.double(), stride=s, padding=pad)
+        want = _conv64(x, w, b, s, pad, on)
         if with_res:
             want = want + res.double()
         want = F.leaky_relu(want, 0.1) if leaky else want

@@ -21,27 +21,33 @@ import torch.nn.functional as F
 import pivlfn
 import pivlfn_oracle as orc
 from pivlfn import _lib, synth
+from test_conv_kernel_plans import POLICY, SPLIT, inst, kplan
 
 pytestmark = pytest.mark.gpu
 
-# cout, cin, kh, kw, B, H, W
-LAYERS = [(128, 128, 3, 3, 1, 128, 128),   # <2,2> twice over the channels
-          (128, 128, 3, 3, 2, 272, 1024),  # enough 16-row tiles for the one-workgroup-per-CU kernel (three terms), ragged in y
-          (64, 132, 3, 3, 1, 544, 512),    # the same with 64 channels and a 4-channel K tail
-          (256, 96, 3, 3, 1, 256, 544),    # two 128-channel blocks
-          (128, 100, 3, 3, 1, 530, 500),   # the same kernel with ragged tiles in x and y and a 4-channel K tail
-          (64, 128, 3, 3, 2, 64, 96),
-          (64, 64, 3, 3, 1, 72, 100),      # ragged edges
-          (32, 64, 3, 3, 1, 64, 64),       # <2,1>
-          (32, 32, 3, 3, 1, 37, 45),       # ragged
-          (128, 49, 3, 3, 1, 64, 64),      # conv_M.0: 49 channels in 52 lanes, K padded to 64
-          (128, 130, 3, 3, 1, 64, 64),     # 130 channels: 8 full chunks + a chunk of 2 (+2 zero lanes)
-          (64, 32, 1, 1, 1, 128, 128),     # 1x1 (NetC_ext)
-          (128, 32, 1, 1, 1, 64, 64),      # 1x1 (moduleFeat)
-          (49, 32, 7, 1, 1, 96, 96),       # separable k x 1, cout 49 -> 52 lanes
-          (49, 49, 1, 7, 1, 96, 96),       # 1 x k with a 52-lane source
-          (25, 32, 5, 5, 1, 64, 64),       # 5 x 5 (conv_dist_R.0 of the Hui layout)
-          (9, 32, 3, 3, 1, 64, 64)]
+# cout, cin, kh, kw, B, H, W; then the kernel the layer runs on at six and at three terms, asserted on pivlfn_conv2d_nhwc_kernel_plan:
+# launch_x<terms, MT, NT, PM, WM, workgroups per CU> (rows 4 MT, channels 32 NT) or launch_xbig<NT>, and the split-K shares.
+# Every instantiation at its edges: tests/test_gpu_conv_kernel_tiles.py
+X, BIG = "launch_x", "launch_xbig"
+LAYERS = [(128, 128, 3, 3, 1, 128, 128, (X, (6, 2, 2, 3, 5, 2), 1), (X, (3, 1, 2, 2, 3, 4), 1)),    # 64-channel tiles, two over the channels
+          # enough 16-row tiles for the one-workgroup-per-CU kernel (three terms), ragged in y
+          (128, 128, 3, 3, 2, 272, 1024, (X, (6, 2, 2, 3, 5, 2), 1), (BIG, (4,), 1)),
+          (64, 132, 3, 3, 1, 544, 512, (X, (6, 2, 2, 3, 5, 2), 1), (BIG, (2,), 1)),      # the same with 64 channels and a folded 4-channel K tail
+          (256, 96, 3, 3, 1, 256, 544, (X, (6, 2, 2, 3, 5, 2), 1), (BIG, (4,), 1)),      # two 128-channel blocks
+          # the same kernel with ragged tiles in x and y and a folded 4-channel K tail
+          (128, 100, 3, 3, 1, 530, 500, (X, (6, 2, 2, 3, 5, 2), 1), (BIG, (4,), 1)),
+          (64, 128, 3, 3, 2, 64, 96, (X, (6, 2, 2, 3, 5, 2), 1), (X, (3, 1, 2, 2, 3, 4), 8)),      # a batch on a small grid: image by image
+          (64, 64, 3, 3, 1, 72, 100, (X, (6, 2, 2, 3, 5, 2), 1), (X, (3, 1, 2, 2, 3, 4), 4)),      # ragged edges
+          (32, 64, 3, 3, 1, 64, 64, (X, (6, 2, 1, 3, 3, 2), 1), (X, (3, 1, 1, 2, 2, 4), 4)),
+          (32, 32, 3, 3, 1, 37, 45, (X, (6, 2, 1, 3, 3, 2), 1), (X, (3, 1, 1, 2, 2, 4), 2)),       # ragged
+          (128, 49, 3, 3, 1, 64, 64, (X, (6, 2, 2, 3, 5, 2), 1), (X, (3, 1, 2, 2, 3, 4), 4)),      # conv_M.0: 49 channels in 52 lanes, K padded to 64
+          (128, 130, 3, 3, 1, 64, 64, (X, (6, 2, 2, 3, 5, 2), 1), (X, (3, 1, 2, 2, 3, 4), 8)),     # 130 channels: 8 full chunks + a chunk of 2 (+2 zero lanes)
+          (64, 32, 1, 1, 1, 128, 128, (X, (6, 2, 2, 3, 5, 2), 1), (X, (3, 1, 2, 2, 3, 4), 2)),     # 1x1 (NetC_ext)
+          (128, 32, 1, 1, 1, 64, 64, (X, (6, 2, 2, 3, 5, 2), 1), (X, (3, 1, 2, 2, 3, 4), 2)),      # 1x1 (moduleFeat)
+          (49, 32, 7, 1, 1, 96, 96, (X, (6, 2, 2, 5, 5, 2), 1), (X, (3, 2, 2, 5, 3, 2), 2)),       # separable k x 1, cout 49 -> 52 lanes
+          (49, 49, 1, 7, 1, 96, 96, (X, (6, 2, 2, 5, 11, 2), 1), (X, (3, 2, 2, 5, 7, 2), 4)),      # 1 x k with a 52-lane source
+          (25, 32, 5, 5, 1, 64, 64, (X, (6, 2, 1, 5, 6, 2), 1), (X, (3, 2, 1, 5, 4, 2), 2)),       # 5 x 5 (conv_dist_R.0 of the Hui layout)
+          (9, 32, 3, 3, 1, 64, 64, (X, (6, 2, 1, 3, 3, 2), 1), (X, (3, 1, 1, 2, 2, 4), 2))]
 
 
 def _run(lib, h, fn, x, xs, co, B, H, W, kh, kw, dev, terms=6):
@@ -88,7 +94,10 @@ def _layer_errors(layer, dev, wscale=1.0, xscale=1.0, mixed=False, terms=6):
 @pytest.mark.parametrize("terms", [6, 3])
 @pytest.mark.parametrize("layer", LAYERS, ids=[f"{c[0]}x{c[1]}k{c[2]}x{c[3]}_{c[4]}x{c[5]}x{c[6]}" for c in LAYERS])
 def test_split_kernel_has_the_fp32_kernels_error(layer, terms, dev):
-    es, ef, ms, mf = _layer_errors(layer, dev, terms=terms)
+    co, ci, kh, kw, B, H, W = layer[:7]
+    plan = kplan(SPLIT, co, ci, kh, kw, 1, (kh // 2, kw // 2), H, W, B, terms)
+    assert inst(plan) + (plan[6],) == layer[7 if terms == 6 else 8], POLICY
+    es, ef, ms, mf = _layer_errors(layer[:7], dev, terms=terms)
     print(f"{terms} terms, max-abs error / max|out| against float64: split {es:.2e}, fp32 instruction {ef:.2e}; mean {ms:.2e} vs {mf:.2e}")
     assert es < 2e-5, es                                        # the fp32 kernel's own bar (tests/test_gpu_conv.py)
     assert ms < 2.0 * mf + 1e-9, (ms, mf)                       # and on average no worse than twice the fp32 instruction's

@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from pivlfn import _lib
+from test_conv_kernel_plans import POLICY, WINO, inst, kplan
 from test_gpu_conv import Conv, run as run_direct
 
 pytestmark = pytest.mark.gpu
@@ -142,14 +143,17 @@ def test_wino_error_beside_the_direct_kernel(dev):
 
 def test_wino_wide_lanes_and_batch_invariance(dev):
     """Input living in a wider tensor, output into a wider tensor; a sample's bits do not depend on its batch mates or on the tile
-    shape the launch picks (8-row blocks for small launches, 16-row blocks for large ones)."""
+    shape the launch picks: here two channel blocks per wave (launch_w<1, 2>, from 256 workgroups of them) against one (launch_w<1, 1>),
+    asserted on the launcher's plan.  8- against 16-row blocks: tests/test_gpu_conv_kernel_tiles.py."""
     g = torch.Generator().manual_seed(5)
     w = torch.randn(64, 32, 3, 3, generator=g) / 17
     b = torch.randn(64, generator=g)
     conv = Conv(w, b)
-    x = torch.randn(40, 32, 64, 64, generator=g)          # 40 x 4 x 4 x 2 = 1280 16-row blocks -> MB = 2
+    x = torch.randn(40, 32, 64, 64, generator=g)          # 40 x 8 x 4 = 1280 8-row blocks of 64 channels
     full = run_wino(conv, x, True, dev, x_lanes=40, y_lanes=72)
-    one = run_wino(conv, x[7:8], True, dev, x_lanes=40, y_lanes=72)      # 32 blocks -> MB = 1
+    one = run_wino(conv, x[7:8], True, dev, x_lanes=40, y_lanes=72)      # 32 of them: two workgroups each, of 32 channels
+    for B, launch_w in ((40, (1, 2)), (1, (1, 1))):
+        assert inst(kplan(WINO, 64, 32, 3, 3, 1, (1, 1), 64, 64, B, xs=40, ys=72)) == ("launch_w", launch_w), POLICY
     assert torch.equal(one[0], full[7])
     want = F.leaky_relu(F.conv2d(x[7:8].double(), w.double(), b.double(), padding=1), 0.1)
     assert (one.double() - want).abs().max().item() < 1e-5 * want.abs().max().item()
