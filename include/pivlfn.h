@@ -36,7 +36,7 @@ typedef struct {
 
 const char *pivlfn_last_error(void);
 /* ABI version.  3 (round 6): + pivlfn_conv2d_nhwc_wino_b3, PIVLFN_PRECISION_F32_WINO_MFMA32; - pivlfn_conv2d_nhwc_wino4 (now exported by the tools build only).  2 (round 4): + pivlfn_warp_corr_nhwc_timed, pivlfn_conv2d_nhwc_wino4, pivlfn_conv_create_cat, pivlfn_conv2d_nhwc_cat; since 1 also pivlfn_conv2d_nhwc_wino and PIVLFN_PRECISION_F32_DIRECT
- * (added in round 3 without a bump); since 3 also the host-only pivlfn_conv2d_nhwc_plan and pivlfn_conv2d_nhwc_kernel_plan.  No entry point of version 1 changed its signature or meaning. */
+ * (added in round 3 without a bump); since 3 also the host-only pivlfn_conv2d_nhwc_plan, pivlfn_conv2d_nhwc_kernel_plan and pivlfn_conv_head_nhwc_plan.  No entry point of version 1 changed its signature or meaning. */
 int         pivlfn_abi_version(void);
 
 /* The library keeps no process-global mutable state: entry points may be called concurrently from several threads, on
@@ -902,9 +902,21 @@ int pivlfn_conv2d_nhwc_cat(const pivlfn_conv *conv, int nsrc, const float *const
                            int B, int H, int W, int leaky, void *stream);
 
 /* The 32 -> 2 channel k x k flow head (conv_M.6 / conv_S.6) on its dedicated kernel: x [B,H,W,32], res4/out4 [B,H,W,4].  Lanes 2-3
- * of res4 are not read (pivlfn_forward's flow4 holds zeros there); lanes 2-3 of out4 are written as +0.0. */
+ * of res4 are not read (pivlfn_forward's flow4 holds zeros there); lanes 2-3 of out4 are written as +0.0.  res4 may be NULL: no
+ * residual is added (pivlfn_forward's coarsest level, which has no flow to refine); the bits are those of a residual of +0.0. */
 int pivlfn_conv_head_nhwc(const pivlfn_conv *conv, const float *x, const float *res4, float *out4, int B, int H, int W,
                           void *stream);
+/* Which kernel pivlfn_conv_head_nhwc runs for a k x k head (k = 3, 5, 7) on B images of H x W: the launcher's own decision, made on
+ * the host -- nothing is launched, no handle and no GPU is needed.  plan[0] the kernel family, plan[1] / plan[2] the output rows /
+ * columns of one workgroup's tile (16 x 16, 16 x 16, 32 x 32, 8 x 58), plan[3] the workgroups of the launch.
+ * Returns PIVLFN_ERR_ARG, with the same message, for everything pivlfn_conv_head_nhwc refuses for that geometry (its pointers apart).
+ * The family depends on the size of one image alone, never on B: the families sum in different orders, and a pair's flow must not
+ * depend on its batch mates (tests/test_conv_head_plan.py, tests/test_gpu_conv_head.py).  Added without an ABI bump (additive). */
+#define PIVLFN_HEAD_PLAN_PIXEL_LDS 1   /* conv_head_kernel<k, true>: one pixel per lane, weights in LDS; at most 512 tiles of 16 x 16 per image */
+#define PIVLFN_HEAD_PLAN_PIXEL     2   /* conv_head_kernel<k, false>: the same with the weights through the scalar cache; same bits */
+#define PIVLFN_HEAD_PLAN_ROWS4     3   /* conv_head4_kernel<k>: four rows per lane; images of >= 512 x 512 pixels that MFMA does not take */
+#define PIVLFN_HEAD_PLAN_MFMA      4   /* conv_head_mfma_kernel<7, 8>: k = 7, images of >= 256 x 256 pixels and < 2^31 bytes of input */
+int pivlfn_conv_head_nhwc_plan(int k, int B, int H, int W, int plan[4]);
 
 /* ---- per-layer checks: the level-pipeline ops that otherwise run only inside pivlfn_forward, each on the kernel and with the
  * weight packing pivlfn_forward uses, exported so that every kernel can be checked on its own (tests/test_gpu_net_ops.py).  Not a

@@ -109,6 +109,15 @@ int pivlfn_conv2d_nhwc_kernel_plan(int kernel, int cout, int cin, int kh, int kw
     return PIVLFN_OK;
 }
 
+int pivlfn_conv_head_nhwc_plan(int k, int B, int H, int W, int plan[4])
+{
+    PIV_REQUIRE(plan, "conv_head_plan: bad arguments");
+    HeadPlan pl;
+    if (int rc = choose_conv_head(k, B, H, W, 0, pl)) return rc;
+    plan[0] = pl.family; plan[1] = pl.rows; plan[2] = pl.cols; plan[3] = pl.blocks;
+    return PIVLFN_OK;
+}
+
 int pivlfn_backwarp(const float *in, const float *flow, float *out, int B, int C, int H, int W, void *stream)
 {
     return launch_backwarp_nchw(in, flow, out, B, C, H, W, (hipStream_t)stream);

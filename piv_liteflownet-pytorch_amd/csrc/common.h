@@ -257,6 +257,10 @@ int check_conv_col7(int x_stride, int out_stride, int cout_store, int single48, 
 int check_conv_row7(int x_stride, int out_stride, int B, int H, int W);                                  // pointers apart
 int launch_conv_head(const float *x, const float *w, float b0, float b1, const float *res4, float *out4, int B, int H, int W,
                      int k, hipStream_t st);
+// What launch_conv_head runs for a call (pivlfn_conv_head_nhwc_plan): kernel family (PIVLFN_HEAD_PLAN_*), output rows and columns of a
+// workgroup's tile, workgroups of the launch.  The launcher's decision from the geometry alone; exclude = 0: the shipped policy.
+struct HeadPlan { int family, rows, cols, blocks; };
+int choose_conv_head(int k, int B, int H, int W, unsigned exclude, HeadPlan &pl);
 
 // ---- warp + correlation (warp_corr.hip) ------------------------------------------------------------
 int launch_warp_corr(const float *f1, const float *f2, const float *flow, float flow_scale, float *out,

@@ -583,10 +583,42 @@ int launch_conv_row7(const float *x, int x_stride, const float *wf, const float 
     return PIVLFN_OK;
 }
 
+// Which kernel a k x k head on a batch of B images of H x W runs, from the geometry alone: no pointer is read and no device is touched,
+// so pivlfn_conv_head_nhwc_plan reports exactly what launch_head_t launches.  Everything launch_conv_head refuses apart from its pointers
+// is refused here.  The choice is made per IMAGE size, never per batch: a pair's flow must not depend on its batch mates (the four-row
+// kernel and the matrix-core kernel sum in other orders than the two one-pixel variants, which produce the same bits as each other).
+// exclude: families a tools build's knobs rule out (bits 1 << PIVLFN_HEAD_PLAN_*; PIXEL cannot be excluded); 0 is the shipped policy.
+int choose_conv_head(int k, int B, int H, int W, unsigned exclude, HeadPlan &pl)
+{
+    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "conv_head: bad arguments");
+    PIV_REQUIRE(k == 3 || k == 5 || k == 7, "conv_head: k=%d unsupported", k);
+    const long px = (long)H * W;
+    const auto allowed = [&](int family) { return !(exclude & (1u << family)); };
+    const auto tiles = [&](long rows, long cols) { return ((H + rows - 1) / rows) * ((W + cols - 1) / cols); };      // of one image
+    if (k == 7 && px >= 256 * 256 && px * 32 * 4 < (1L << 31) && allowed(PIVLFN_HEAD_PLAN_MFMA))
+        // 7 x 7 heads on images of at least 256 x 256: the matrix-core formulation, while its 32-bit buffer offsets span the image
+        pl = {PIVLFN_HEAD_PLAN_MFMA, 8, 64 - 2 * (k / 2), 0};
+    else if (px >= 512 * 512 && allowed(PIVLFN_HEAD_PLAN_ROWS4))
+        pl = {PIVLFN_HEAD_PLAN_ROWS4, 32, 32, 0};
+    else if (tiles(16, 16) <= 512 && allowed(PIVLFN_HEAD_PLAN_PIXEL_LDS))
+        pl = {PIVLFN_HEAD_PLAN_PIXEL_LDS, 16, 16, 0};      // few workgroups: the weights through LDS
+    else
+        pl = {PIVLFN_HEAD_PLAN_PIXEL, 16, 16, 0};
+    const long blocks = tiles(pl.rows, pl.cols) * B;      // <= 2^31 * 2^31 / 256: no overflow
+    PIV_REQUIRE(blocks < (1L << 31), "conv_head: %ld workgroups exceed the grid's 32-bit range", blocks);
+    pl.blocks = (int)blocks;
+    return PIVLFN_OK;
+}
+
 template <int K>
 static int launch_head_t(const float *x, const float *w, float b0, float b1, const float *res4, float *out4, int B, int H, int W,
                          hipStream_t st)
 {
+    // tools build only: knob bits that rule a family out (every knob is the constant 0 in the production library)
+    const unsigned exclude = (PIV_KNOB(1) & 65536 * 8 ? 1u << PIVLFN_HEAD_PLAN_MFMA : 0u) | (PIV_KNOB(1) & 8192 ? 1u << PIVLFN_HEAD_PLAN_ROWS4 : 0u) |
+                             (PIV_KNOB(1) & 1024 ? 1u << PIVLFN_HEAD_PLAN_PIXEL_LDS : 0u);
+    HeadPlan pl;
+    if (int rc = choose_conv_head(K, B, H, W, exclude, pl)) return rc;
     constexpr int PW = 16 + K - 1;
     const size_t lds = ((size_t)PW * PW * 32 + K * K * 64) * sizeof(float);
     static LdsAttr attr_a, attr_b;
@@ -594,31 +626,27 @@ static int launch_head_t(const float *x, const float *w, float b0, float b1, con
         if (int rc = ensure_dyn_lds(attr_a, reinterpret_cast<const void *>(conv_head_kernel<K, false>), (int)lds)) return rc;
         if (int rc = ensure_dyn_lds(attr_b, reinterpret_cast<const void *>(conv_head_kernel<K, true>), (int)lds)) return rc;
     }
-    const int nblk = cdiv(W, 16) * cdiv(H, 16) * B;
-    // Kernel choice per IMAGE size, never per batch: a pair's flow must not depend on its batch mates (the four-row kernel sums
-    // in a different order than the two one-pixel variants, which produce the same bits as each other).
-    // 7 x 7 heads on images of at least 256 x 256: the matrix-core formulation (per image, never per batch)
-    if (K == 7 && (long)H * W >= 256 * 256 && (long)H * W * 32 * 4 < (1L << 31) && !(PIV_KNOB(1) & 65536 * 8)) {
-        constexpr int TWO = 64 - 2 * (K / 2);
-        constexpr int THM = 8;
-        const size_t ldsm = (size_t)(THM / 2) * 64 * 16 * sizeof(float);
-        static LdsAttr attr_m;
-        if (int rc = ensure_dyn_lds(attr_m, reinterpret_cast<const void *>(conv_head_mfma_kernel<K, THM>), (int)ldsm)) return rc;
-        hipLaunchKernelGGL((conv_head_mfma_kernel<K, THM>), dim3(cdiv(W, TWO) * cdiv(H, THM) * B), dim3(256), ldsm, st, x, w, b0, b1, res4, out4, B, H, W);
-        PIV_CHECK_HIP(hipGetLastError());
-        return PIVLFN_OK;
+    switch (pl.family) {
+        case PIVLFN_HEAD_PLAN_MFMA: {
+            constexpr int THM = 8;
+            const size_t ldsm = (size_t)(THM / 2) * 64 * 16 * sizeof(float);
+            static LdsAttr attr_m;
+            if (int rc = ensure_dyn_lds(attr_m, reinterpret_cast<const void *>(conv_head_mfma_kernel<K, THM>), (int)ldsm)) return rc;
+            hipLaunchKernelGGL((conv_head_mfma_kernel<K, THM>), dim3(pl.blocks), dim3(256), ldsm, st, x, w, b0, b1, res4, out4, B, H, W);
+            break;
+        }
+        case PIVLFN_HEAD_PLAN_ROWS4: {
+            constexpr int PW4 = 32 + K - 1;
+            hipLaunchKernelGGL((conv_head4_kernel<K>), dim3(pl.blocks), dim3(256), (size_t)PW4 * PW4 * 8 * sizeof(float), st,
+                               x, w, b0, b1, res4, out4, B, H, W);
+            break;
+        }
+        case PIVLFN_HEAD_PLAN_PIXEL_LDS:
+            hipLaunchKernelGGL((conv_head_kernel<K, true>), dim3(pl.blocks), dim3(256), lds, st, x, w, b0, b1, res4, out4, B, H, W);
+            break;
+        default:
+            hipLaunchKernelGGL((conv_head_kernel<K, false>), dim3(pl.blocks), dim3(256), lds, st, x, w, b0, b1, res4, out4, B, H, W);
     }
-    if ((long)H * W >= 512 * 512 && !(PIV_KNOB(1) & 8192)) {
-        constexpr int PW4 = 32 + K - 1;
-        hipLaunchKernelGGL((conv_head4_kernel<K>), dim3(cdiv(W, 32) * cdiv(H, 32) * B), dim3(256), (size_t)PW4 * PW4 * 8 * sizeof(float), st,
-                           x, w, b0, b1, res4, out4, B, H, W);
-        PIV_CHECK_HIP(hipGetLastError());
-        return PIVLFN_OK;
-    }
-    if (cdiv(W, 16) * cdiv(H, 16) <= 512 && !(PIV_KNOB(1) & 1024))
-        hipLaunchKernelGGL((conv_head_kernel<K, true>), dim3(nblk), dim3(256), lds, st, x, w, b0, b1, res4, out4, B, H, W);
-    else
-        hipLaunchKernelGGL((conv_head_kernel<K, false>), dim3(nblk), dim3(256), lds, st, x, w, b0, b1, res4, out4, B, H, W);
     PIV_CHECK_HIP(hipGetLastError());
     return PIVLFN_OK;
 }
@@ -627,14 +655,14 @@ static int launch_head_t(const float *x, const float *w, float b0, float b1, con
 int launch_conv_head(const float *x, const float *w, float b0, float b1, const float *res4, float *out4, int B, int H, int W,
                      int k, hipStream_t st)
 {
-    PIV_REQUIRE(x && w && out4 && B > 0 && H > 0 && W > 0, "conv_head: bad arguments");
+    PIV_REQUIRE(x && w && out4, "conv_head: bad arguments");
     switch (k) {
         case 3: return launch_head_t<3>(x, w, b0, b1, res4, out4, B, H, W, st);
         case 5: return launch_head_t<5>(x, w, b0, b1, res4, out4, B, H, W, st);
         case 7: return launch_head_t<7>(x, w, b0, b1, res4, out4, B, H, W, st);
     }
-    set_error("conv_head: k=%d unsupported", k);
-    return PIVLFN_ERR_ARG;
+    HeadPlan refused;
+    return choose_conv_head(k, B, H, W, 0, refused);      // k outside {3, 5, 7}: the shared decision's message
 }
 
 }  // namespace pivlfn

@@ -101,6 +101,7 @@ SIGNATURES = {
     "pivlfn_conv2d_nhwc_plan": (ctypes.c_int, [ctypes.c_int] * 14 + [ctypes.POINTER(ctypes.c_int)]),
     "pivlfn_conv2d_nhwc_kernel_plan": (ctypes.c_int, [ctypes.c_int] * 16 + [ctypes.POINTER(ctypes.c_int)]),
     "pivlfn_conv_head_nhwc": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
+    "pivlfn_conv_head_nhwc_plan": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)]),
     "pivlfn_upconv_nhwc": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
     "pivlfn_backwarp_nhwc": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_float, ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     "pivlfn_reg_prep": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_float] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),

@@ -50,7 +50,7 @@ def test_argument_errors_are_reported_without_a_gpu():
 
 NEW_OPS = ("pivlfn_upconv_nhwc", "pivlfn_backwarp_nhwc", "pivlfn_reg_prep", "pivlfn_reg_tail", "pivlfn_prep_pyramid",
            "pivlfn_conv1_fused_nhwc")
-PLAN_OPS = ("pivlfn_conv2d_nhwc_plan", "pivlfn_conv2d_nhwc_kernel_plan")      # host only: no handle, no stream, nothing launched
+PLAN_OPS = ("pivlfn_conv2d_nhwc_plan", "pivlfn_conv2d_nhwc_kernel_plan", "pivlfn_conv_head_nhwc_plan")      # host only: no handle, no stream, nothing launched
 
 
 def test_per_layer_entry_points_are_declared():
@@ -116,3 +116,9 @@ def test_per_layer_entry_points_reject_bad_arguments_without_a_gpu():
     refused(lib.pivlfn_conv2d_nhwc_kernel_plan(2, 64, 32, 3, 3, 1, 64, 64, 1, 1, 1, 5, 0, 32, 64, 256, plan), "conv2d_split", "terms=5")
     refused(lib.pivlfn_conv2d_nhwc_kernel_plan(0, 64, 32, 3, 3, 1, 64, 64, 1, 1, 1, 3, 0, 32, 64, 256, plan), "kernel=0")
     refused(lib.pivlfn_conv2d_nhwc_kernel_plan(2, 64, 32, 3, 3, 1, 64, 64, 1, 1, 1, 3, 0, 32, 64, 256, None), "conv2d_kernel_plan")
+    assert lib.pivlfn_conv_head_nhwc_plan(7, 2, 256, 300, plan) == 0 and tuple(plan[:4]) == (4, 8, 58, 2 * 32 * 6)
+    refused(lib.pivlfn_conv_head_nhwc_plan(4, 1, 64, 64, plan), "conv_head", "k=4")
+    refused(lib.pivlfn_conv_head_nhwc_plan(7, 1, 0, 64, plan), "conv_head", "bad arguments")
+    refused(lib.pivlfn_conv_head_nhwc_plan(7, 1, 64, 64, None), "conv_head_plan")
+    # the entry point itself: the same refusals, before anything is launched
+    refused(lib.pivlfn_conv_head_nhwc(None, P, P, P, 1, 64, 64, None), "conv_head")

@@ -65,6 +65,14 @@ CASES = [
     (49, 49, 1, 7, 1, (0, 3), 32, 40, 1),         # conv_dist_R.1
     (49, 49, 1, 7, 1, (0, 3), 256, 272, 1),       # conv_dist_R.1 at >= 256 x 256: its streaming matrix-core kernel (columns walk along x)
     (49, 49, 1, 7, 1, (0, 3), 261, 300, 2),       # ragged rows and columns, batch 2
+    # the two streaming kernels on thin images of >= 256 x 256 pixels: fewer rows (columns) than the column (row) kernel has taps, fewer
+    # than its 16-row (16-column) tile, and one row
+    (49, 32, 7, 1, 1, (3, 0), 5, 13109, 1),
+    (49, 32, 7, 1, 1, (3, 0), 13109, 5, 1),
+    (49, 32, 7, 1, 1, (3, 0), 1, 65536, 1),
+    (49, 49, 1, 7, 1, (0, 3), 5, 13109, 1),
+    (49, 49, 1, 7, 1, (0, 3), 13109, 5, 1),
+    (49, 49, 1, 7, 1, (0, 3), 1, 65536, 1),
     (25, 25, 1, 5, 1, (0, 2), 16, 32, 1),
     (9, 32, 3, 3, 1, (1, 1), 8, 8, 3),            # conv_dist_R level 5/6
     (2, 32, 7, 7, 1, (3, 3), 32, 48, 1),          # flow head on the matrix-core path
@@ -81,6 +89,12 @@ def test_conv2d_matches_torch(case, dev):
     b = torch.randn(co, generator=g) * 0.1
     x = torch.randn(B, ci, H, W, generator=g)
     conv = Conv(w, b)
+    if sorted((kh, kw)) == [1, 7] and H * W >= 256 * 256:
+        # without an activation, and with the strides run() passes, these land on the streaming kernels (pivlfn_conv2d_nhwc_plan)
+        plan = (ctypes.c_int * 5)()
+        lanes = (-(-ci // 4) * 4, -(-co // 4) * 4)
+        _lib.check(_lib.load().pivlfn_conv2d_nhwc_plan(co, ci, kh, kw, B, H, W, s, pad[0], pad[1], 0, 0, lanes[0], lanes[1], plan), "plan")
+        assert plan[0] == (6 if kh == 7 else 7), (case, tuple(plan))      # PIVLFN_CONV_PLAN_COL7 / _ROW7
     for leaky in (False, True):
         want = F.conv2d(x.double(), w.double(), b.double(), stride=s, padding=pad)
         if leaky:

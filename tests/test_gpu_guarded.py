@@ -25,6 +25,7 @@ from pivlfn.models import LiteFlowNet2
 from pivlfn.synth import MODEL_CFG
 import net_ops_reference as ref
 from guarded import KINDS, check_guards, check_lanes, guarded, poison, same_bits
+from test_conv_head_plan import plan as head_plan
 from test_gpu_conv import Conv
 from test_gpu_net_ops import OP_BAR, WARP_BAR, _nhwc, _within
 from test_gpu_wino import CAT_CASES
@@ -302,9 +303,16 @@ def test_concatenated_sources_guarded(case, dev):
         lib.pivlfn_conv_destroy(h)
 
 
-@pytest.mark.parametrize("k,B,H,W", [(3, 2, 37, 53), (5, 1, 3, 70), (7, 2, 37, 53), (7, 1, 256, 300)])
+@pytest.mark.parametrize("k,B,H,W", [(3, 2, 37, 53), (5, 1, 3, 70), (7, 2, 37, 53), (7, 1, 256, 300),
+                                     # the other kernels of the launcher (tests/test_conv_head_plan.py): one weight per lane through the
+                                     # scalar cache, four rows per lane, and the matrix-core head on images thinner than its tile and halo
+                                     (3, 1, 3, 8200), (5, 1, 17, 4107), (7, 1, 7, 8195), (3, 1, 509, 517), (5, 1, 5, 52431),
+                                     (7, 1, 1, 65536), (7, 1, 65537, 1), (7, 1, 5, 13109)])
 def test_flow_head_guarded(k, B, H, W, dev):
     """res4 lanes 2-3 are not read (pivlfn.h); out4 lanes 2-3 are written as +0.0."""
+    new = {(3, 3, 8200): 2, (5, 17, 4107): 2, (7, 7, 8195): 2, (3, 509, 517): 3, (5, 5, 52431): 3, (7, 1, 65536): 4, (7, 65537, 1): 4, (7, 5, 13109): 4}
+    if (k, H, W) in new:                            # PIVLFN_HEAD_PLAN_PIXEL, _ROWS4, _MFMA
+        assert head_plan(k, B, H, W)[0] == new[(k, H, W)]
     g = torch.Generator().manual_seed(k + H)
     w = torch.randn(2, 32, k, k, generator=g) / (32 * k * k) ** 0.5
     b = torch.randn(2, generator=g) * 0.1
@@ -332,6 +340,45 @@ def test_flow_head_guarded(k, B, H, W, dev):
     plain = call(None)
     want = F.conv2d(x.permute(0, 3, 1, 2).double(), w.double(), b.double(), padding=k // 2) + res.permute(0, 3, 1, 2).double()
     assert (plain[..., :2].permute(0, 3, 1, 2).double() - want).abs().max().item() < 2e-5 * max(1.0, want.abs().max().item())
+    for kind in KINDS:
+        assert same_bits(call(kind), plain), (k, kind)
+
+
+def test_flow_head_guarded_rows4_k7(dev):
+    """For k = 7 the four-row kernel runs only from 2^31 bytes of input (below, the matrix-core head does): the guards, lanes and bits of
+    test_flow_head_guarded on a 4096 x 4096 image that never leaves the device.  Its values against float64, on bands:
+    tests/test_gpu_conv_head.py."""
+    k, B, H, W = 7, 1, 4096, 4096
+    assert head_plan(k, B, H, W)[0] == 3            # PIVLFN_HEAD_PLAN_ROWS4
+    if torch.cuda.mem_get_info(dev)[0] < (8 << 30):
+        pytest.skip("two copies of a 2 GiB input need about 8 GiB of free device memory")
+    g = torch.Generator().manual_seed(k + H)
+    w = torch.randn(2, 32, k, k, generator=g) / (32 * k * k) ** 0.5
+    b = torch.randn(2, generator=g) * 0.1
+    conv = Conv(w, b)
+    gd = torch.Generator(device=dev).manual_seed(k + H)
+    x = torch.empty(B, H, W, 32, device=dev).normal_(generator=gd)
+    res = torch.empty(B, H, W, 2, device=dev).normal_(generator=gd)
+
+    def call(kind):
+        if kind is None:
+            xd, r4, out = x, torch.zeros(B, H, W, 4, device=dev), torch.full((B, H, W, 4), NAN, device=dev)
+        else:
+            xd = guarded((B, H, W, 32), torch.float32, dev, kind)
+            xd.copy_(x)
+            r4 = poison(guarded((B, H, W, 4), torch.float32, dev, kind), slice(2, 4), kind)
+            out = guarded((B, H, W, 4), torch.float32, dev, "sentinel")
+        r4[..., :2] = res
+        _lib.check(_lib.load().pivlfn_conv_head_nhwc(conv.h, xd.data_ptr(), r4.data_ptr(), out.data_ptr(), B, H, W, _st(dev)), "head")
+        torch.cuda.synchronize()
+        if kind is not None:
+            for t in (xd, r4, out):
+                check_guards(t, f"head k={k} {kind}")
+            check_lanes(out, slice(2, 4), "zero", f"head k={k} {kind}")
+        return out
+
+    plain = call(None)
+    assert bool(torch.isfinite(plain).all())
     for kind in KINDS:
         assert same_bits(call(kind), plain), (k, kind)
 
