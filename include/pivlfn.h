@@ -967,6 +967,57 @@ int pivlfn_conv1_fused_nhwc(const float *w1, const float *b1, const float *w_ext
 int pivlfn_profile_enable(pivlfn_net *net, int level);   /* level 1..6, 0 = off */
 int pivlfn_profile_read(pivlfn_net *net, double *ms_dispatch, double *ms_event_pair, long *launches, int reset);
 
+/* ---- uncertainty of an estimated flow from correlation statistics (Wieneke 2015, "PIV uncertainty quantification from correlation
+ * statistics"): per vector and axis, the standard uncertainty in pixels that follows from how asymmetric the correlation peak of image 1
+ * against image 2 warped back by the flow may be, given the pixel-wise scatter of the products the peak is summed from, carried
+ * through the three-point Gaussian peak fit.  Needs no truth field.  Added without an ABI bump (additive).
+ * img1, img2, flow, mask: as for pivlfn_match_quality;  unc: NCHW [B,2,H,W] fp32, planes ux, uy in pixels;  flag: [B,H,W] bytes;
+ * workspace: 8-byte aligned, at least pivlfn_flow_uncertainty_workspace_bytes(B,H,W,radius,lag) bytes (74 bytes per pixel and pair:
+ * nine fp64 planes and two bytes; 0 for arguments out of range), needs no initial contents.  Launches only on `stream`, no
+ * allocation, no host synchronisation, no floating-point atomics; no output depends on what unc, flag or the workspace held before
+ * the call; a pair gives the same bits alone, inside any batch and from run to run.
+ * Arithmetic contract, all fp64, every operation rounded on its own (no fma), divisions and square roots correctly rounded; r =
+ * radius:
+ *   a, b, m, k:  the gray value a of img1, the warped gray value b of img2, the validity m of the sample and the exclusion k, word for
+ *                word those of pivlfn_match_quality (the same kernel forms them).  Pixel q is valid, v(q) = 1, iff k(q) = 1 && m(q) = 1.
+ *   box sums:    every sum below over a (2*R+1)^2 box around a pixel is taken over the box clipped to the image, in
+ *                pivlfn_match_quality's order: per row the terms left to right from +0.0, then the row sums top to bottom from
+ *                +0.0; a term that is not defined is +0.0.  The order is fixed by this contract and not by the launch geometry.
+ *   high-pass:   n1(q), A1(q), B1(q) = the box sums of radius r of v, of a where v = 1 and of b where v = 1.  Where v(q) = 1:
+ *                a'(q) = a(q) - A1(q)/n1(q), b'(q) = b(q) - B1(q)/n1(q) (the local background would flatten the peak).
+ *   fields:      p(q) = a'(q)*b'(q) where v(q) = 1.  For the axis e in {(1,0), (0,1)} (x, then y), where q+e lies inside the image and
+ *                v(q) = v(q+e) = 1 (q is a pair of e): t1 = a'(q)*b'(q+e), t2 = a'(q+e)*b'(q), s_e(q) = t1 + t2, d_e(q) = t1 - t2
+ *                (the terms of C+ + C- and of C+ - C-);  D_e(q) = the box sum of radius `lag` of d_e;  g_e(q) = d_e(q)*D_e(q) where q
+ *                is a pair of e: its window sum is the autocovariance of the terms of C+ - C- summed over the lags |delta| <= lag,
+ *                the variance of C+ - C-.
+ *   window sums: box sums of radius r around p:  n0 of v, C0 of p, and per axis n_e of the pairs, S_e of s_e, V_e of g_e (the counts
+ *                are exact).
+ *   per axis:    sig = sqrt(V_e);  Cpm = 0.5*S_e;  Cm = Cpm - 0.5*sig;  Cp = Cpm + 0.5*sig.
+ *   flag byte:   bit 0 (1) FEW: n0 < min_count || n_x < min_count || n_y < min_count;  bit 1 (2) FLAT: FEW is clear and
+ *                C0 < floor*floor*n0;  where FEW and FLAT are clear: bit 2 (4) NO_PEAK: on either axis Cm <= 0 || C0 - Cp < 1e-6*C0
+ *                (free of logarithms, so the flags are bit-exact; a NaN compares false);  bit 3 (8) NO_VARIANCE: on either axis
+ *                V_e <= 0 or V_e is not finite;  bit 4 (16) CENTRE_OUT: v(p) = 0 (informational: the values are still formed).
+ *   outputs:     where bits 0-3 are clear, with l = ln (the device library's fp64 logarithm, the one operation here that is not
+ *                correctly rounded): u_e = | 0.5*(l(Cm) - l(Cp)) / ((l(Cm) - 2.0*l(C0)) + l(Cp)) |, rounded once to fp32; the
+ *                conditions keep the denominator at or below about -2e-6.  Elsewhere both planes are NaN.
+ * Errors (PIVLFN_ERR_ARG, before any launch): those of pivlfn_match_quality (with unc in the place of quality), and lag outside 0..4.
+ *
+ * pivlfn_uncertainty_accumulate adds the pairs of unc / flag, in batch order, to sums [3,H,W] fp64 (8-byte aligned; planes: the sum of
+ * ux^2, the sum of uy^2, the number of pairs): one thread per pixel, sum = sum + (double)u*(double)u and n = n + 1.0 for every pair
+ * whose flag has bits 0-3 clear, the others are skipped.  Only on `stream`, no atomics.  Errors: a null pointer, a non-positive size,
+ * H*W >= 2^31, misaligned sums, sums overlapping an input. */
+#define PIVLFN_UNCERTAINTY_FEW         1
+#define PIVLFN_UNCERTAINTY_FLAT        2
+#define PIVLFN_UNCERTAINTY_NO_PEAK     4
+#define PIVLFN_UNCERTAINTY_NO_VARIANCE 8
+#define PIVLFN_UNCERTAINTY_CENTRE_OUT 16
+size_t pivlfn_flow_uncertainty_workspace_bytes(int B, int H, int W, int radius, int lag);
+int pivlfn_flow_uncertainty(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask,
+                            float *unc /* [B,2,H,W]: ux, uy in px */, unsigned char *flag /* [B,H,W] */, int B, int H, int W, int radius,
+                            int lag, int min_count, double floor, void *workspace, size_t workspace_bytes, void *stream);
+int pivlfn_uncertainty_accumulate(const float *unc, const unsigned char *flag, double *sums /* [3,H,W]: sum ux^2, sum uy^2, n */, int B,
+                                  int H, int W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,24 @@ int pivlfn_match_quality(const float *img1, const float *img2, int C, const floa
                                 (hipStream_t)stream);
 }
 
+size_t pivlfn_flow_uncertainty_workspace_bytes(int B, int H, int W, int radius, int lag)
+{
+    return flow_uncertainty_workspace_bytes(B, H, W, radius, lag);
+}
+
+int pivlfn_flow_uncertainty(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask, float *unc,
+                            unsigned char *flag, int B, int H, int W, int radius, int lag, int min_count, double floor, void *workspace,
+                            size_t workspace_bytes, void *stream)
+{
+    return launch_flow_uncertainty(img1, img2, C, flow, mask, unc, flag, B, H, W, radius, lag, min_count, floor, workspace,
+                                   workspace_bytes, (hipStream_t)stream);
+}
+
+int pivlfn_uncertainty_accumulate(const float *unc, const unsigned char *flag, double *sums, int B, int H, int W, void *stream)
+{
+    return launch_uncertainty_accumulate(unc, flag, sums, B, H, W, (hipStream_t)stream);
+}
+
 size_t pivlfn_vortex_gamma_workspace_bytes(int B, int H, int W, int radius, int spacing)
 {
     return vortex_gamma_workspace_bytes(B, H, W, radius, spacing);

@@ -328,6 +328,17 @@ int launch_match_quality(const float *img1, const float *img2, int C, const floa
                          unsigned char *flag, int B, int H, int W, int radius, int min_count, double floor, void *ws, size_t ws_bytes,
                          hipStream_t st);
 
+// the warp kernel of match_quality alone: a, b [B,H,W] fp64 and the byte of m (bit 0) and k (bit 1); arguments checked by the caller
+int launch_quality_warp(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask, double *wa, double *wb,
+                        unsigned char *wf, int B, int H, int W, hipStream_t st);
+
+// ---- flow uncertainty (uncertainty.hip): per-vector uncertainty from correlation statistics, and its per-pixel sums over a sequence ----
+size_t flow_uncertainty_workspace_bytes(int B, int H, int W, int radius, int lag);
+int launch_flow_uncertainty(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask, float *unc,
+                            unsigned char *flag, int B, int H, int W, int radius, int lag, int min_count, double floor, void *ws,
+                            size_t ws_bytes, hipStream_t st);
+int launch_uncertainty_accumulate(const float *unc, const unsigned char *flag, double *sums, int B, int H, int W, hipStream_t st);
+
 // ---- vortex identification (vortex.hip): Gamma1 and Gamma2 of a flow over the (2r+1)^2 neighbours at spacing s -----------------------
 size_t vortex_gamma_workspace_bytes(int B, int H, int W, int radius, int spacing);
 int launch_vortex_gamma(const float *flow, const unsigned char *mask, float *gamma, unsigned char *flag, int B, int H, int W, int radius,

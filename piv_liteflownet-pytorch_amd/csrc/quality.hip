@@ -250,6 +250,21 @@ static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
     return b != nullptr && pa < pb + nb && pb < pa + na;
 }
 
+// The first kernel of match_quality, shared with flow_uncertainty (uncertainty.hip): a, b and the byte of m and k of every pixel.  The
+// caller has checked the arguments (C is 1 or 3, 0 < B <= 65535, H*W < 2^31).
+int launch_quality_warp(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask, double *wa, double *wb,
+                        unsigned char *wf, int B, int H, int W, hipStream_t st)
+{
+    const size_t g = ((size_t)H * W + 255) / 256, cap = 16384 / (size_t)B > 64 ? 16384 / (size_t)B : 64;
+    const dim3 wgrid((unsigned)(g > cap ? cap : g), (unsigned)B);
+    if (C == 1)
+        hipLaunchKernelGGL(quality_warp_kernel<1>, wgrid, dim3(256), 0, st, img1, img2, flow, mask, wa, wb, wf, H, W);
+    else
+        hipLaunchKernelGGL(quality_warp_kernel<3>, wgrid, dim3(256), 0, st, img1, img2, flow, mask, wa, wb, wf, H, W);
+    PIV_CHECK_HIP(hipGetLastError());
+    return PIVLFN_OK;
+}
+
 int launch_match_quality(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask, float *quality,
                          unsigned char *flag, int B, int H, int W, int radius, int min_count, double floor, void *ws, size_t ws_bytes,
                          hipStream_t st)
@@ -280,13 +295,7 @@ int launch_match_quality(const float *img1, const float *img2, int C, const floa
 
     double *wa = (double *)ws, *wb = wa + px;
     unsigned char *wf = (unsigned char *)(wb + px);
-    const size_t g = ((size_t)H * W + 255) / 256, cap = 16384 / (size_t)B > 64 ? 16384 / (size_t)B : 64;
-    const dim3 wgrid((unsigned)(g > cap ? cap : g), (unsigned)B);
-    if (C == 1)
-        hipLaunchKernelGGL(quality_warp_kernel<1>, wgrid, dim3(256), 0, st, img1, img2, flow, mask, wa, wb, wf, H, W);
-    else
-        hipLaunchKernelGGL(quality_warp_kernel<3>, wgrid, dim3(256), 0, st, img1, img2, flow, mask, wa, wb, wf, H, W);
-    PIV_CHECK_HIP(hipGetLastError());
+    if (int rc = launch_quality_warp(img1, img2, C, flow, mask, wa, wb, wf, B, H, W, st)) return rc;
 
     // 16-row tiles keep two workgroups on a CU up to r = 8; above, 32 rows halve the share of halo rows in the horizontal pass
     const int TY = radius <= 8 ? 16 : 32;

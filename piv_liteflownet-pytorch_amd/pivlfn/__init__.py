@@ -13,6 +13,7 @@ from .validate import MaskedFlowStats, validate_flow                     # noqa:
 from .preproc import FrameBackground, preprocess_frames                  # noqa: F401
 from .evaluate import ErrorStats, FlowErrors, flow_errors, level_errors  # noqa: F401
 from .quality import CENTRE_OUT, FEW, FLAT, NO_PEAK, MatchQuality, match_quality  # noqa: F401
+from .uncertainty import FlowUncertainty, UncertaintyStats, flow_uncertainty, uncertainty_coverage  # noqa: F401
 from .vortex import VortexField, vortex_gamma                           # noqa: F401
 from .flowmap import LOST, OUT, UNDEFINED, FlowMap, FTLEField           # noqa: F401
 from .pod import FlowPOD, PODResult                                     # noqa: F401
@@ -30,6 +31,7 @@ __all__ = ["FunctionCorrelation", "ModuleCorrelation", "LiteFlowNet", "LiteFlowN
            "preprocess_frames", "FrameBackground", "flow_errors", "level_errors", "FlowErrors", "ErrorStats", "flow_to_color", "motion_to_color",
            "flow_maxrad", "scalar_to_color", "field_absmax", "vorticity_image", "decimate_flow", "quiver_plot", "color_wheel_image",
            "write_png", "PngWriter", "write_png_gray", "GrayPngWriter", "match_quality", "MatchQuality", "FEW", "FLAT", "NO_PEAK", "CENTRE_OUT",
+           "flow_uncertainty", "FlowUncertainty", "UncertaintyStats", "uncertainty_coverage",
            "vortex_gamma", "VortexField", "FlowMap", "FTLEField", "OUT", "LOST", "UNDEFINED", "FlowPOD", "PODResult", "TwoPointStats", "TwoPointResult",
            "TemporalSpectrum", "TemporalSpectrumResult", "PressureField", "PressureResult",
            "gen_template", "template_match", "target_points", "find_markers", "index_lattice", "fit_mapping", "dewarp_frames", "calibrate_camera",

@@ -58,6 +58,10 @@ SIGNATURES = {
     "pivlfn_match_quality_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "pivlfn_match_quality": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5
                              + [ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "pivlfn_flow_uncertainty_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "pivlfn_flow_uncertainty": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6
+                                + [ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "pivlfn_uncertainty_accumulate": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
     "pivlfn_vortex_gamma_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "pivlfn_vortex_gamma": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "pivlfn_flowmap_advect": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3

@@ -5,7 +5,8 @@
                 [--weights FILE] [--batch B] [--stats] [--validate flag|mask|replace]
                 [--background min|FILE] [--minmax K] [--minmax-floor N] [--truth DIR [--truth-levels]]
                 [--color [--color-max X] [--color-wheel interp|original]] [--vort-image [--vort-max X]] [--quiver [CELL]]
-                [--quality [R] [--quality-image]] [--vortex [R] [--vortex-spacing S] [--vortex-image]] [--pod K [--pod-cell C]]
+                [--quality [R] [--quality-image]] [--uncertainty [R] [--uncertainty-lag L] [--uncertainty-image [--uncertainty-max X]]]
+                [--vortex [R] [--vortex-spacing S] [--vortex-image]] [--pod K [--pod-cell C]]
                 [--ftle [SPACING] [--ftle-steps T] [--ftle-image [--ftle-max X]]]
                 [--twopoint [R] [--twopoint-step S] [--twopoint-mean FILE]]
                 [--spectrum [L] [--spectrum-overlap O] [--spectrum-cell C] [--spectrum-fps F] [--spectrum-image]]
@@ -43,6 +44,14 @@ Differences, all deliberate:
     flow inside (2R+1)^2 windows, and the sub-pixel residual of its peak): <name>_qual.flo with the three bands c, dx, dy, the
     summaries in <save>/quality.json, and with `--quality-image` <name>_corr.png (c on 0..1 in gray, undefined pixels red); with
     --validate flag|mask the rejected vectors are left out of the windows;
+  * `--uncertainty [R]` writes the standard uncertainty of every vector in pixels beside every .flo, computed on the device from the two
+    frames the network was given and the flow that is written (pivlfn.uncertainty.flow_uncertainty: the correlation statistics of
+    (2R+1)^2 windows, the covariance of the contributions summed over `--uncertainty-lag L` pixels, default 2): <name>_unc.flo with the
+    bands ux, uy (1e10 where a vector has none), the parameters and summaries in <save>/uncertainty.json -- with `--truth` also the
+    coverage, the share of vectors whose error is within their uncertainty (0.68 for a calibrated estimate), and RMS error / RMS u --
+    with `--stats` <save>/uncertainty_stats.npz (the noise share of the normal stresses and the uncertainty of the mean, per pixel), and
+    with `--uncertainty-image` <name>_unc.png (|u| in gray on 0..X of `--uncertainty-max`, default 0.5 px; vectors without a value red);
+    with --validate flag|mask the rejected vectors are left out of the windows;
   * `--vortex [R]` writes the vortex identification functions of the flow that is written beside every .flo, computed on the device
     (pivlfn.vortex.vortex_gamma: Gamma1 and Gamma2 over the (2R+1)^2 vectors at `--vortex-spacing S` pixels around each one):
     <name>_gamma.flo with the two bands, the vortex centres and core areas of every pair and the summary of the run in
@@ -106,7 +115,7 @@ HERE = os.path.dirname(os.path.realpath(__file__))
 sys.path.insert(0, HERE)
 
 from pivlfn import Network                               # noqa: E402
-from pivlfn import flowmap, quality, synth, viz, vortex  # noqa: E402
+from pivlfn import flowmap, quality, synth, uncertainty, viz, vortex  # noqa: E402
 from pivlfn.datasets import Run, image_files_from_folder, pair_files     # noqa: E402
 from pivlfn.dist import shard_bounds                     # noqa: E402
 from pivlfn.evaluate import ErrorStats, flow_errors, level_errors        # noqa: E402
@@ -206,6 +215,20 @@ parser.add_argument("--quality", type=int, nargs="?", const=8, default=None, met
                          "of the windows, with --validate replace the replaced flow is rated")
 parser.add_argument("--quality-image", action="store_true",
                     help="with --quality: also <name>_corr.png, c on 0..1 in gray, pixels without a value in red")
+parser.add_argument("--uncertainty", type=int, nargs="?", const=8, default=None, metavar="R",
+                    help="also write <name>_unc.flo beside every .flo: the standard uncertainty of the written flow in pixels, bands ux "
+                         "and uy, from the correlation statistics of (2R+1) x (2R+1) windows (pivlfn.uncertainty.flow_uncertainty; R = "
+                         "1..15, default 8; not a reference flag; not with -b/-c); 1e10 where a vector has none; the summaries go to "
+                         "<save>/uncertainty.json, with --truth also the coverage, with --stats the per-pixel sums to "
+                         "<save>/uncertainty_stats.npz.  With --validate flag|mask the rejected vectors are left out of the windows, "
+                         "with --validate replace the replaced flow is rated")
+parser.add_argument("--uncertainty-lag", type=int, default=None, metavar="L",
+                    help="with --uncertainty: the covariance of the pixel-wise contributions is summed over (2L+1) x (2L+1) offsets, "
+                         "L = 0..4 (default 2)")
+parser.add_argument("--uncertainty-image", action="store_true",
+                    help="with --uncertainty: also <name>_unc.png, |u| in gray on 0..X, vectors without a value in red")
+parser.add_argument("--uncertainty-max", type=float, default=None, metavar="X",
+                    help="with --uncertainty-image: the |u| in pixels that is drawn white (default 0.5)")
 parser.add_argument("--vortex", type=int, nargs="?", const=4, default=None, metavar="R",
                     help="also write <name>_gamma.flo beside every .flo: the vortex identification functions Gamma1 and Gamma2 of the "
                          "written flow (pivlfn.vortex.vortex_gamma; not a reference flag; not with -b/-c) over the (2R+1) x (2R+1) "
@@ -279,10 +302,11 @@ TWOPOINT_FLAGS = ("twopoint", "twopoint_step", "twopoint_mean")
 POD_FLAGS = ("pod", "pod_cell")
 QUALITY_FLAGS = ("quality", "quality_image")
 QUALITY_BAD_RGB = (255, 0, 0)
+UNCERTAINTY_FLAGS = ("uncertainty", "uncertainty_lag", "uncertainty_image", "uncertainty_max")
 VORTEX_FLAGS = ("vortex", "vortex_spacing", "vortex_image")
 PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
 FTLE_FLAGS = ("ftle", "ftle_steps", "ftle_image", "ftle_max")
-VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + SPECTRUM_FLAGS + PRESSURE_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + UNCERTAINTY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + SPECTRUM_FLAGS + PRESSURE_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -393,6 +417,7 @@ class Batch:
     flag: Optional[torch.Tensor] = None     # the validator's flags
     mode: Optional[str] = None              # the validation mode
     levels: Optional[list] = None           # the per-level flows of the same forward, if a stage asked for them
+    truth: Optional[torch.Tensor] = None    # the known flows [n,2,H,W], once the Truth stage has run
     extras: dict = field(default_factory=dict)      # name -> tensor [n, ...] that returns to the host with the flows
 
     def masked(self):
@@ -744,7 +769,7 @@ class Truth(Stage):
         main = torch.cuda.current_stream(batch.raw.device)
         main.wait_stream(self.copy)
         self.raw.record_stream(main)
-        truth = self.raw.permute(0, 3, 1, 2).contiguous()
+        truth = batch.truth = self.raw.permute(0, 3, 1, 2).contiguous()
         scored, mask = batch.masked()
         self.mode = batch.mode
         if mask is not None:
@@ -868,6 +893,68 @@ class Quality(Stage):
             total = [a + b for a, b in zip(total, row)]
         doc = {"radius": self.radius, "floor": self.floor, "min_count": self.min_count, "mask": self.mask,
                "pairs": {name: quality.summarize(row) for name, row in zip(names, rows)}, "total": quality.summarize(total)}
+        write_json(self.file, json_strict(doc), allow_nan=False)
+
+
+class Uncertainty(Stage):
+    """Puts an uncertainty on every batch of flows on the device, right after them and on the same stream: flow_uncertainty of the
+    frames the network was given and the flow that is written, with the flags of "flag" or "mask" as the mask.  The two bands -- and
+    the picture of |u|, with `image` -- go back to the host with the flows; the per-pair sums (pivlfn.uncertainty.SUMS and, after a
+    Truth stage, COVERAGE_SUMS) stay on the device until finish() copies them once.  `stats`: the file of the per-pixel sums, or
+    None."""
+    extras = True
+
+    def __init__(self, radius, lag, image, vmax, file, stats, mask=None):
+        self.radius, self.lag, self.image, self.vmax, self.file, self.mask = radius, lag, image, vmax, file, mask
+        self.floor = 1.0 / 255.0
+        self.min_count = uncertainty.check_params(radius, lag, self.floor, None)
+        self.stats_file, self.stats = stats, None
+        self._sums, self._coverage = [], []
+
+    def __call__(self, batch):
+        mask = batch.masked()[1]
+        unc = uncertainty.flow_uncertainty(batch.img1, batch.img2, batch.flow, self.radius, self.lag, mask, self.floor, self.min_count)
+        self._sums.append(unc.sums())
+        if batch.truth is not None:
+            self._coverage.append(uncertainty.coverage_sums(batch.flow, batch.truth, unc, mask))
+        if self.stats_file is not None:
+            if self.stats is None:
+                self.stats = uncertainty.UncertaintyStats(unc.u.size(2), unc.u.size(3), device=unc.u.device)
+            self.stats.update(unc)
+        none = (unc.flag & uncertainty.UNUSABLE).ne(0).unsqueeze(1)
+        batch.extras["unc"] = torch.where(none, torch.full_like(unc.u, 1e10), unc.u).permute(0, 2, 3, 1)      # the .flo layout
+        if self.image:
+            batch.extras["unc_image"] = viz.scalar_to_color(unc.magnitude(), 0.0, self.vmax, cmap="gray", bad=QUALITY_BAD_RGB)
+
+    def finish(self, names, ctx):
+        """<save>/uncertainty.json: the parameters, per pair name the summary of FlowUncertainty.summary() -- after a Truth stage with
+        the coverage and RMS error / RMS u of uncertainty_coverage() -- and the same over the run, formed from the per-pair sums in pair
+        order.  Sharded runs: the records of all ranks are gathered (gather_rows) and rank 0 writes.  A value that is not finite is
+        written as null.  With `stats` <save>/uncertainty_stats.npz (a single process)."""
+        rows = _cat(self._sums).tolist() if self._sums else []
+        cover = _cat(self._coverage).tolist() if self._coverage else None
+        assert len(rows) == len(names) and (cover is None or len(cover) == len(names))
+        if self.stats is not None:
+            self.stats.save(self.stats_file, radius=self.radius, lag=self.lag)
+        names, parts = gather_rows(names, (rows, cover), ctx.world)
+        if ctx.rank != 0:
+            return
+        rows = [row for part in parts for row in part[0]]
+        cover = [row for part in parts for row in part[1] or []]
+
+        def record(row, cov):
+            return {**uncertainty.summarize(row), **(uncertainty.summarize_coverage(cov) if cov is not None else {})}
+
+        def total(table, width):
+            tot = [0.0] * width
+            for row in table:
+                tot = [a + b for a, b in zip(tot, row)]
+            return tot
+        scored = len(cover) == len(rows) and len(rows) > 0
+        doc = {"radius": self.radius, "lag": self.lag, "floor": self.floor, "min_count": self.min_count, "mask": self.mask,
+               "pairs": {name: record(row, cover[i] if scored else None) for i, (name, row) in enumerate(zip(names, rows))},
+               "total": record(total(rows, len(uncertainty.SUMS)),
+                               total(cover, len(uncertainty.COVERAGE_SUMS)) if scored else None)}
         write_json(self.file, json_strict(doc), allow_nan=False)
 
 
@@ -1049,6 +1136,11 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
     if args.quality is not None:
         stages.append(Quality(args.quality, args.quality_image, layout.sibling("quality.json"),
                               args.validate if args.validate in ("flag", "mask") else None))
+    if args.uncertainty is not None:
+        stages.append(Uncertainty(args.uncertainty, 2 if args.uncertainty_lag is None else args.uncertainty_lag, args.uncertainty_image,
+                                  0.5 if args.uncertainty_max is None else args.uncertainty_max, layout.sibling("uncertainty.json"),
+                                  layout.sibling("uncertainty_stats.npz") if args.stats else None,
+                                  args.validate if args.validate in ("flag", "mask") else None))
     if args.vortex is not None:
         stages.append(Vortex(args.vortex, args.vortex_spacing or 1, args.vortex_image, layout.sibling("vortices.json"),
                              args.validate if args.validate in ("flag", "mask") else None))
@@ -1144,10 +1236,13 @@ def main_dl(net, inputdir, layout, is_pair, start_id, num_images, device, batch,
             writer.submit(flow, flowname_modifier(name, savedir, pair=False))
             if extras and "qual" in extras:
                 writer.submit(extras["qual"], flowname_modifier(name, savedir, ext="_qual.flo", pair=False))
+            if extras and "unc" in extras:
+                writer.submit(extras["unc"], flowname_modifier(name, savedir, ext="_unc.flo", pair=False))
             if extras and "gamma" in extras:
                 writer.submit(extras["gamma"], flowname_modifier(name, savedir, ext="_gamma.flo", pair=False))
                 vortices.pair(extras["gamma"])
-            for key, ext in (("color", "_out.png"), ("vort", "_vort.png"), ("corr", "_corr.png"), ("gamma2", "_gamma2.png")):
+            for key, ext in (("color", "_out.png"), ("vort", "_vort.png"), ("corr", "_corr.png"), ("unc_image", "_unc.png"),
+                             ("gamma2", "_gamma2.png")):
                 if extras and key in extras:
                     pictures.submit(extras[key], flowname_modifier(name, savedir, ext=ext, pair=False))
             if extras and "quiver_mean" in extras:          # pyplot is not thread-safe: the arrows are drawn here
@@ -1199,6 +1294,7 @@ def args_lines(args) -> List[str]:
             if not ((args.validate is None and k.startswith("validate")) or (not prep and k in PREP_FLAGS) or
                     (args.truth is None and k in TRUTH_FLAGS) or (not pictures and k in PICTURE_FLAGS) or
                     (args.quality is None and k in QUALITY_FLAGS) or (args.vortex is None and k in VORTEX_FLAGS) or
+                    (args.uncertainty is None and k in UNCERTAINTY_FLAGS) or
                     (args.pod is None and k in POD_FLAGS) or (args.ftle is None and k in FTLE_FLAGS) or
                     (args.twopoint is None and k in TWOPOINT_FLAGS) or (args.spectrum is None and k in SPECTRUM_FLAGS) or
                     (args.pressure is None and k in PRESSURE_FLAGS))]
@@ -1312,6 +1408,16 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.quality is not None:
         refuse_mods(args, "--quality is")
         checked("--quality: ", quality.check_params, args.quality, 1.0 / 255.0, None)
+    if _used(args, UNCERTAINTY_FLAGS[1:]) and args.uncertainty is None:
+        raise SystemExit("run.py: --uncertainty-lag, --uncertainty-image and --uncertainty-max need --uncertainty")
+    if args.uncertainty is not None:
+        refuse_mods(args, "--uncertainty is")
+        checked("--uncertainty: ", uncertainty.check_params, args.uncertainty, 2 if args.uncertainty_lag is None else args.uncertainty_lag,
+                1.0 / 255.0, None)
+        if args.uncertainty_max is not None and not args.uncertainty_image:
+            raise SystemExit("run.py: --uncertainty-max needs --uncertainty-image")
+        if args.uncertainty_max is not None and not (math.isfinite(args.uncertainty_max) and args.uncertainty_max > 0):
+            raise SystemExit(f"run.py: --uncertainty-max {args.uncertainty_max} must be a finite positive number")
     if (args.vortex_image or args.vortex_spacing is not None) and args.vortex is None:
         raise SystemExit("run.py: --vortex-spacing and --vortex-image need --vortex")
     if args.vortex is not None:
@@ -1337,7 +1443,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())   # ranks may share a card
     torch.cuda.set_device(device)
-    if (args.truth is not None or args.quality is not None or args.vortex is not None) and world > 1:        # the ranks' records and maps meet on rank 0: a small host-side exchange
+    if (args.truth is not None or args.quality is not None or args.vortex is not None or args.uncertainty is not None) and world > 1:        # the ranks' records and maps meet on rank 0: a small host-side exchange
         import torch.distributed as dist
         if not dist.is_initialized():
             dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -1363,7 +1469,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                              make_stages(args, lay, imdir, net, device, rank, world, truth_paths.get(imdir)), prep)
         else:
             total += main_mod(net, imdir, lay.flow, args.start, args.num_images, device, mods, args.batch, rank, world)
-    if (args.truth is not None or args.quality is not None or args.vortex is not None) and world > 1:
+    if (args.truth is not None or args.quality is not None or args.vortex is not None or args.uncertainty is not None) and world > 1:
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
