@@ -8,7 +8,7 @@
 // contract's order), scores every (level, stage) job on the pooled values, and leaves one 7-tuple per job; eval_finish_kernel
 // continues the same tree over the tile grid, 16 x 16 nodes (four steps) per pass.
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -302,16 +302,11 @@ static int eval_check(const char *what, const void *truth, const void *sums, con
                       double div_flow)
 {
     PIV_REQUIRE(truth && sums && ws, "%s: null pointer (flows, truth, sums and the workspace are required)", what);
-    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d (all must be positive)", what, B, H, W);
-    PIV_REQUIRE((size_t)H * W < ((size_t)1 << 31), "%s: H*W=%zu pixels, must stay below 2^31 (32-bit pixel index)", what, (size_t)H * W);
-    PIV_REQUIRE(B <= 65535, "%s: B=%d pairs, at most 65535 per call (grid y dimension)", what, B);
+    if (int rc = check_shape(what, B, H, W, "pairs")) return rc;
     PIV_REQUIRE((size_t)B * EV_MAX_JOBS * eval_tiles(H, W) < ((size_t)1 << 31), "%s: B=%d pairs of %d x %d are too many tiles for one call",
                 what, B, H, W);
     PIV_REQUIRE(std::isfinite(div_flow), "%s: div_flow=%g must be finite", what, div_flow);
-    PIV_REQUIRE(((size_t)ws & 7) == 0, "%s: the workspace must be 8-byte aligned", what);
-    PIV_REQUIRE(ws_bytes >= flow_errors_workspace_bytes(B, H, W), "%s: workspace of %zu bytes is too small, %zu needed for B=%d H=%d W=%d",
-                what, ws_bytes, flow_errors_workspace_bytes(B, H, W), B, H, W);
-    return PIVLFN_OK;
+    return check_workspace(what, ws, ws_bytes, flow_errors_workspace_bytes(B, H, W), "B=%d H=%d W=%d", B, H, W);
 }
 
 static bool aligned16(const void *p, int w) { return ((size_t)p & 15) == 0 && (w & 3) == 0; }
@@ -392,11 +387,8 @@ int launch_level_errors(const float *levels, int lowest_level, const float *trut
 int launch_error_stats(const float *flow, const float *truth, const unsigned char *mask, double *acc, int B, int H, int W, hipStream_t st)
 {
     PIV_REQUIRE(flow && truth && acc, "error_stats_accumulate: null pointer (flow, truth and acc are required)");
-    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "error_stats_accumulate: bad shape B=%d H=%d W=%d (all must be positive)", B, H, W);
-    PIV_REQUIRE((size_t)H * W < ((size_t)1 << 31), "error_stats_accumulate: H*W=%zu pixels, must stay below 2^31 (32-bit pixel index)",
-                (size_t)H * W);
-    const size_t g = ((size_t)H * W + 255) / 256;
-    hipLaunchKernelGGL(error_stats_kernel, dim3((unsigned)(g > 16384 ? 16384 : g)), dim3(256), 0, st, flow, truth, mask, acc, B,
+    if (int rc = check_shape("error_stats_accumulate", B, H, W, "frames", false)) return rc;
+    hipLaunchKernelGGL(error_stats_kernel, dim3(frame_grid((size_t)H * W, 1)), dim3(256), 0, st, flow, truth, mask, acc, B,
                        (unsigned)H * (unsigned)W);
     PIV_CHECK_HIP(hipGetLastError());
     return PIVLFN_OK;

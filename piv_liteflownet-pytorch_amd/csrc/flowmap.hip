@@ -15,7 +15,7 @@
 // Cauchy-Green tensor in closed form and two square roots.  The logarithm is left to the caller (the device's log is not correctly
 // rounded; a contract of bits cannot hold it).
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -124,12 +124,6 @@ __global__ __launch_bounds__(256) void flowmap_ftle_kernel(const double *__restr
     oflag[n] = (unsigned char)(own | (undefined ? FM_UNDEFINED : 0u));
 }
 
-static bool fm_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
-    return a != nullptr && b != nullptr && na > 0 && nb > 0 && pa < pb + nb && pb < pa + na;
-}
-
 int launch_flowmap_advect(const float *flows, const unsigned char *mask, int B, int H, int W, double *pos, unsigned char *flag, int N,
                           int backward, int iters, double *trace, hipStream_t st)
 {
@@ -142,15 +136,13 @@ int launch_flowmap_advect(const float *flows, const unsigned char *mask, int B, 
     if (N == 0 || B == 0) return PIVLFN_OK;                         // nothing to move, nothing to move through: no pointer is read
     PIV_REQUIRE(flows && pos && flag, "flowmap_advect: null pointer (flows, pos and flag are required)");
     const size_t px = (size_t)B * H * W;
-    const struct { const void *ptr; size_t bytes; const char *name; } ins[] = {{flows, px * 8, "flows"}, {mask, px, "mask"}};
-    const struct { const void *ptr; size_t bytes; const char *name; } outs[] = {{pos, (size_t)N * 16, "pos"}, {flag, (size_t)N, "flag"},
-                                                                               {trace, (size_t)B * N * 16, "trace"}};
-    for (const auto &o : outs)
-        for (const auto &in : ins)
-            PIV_REQUIRE(!fm_overlap(o.ptr, o.bytes, in.ptr, in.bytes), "flowmap_advect: %s overlaps %s (the state and the trace must not alias an input)", o.name, in.name);
-    PIV_REQUIRE(!fm_overlap(pos, (size_t)N * 16, flag, N), "flowmap_advect: pos overlaps flag");
-    PIV_REQUIRE(!fm_overlap(trace, (size_t)B * N * 16, pos, (size_t)N * 16), "flowmap_advect: trace overlaps pos");
-    PIV_REQUIRE(!fm_overlap(trace, (size_t)B * N * 16, flag, N), "flowmap_advect: trace overlaps flag");
+    const Span ps = {pos, (size_t)N * 16, "pos"}, flg = {flag, (size_t)N, "flag"}, trc = {trace, (size_t)B * N * 16, "trace"};
+    if (int rc = check_alias_by_output("flowmap_advect", {ps, flg, trc}, {{flows, px * 8, "flows"}, {mask, px, "mask"}},
+                                       " (the state and the trace must not alias an input)"))
+        return rc;
+    if (int rc = check_apart("flowmap_advect", ps, flg)) return rc;
+    if (int rc = check_apart("flowmap_advect", trc, ps)) return rc;
+    if (int rc = check_apart("flowmap_advect", trc, flg)) return rc;
     hipLaunchKernelGGL(flowmap_advect_kernel, dim3((unsigned)(((size_t)N + 255) / 256)), dim3(256), 0, st, flows, mask, B, H, W, pos, flag, N,
                        backward, iters, trace);
     PIV_CHECK_HIP(hipGetLastError());
@@ -172,7 +164,7 @@ int launch_flowmap_seed(double *pos, unsigned char *flag, int h, int w, int spac
     if (int rc = flowmap_lattice_ok("flowmap_seed", h, w, spacing)) return rc;
     PIV_REQUIRE(pos && flag, "flowmap_seed: null pointer (pos and flag are required)");
     const size_t N = (size_t)h * w;
-    PIV_REQUIRE(!fm_overlap(pos, N * 16, flag, N), "flowmap_seed: pos overlaps flag");
+    if (int rc = check_apart("flowmap_seed", {pos, N * 16, "pos"}, {flag, N, "flag"})) return rc;
     hipLaunchKernelGGL(flowmap_seed_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, pos, flag, h, w, spacing);
     PIV_CHECK_HIP(hipGetLastError());
     return PIVLFN_OK;
@@ -184,12 +176,10 @@ int launch_flowmap_ftle(const double *pos, const unsigned char *flag, int h, int
     if (int rc = flowmap_lattice_ok("flowmap_ftle", h, w, spacing)) return rc;
     PIV_REQUIRE(pos && flag && stretch && oflag, "flowmap_ftle: null pointer (pos, flag, stretch and oflag are required)");
     const size_t N = (size_t)h * w;
-    const struct { const void *ptr; size_t bytes; const char *name; } ins[] = {{pos, N * 16, "pos"}, {flag, N, "flag"}};
-    for (const auto &in : ins) {
-        PIV_REQUIRE(!fm_overlap(stretch, N * 8, in.ptr, in.bytes), "flowmap_ftle: stretch overlaps %s (outputs must not alias an input)", in.name);
-        PIV_REQUIRE(!fm_overlap(oflag, N, in.ptr, in.bytes), "flowmap_ftle: oflag overlaps %s (outputs must not alias an input)", in.name);
-    }
-    PIV_REQUIRE(!fm_overlap(stretch, N * 8, oflag, N), "flowmap_ftle: stretch overlaps oflag");
+    const Span str = {stretch, N * 8, "stretch"}, ofl = {oflag, N, "oflag"};
+    if (int rc = check_alias_by_input("flowmap_ftle", {str, ofl}, {{pos, N * 16, "pos"}, {flag, N, "flag"}}, " (outputs must not alias an input)"))
+        return rc;
+    if (int rc = check_apart("flowmap_ftle", str, ofl)) return rc;
     hipLaunchKernelGGL(flowmap_ftle_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, pos, flag, h, w, spacing, stretch, oflag);
     PIV_CHECK_HIP(hipGetLastError());
     return PIVLFN_OK;

@@ -22,7 +22,7 @@
 //                            0.05 particles per pixel are 1.5 % of the HBM bound (DESIGN 4.15 has the measurement and where the
 //                            time goes).
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -327,14 +327,6 @@ __global__ __launch_bounds__(256) void particles_render_kernel(const double *__r
     }
 }
 
-static bool pt_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
-    return a != nullptr && b != nullptr && na > 0 && nb > 0 && pa < pb + nb && pb < pa + na;
-}
-
-struct PtBuf { const void *ptr; size_t bytes; const char *name; };
-
 int launch_particles_displace(const double *pos, const float *flow, const unsigned char *mask, int H, int W, int N, int method,
                               unsigned char *flag, double *out, hipStream_t st)
 {
@@ -345,12 +337,11 @@ int launch_particles_displace(const double *pos, const float *flow, const unsign
     if (N == 0) return PIVLFN_OK;                                   // nothing to move: no pointer is read
     PIV_REQUIRE(pos && flow && flag && out, "particles_displace: null pointer (pos, flow, flag and out are required)");
     const size_t px = (size_t)H * W;
-    const PtBuf ins[] = {{pos, (size_t)N * 16, "pos"}, {flow, px * 8, "flow"}, {mask, px, "mask"}};
-    for (const auto &in : ins) {
-        PIV_REQUIRE(!pt_overlap(out, (size_t)N * 16, in.ptr, in.bytes), "particles_displace: out overlaps %s (the outputs must not alias an input)", in.name);
-        PIV_REQUIRE(!pt_overlap(flag, N, in.ptr, in.bytes), "particles_displace: flag overlaps %s (the outputs must not alias an input)", in.name);
-    }
-    PIV_REQUIRE(!pt_overlap(out, (size_t)N * 16, flag, N), "particles_displace: out overlaps flag");
+    const Span moved = {out, (size_t)N * 16, "out"}, flg = {flag, (size_t)N, "flag"};
+    if (int rc = check_alias_by_input("particles_displace", {moved, flg}, {{pos, (size_t)N * 16, "pos"}, {flow, px * 8, "flow"}, {mask, px, "mask"}},
+                                      " (the outputs must not alias an input)"))
+        return rc;
+    if (int rc = check_apart("particles_displace", moved, flg)) return rc;
     hipLaunchKernelGGL(particles_displace_kernel, dim3((unsigned)(((size_t)N + 255) / 256)), dim3(256), 0, st, pos, flow, mask, H, W, N, method,
                        flag, out);
     PIV_CHECK_HIP(hipGetLastError());
@@ -378,14 +369,11 @@ int launch_particles_render(const double *pos, const float *diam, const float *a
     PIV_REQUIRE(workspace_bytes >= need, "particles_render: workspace of %zu bytes, needs %zu (pivlfn_particles_render_workspace_bytes)",
                 workspace_bytes, need);
     const size_t px = (size_t)B * H * W;
-    const PtBuf ins[] = {{pos, bn * 16, "pos"}, {diam, bn * 4, "diam"}, {amp, bn * 4, "amp"}, {flag, bn, "flag"}};
-    const PtBuf outs[] = {{intensity, px * 4, "intensity"}, {image, px, "image"}, {workspace, need, "workspace"}};
-    for (const auto &o : outs)
-        for (const auto &in : ins)
-            PIV_REQUIRE(!pt_overlap(o.ptr, o.bytes, in.ptr, in.bytes), "particles_render: %s overlaps %s (what is written must not alias an input)", o.name, in.name);
-    for (int a = 0; a < 3; ++a)
-        for (int c = a + 1; c < 3; ++c)
-            PIV_REQUIRE(!pt_overlap(outs[a].ptr, outs[a].bytes, outs[c].ptr, outs[c].bytes), "particles_render: %s overlaps %s", outs[a].name, outs[c].name);
+    const std::initializer_list<Span> outs = {{intensity, px * 4, "intensity"}, {image, px, "image"}, {workspace, need, "workspace"}};
+    if (int rc = check_alias_by_output("particles_render", outs, {{pos, bn * 16, "pos"}, {diam, bn * 4, "diam"}, {amp, bn * 4, "amp"}, {flag, bn, "flag"}},
+                                       " (what is written must not alias an input)"))
+        return rc;
+    if (int rc = check_outputs_apart("particles_render", outs)) return rc;
     const unsigned tb = (unsigned)((tiles + 255) / 256), pb = (unsigned)((bn + 255) / 256);
     hipLaunchKernelGGL(particles_zero_kernel, dim3(tb), dim3(256), 0, st, ws, (unsigned)tiles);
     if (pb) hipLaunchKernelGGL(particles_bin_kernel<false>, dim3(pb), dim3(256), 0, st, pos, diam, amp, flag, B, N, H, W, radius, ws);

@@ -9,7 +9,7 @@
 // PIVLFN_GRAM_SLAB / GR_KC chunks chained into accumulators that start at +0.0; the slab sums are then added in slab order, by the
 // workgroup itself (direct) or, where G has too few blocks to fill the device and the workspace may hold every slab sum, by
 // gram_fold_kernel.  Either way G[i][j] = (((+0.0 + S_0) + S_1) + ...) with S_s the MFMA chain of slab s: the bits depend on P alone.
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -191,9 +191,7 @@ int launch_snapshot_gram(const float *X, int n, long P, long ldx, double *G, voi
     PIV_REQUIRE(ldx >= P, "snapshot_gram: row stride ldx=%ld is smaller than P=%ld", ldx, P);
     GramPlan g;
     gram_plan(n, P, g);
-    PIV_REQUIRE(((size_t)ws & 7) == 0, "snapshot_gram: the workspace must be 8-byte aligned");
-    PIV_REQUIRE(ws_bytes >= g.ws_bytes, "snapshot_gram: workspace of %zu bytes is too small, %zu needed for n=%d P=%ld", ws_bytes,
-                g.ws_bytes, n, P);
+    if (int rc = check_workspace("snapshot_gram", ws, ws_bytes, g.ws_bytes, "n=%d P=%ld", n, P)) return rc;
     GramParams p;
     p.X = X; p.G = G; p.ws = (double *)ws; p.P = P; p.ldx = ldx; p.n = n;
     p.nb = g.nb; p.ntri = g.ntri; p.nslab = g.nslab;

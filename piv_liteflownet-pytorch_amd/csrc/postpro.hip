@@ -3,7 +3,7 @@
 // Both kernels read a [B,2,H,W] NCHW flow -- what estimate(..., tensor=True) returns -- and work on the 3 x 3 neighbourhood
 // of each pixel, the image edge repeated.  One thread per pixel.  Arithmetic contract: include/pivlfn.h.
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -169,9 +169,7 @@ __global__ __launch_bounds__(256) void flow_stats_masked_kernel(const float *__r
 // Host-side checks shared by both entry points; fills the taps.
 static int postpro_params(const char *what, int B, int H, int W, double calib, PostproParams &p)
 {
-    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d (all must be positive)", what, B, H, W);
-    PIV_REQUIRE((size_t)H * W < ((size_t)1 << 31), "%s: H*W=%zu pixels, must stay below 2^31 (32-bit pixel index)", what,
-                (size_t)H * W);
+    if (int rc = check_shape(what, B, H, W, "frames", false)) return rc;      // flow_fields bounds B itself, after calib
     PIV_REQUIRE(std::isfinite(calib) && calib != 0.0, "%s: calib=%g must be finite and non-zero", what, calib);
     const double d = 8.0 * calib;
     PIV_REQUIRE(std::isfinite(d), "%s: calib=%g must be finite and non-zero, and 8*calib finite", what, calib);
@@ -189,13 +187,6 @@ static int postpro_params(const char *what, int B, int H, int W, double calib, P
     return PIVLFN_OK;
 }
 
-static unsigned postpro_grid(int H, int W, int frames_in_grid)
-{
-    const size_t g = ((size_t)H * W + 255) / 256;
-    const size_t cap = 16384 / (size_t)frames_in_grid > 64 ? 16384 / (size_t)frames_in_grid : 64;   // about as many workgroups as one flat launch
-    return (unsigned)(g > cap ? cap : g);
-}
-
 int launch_flow_fields(const float *flow, void *out, int B, int H, int W, double calib, int kind, int out_f64, hipStream_t st)
 {
     PIV_REQUIRE(flow && out, "flow_fields: null pointer (flow and out are required)");
@@ -206,7 +197,7 @@ int launch_flow_fields(const float *flow, void *out, int B, int H, int W, double
     PIV_REQUIRE(kind == PIVLFN_FIELDS_CALC_VORTICITY || kind == PIVLFN_FIELDS_DE_VORT,
                 "flow_fields: unknown kind=%d (PIVLFN_FIELDS_CALC_VORTICITY 0 or PIVLFN_FIELDS_DE_VORT 1)", kind);
     PIV_REQUIRE(out_f64 == 0 || out_f64 == 1, "flow_fields: out_f64=%d must be 0 (fp32) or 1 (fp64)", out_f64);
-    const dim3 grid(postpro_grid(H, W, B), (unsigned)B);
+    const dim3 grid(frame_grid((size_t)H * W, B), (unsigned)B);
     if (kind == PIVLFN_FIELDS_CALC_VORTICITY) {
         if (out_f64)
             hipLaunchKernelGGL((flow_fields_kernel<PIVLFN_FIELDS_CALC_VORTICITY, double>), grid, dim3(256), 0, st, flow, (double *)out, p);
@@ -228,7 +219,7 @@ int launch_flow_stats(const float *flow, double *acc, int B, int H, int W, doubl
     PostproParams p;
     const int rc = postpro_params("flow_stats_accumulate", B, H, W, calib, p);
     if (rc != PIVLFN_OK) return rc;
-    hipLaunchKernelGGL(flow_stats_kernel, dim3(postpro_grid(H, W, 1)), dim3(256), 0, st, flow, acc, B, p);
+    hipLaunchKernelGGL(flow_stats_kernel, dim3(frame_grid((size_t)H * W, 1)), dim3(256), 0, st, flow, acc, B, p);
     PIV_CHECK_HIP(hipGetLastError());
     return PIVLFN_OK;
 }
@@ -240,7 +231,7 @@ int launch_flow_stats_masked(const float *flow, const unsigned char *flag, doubl
     PostproParams p;
     const int rc = postpro_params("flow_stats_accumulate_masked", B, H, W, calib, p);
     if (rc != PIVLFN_OK) return rc;
-    hipLaunchKernelGGL(flow_stats_masked_kernel, dim3(postpro_grid(H, W, 1)), dim3(256), 0, st, flow, flag, acc, cnt, B, p);
+    hipLaunchKernelGGL(flow_stats_masked_kernel, dim3(frame_grid((size_t)H * W, 1)), dim3(256), 0, st, flow, flag, acc, cnt, B, p);
     PIV_CHECK_HIP(hipGetLastError());
     return PIVLFN_OK;
 }

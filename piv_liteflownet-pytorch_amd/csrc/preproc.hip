@@ -14,7 +14,7 @@
 // is taken once, and each output adds a suffix of the RUN - 1 elements before and a prefix of the RUN - 1 after (k + RUN - 1 reads
 // for RUN outputs instead of RUN * k); sums slide.  Row strides are odd numbers of dwords, so lanes that walk down rows hit 32
 // different banks.  RS takes the place of RM, which is dead by then; 64 x 64 at k = 31 needs 74 KiB: two workgroups per CU.
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -261,12 +261,7 @@ __global__ __launch_bounds__(256) void frames_background_min_kernel(const unsign
 
 static bool aligned_to(const void *p, size_t a) { return p == nullptr || (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
 
-static bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
-    return pa < pb + nb && pb < pa + na;
-}
-
+// the shape of byte frames: its bound is on H*W*3, the bytes of a frame, so it is not launch_checks.h's check_shape
 static int check_frames(const char *what, int n, int H, int W)
 {
     PIV_REQUIRE(n > 0 && H > 0 && W > 0, "%s: bad shape n=%d H=%d W=%d (all must be positive)", what, n, H, W);
@@ -279,13 +274,13 @@ int launch_frames_background_min(const unsigned char *frames, unsigned char *bg,
     PIV_REQUIRE(frames && bg, "frames_background_min: null pointer (frames and bg are required)");
     if (int rc = check_frames("frames_background_min", n, H, W)) return rc;
     const size_t bytes = (size_t)H * W * 3;
-    PIV_REQUIRE(!overlap(frames, bytes * n, bg, bytes), "frames_background_min: bg aliases frames (bg must not overlap the frames)");
+    PIV_REQUIRE(!ranges_overlap(frames, bytes * n, bg, bytes), "frames_background_min: bg aliases frames (bg must not overlap the frames)");
     const bool vec = bytes % 4 == 0 && aligned_to(frames, 4) && aligned_to(bg, 4);
-    const size_t items = vec ? bytes / 4 : bytes, blocks = std::min<size_t>((items + 255) / 256, 16384);
+    const unsigned blocks = frame_grid(vec ? bytes / 4 : bytes, 1);
     if (vec)
-        hipLaunchKernelGGL(frames_background_min_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, frames, bg, n, bytes);
+        hipLaunchKernelGGL(frames_background_min_kernel<true>, dim3(blocks), dim3(256), 0, st, frames, bg, n, bytes);
     else
-        hipLaunchKernelGGL(frames_background_min_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, frames, bg, n, bytes);
+        hipLaunchKernelGGL(frames_background_min_kernel<false>, dim3(blocks), dim3(256), 0, st, frames, bg, n, bytes);
     PIV_CHECK_HIP(hipGetLastError());
     return PIVLFN_OK;
 }
@@ -299,12 +294,11 @@ int launch_frames_preprocess(const unsigned char *frames, const unsigned char *b
     PIV_REQUIRE(k == 0 || (k >= 3 && k <= 31 && (k & 1)), "frames_preprocess: k=%d must be 0 (no min-max) or odd in 3..31", k);
     PIV_REQUIRE(floor >= 1 && floor <= 255, "frames_preprocess: floor=%d must be in 1..255", floor);
     const size_t HW = (size_t)H * W;
-    PIV_REQUIRE(!overlap(frames, HW * 3 * n, out, HW * 12 * n), "frames_preprocess: out aliases frames (out must not overlap the frames)");
-    PIV_REQUIRE(!bg || !overlap(bg, HW * 3, out, HW * 12 * n), "frames_preprocess: out aliases bg (out must not overlap the background)");
+    PIV_REQUIRE(!ranges_overlap(frames, HW * 3 * n, out, HW * 12 * n), "frames_preprocess: out aliases frames (out must not overlap the frames)");
+    PIV_REQUIRE(!ranges_overlap(bg, HW * 3, out, HW * 12 * n), "frames_preprocess: out aliases bg (out must not overlap the background)");
     if (k == 0) {
         const bool vec = HW % 4 == 0 && aligned_to(frames, 4) && aligned_to(bg, 4) && aligned_to(out, 16);
-        const size_t items = vec ? HW / 4 : HW, cap = 16384 / (size_t)n > 64 ? 16384 / (size_t)n : 64;
-        const dim3 grid((unsigned)std::min((items + 255) / 256, cap), (unsigned)n);
+        const dim3 grid(frame_grid(vec ? HW / 4 : HW, n), (unsigned)n);
         if (vec)
             hipLaunchKernelGGL(frames_preprocess_scale_kernel<true>, grid, dim3(256), 0, st, frames, bg, out, (unsigned)HW);
         else

@@ -26,7 +26,7 @@
 // may belong to a later call, or -- the count and rr -- by the read-out.  d is no output, so where the stopping rule fires first the
 // last d is never formed.
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -451,12 +451,6 @@ __global__ __launch_bounds__(PR_THREADS) void pressure_read_kernel(const PrWs ws
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-static bool pr_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
-    return pa < pb + nb && pb < pa + na;
-}
-
 #define PR_SHAPE(fn, F, h, w)                                                                                                   \
     PIV_REQUIRE(h >= 1 && w >= 1, fn ": bad lattice h=%d w=%d (both must be positive)", h, w);                                   \
     PIV_REQUIRE((size_t)(F) * h * w < ((size_t)1 << 31), fn ": F*h*w=%zu nodes, must stay below 2^31 (32-bit node index)", (size_t)(F) * h * w)
@@ -475,10 +469,11 @@ int launch_pressure_gradient(const float *flows, int B, int h, int w, double s, 
     PIV_REQUIRE(std::isfinite(nu), "pressure_gradient: nu=%g must be finite", nu);
     PIV_REQUIRE(flows && g && valid, "pressure_gradient: null pointer (flows, g and valid are required)");
     const int F = B - 2;
-    const size_t N = (size_t)h * w, in_bytes = (size_t)B * 2 * N * 4, g_bytes = (size_t)F * 2 * N * 8, v_bytes = (size_t)F * N;
-    PIV_REQUIRE(!pr_overlap(g, g_bytes, flows, in_bytes), "pressure_gradient: g overlaps flows");
-    PIV_REQUIRE(!pr_overlap(valid, v_bytes, flows, in_bytes), "pressure_gradient: valid overlaps flows");
-    PIV_REQUIRE(!pr_overlap(valid, v_bytes, g, g_bytes), "pressure_gradient: valid overlaps g");
+    const size_t N = (size_t)h * w;
+    const Span in = {flows, (size_t)B * 2 * N * 4, "flows"}, grad = {g, (size_t)F * 2 * N * 8, "g"}, val = {valid, (size_t)F * N, "valid"};
+    if (int rc = check_apart("pressure_gradient", grad, in)) return rc;
+    if (int rc = check_apart("pressure_gradient", val, in)) return rc;
+    if (int rc = check_apart("pressure_gradient", val, grad)) return rc;
     const unsigned total = (unsigned)((size_t)F * N);
     hipLaunchKernelGGL(pressure_gradient_kernel, dim3((total + PR_THREADS - 1) / PR_THREADS), dim3(PR_THREADS), 0, st, flows, F, h, w, s, nu, g,
                        valid);
@@ -494,8 +489,8 @@ int launch_pressure_setup(const double *g, const unsigned char *valid, int F, in
     PIV_REQUIRE(g && valid, "pressure_setup: null pointer (g and valid are required)");
     PR_WORKSPACE("pressure_setup", F, h, w, ws, ws_bytes);
     const size_t N = (size_t)h * w, need = pressure_workspace_bytes(F, h, w);
-    PIV_REQUIRE(!pr_overlap(ws, need, g, (size_t)F * 2 * N * 8), "pressure_setup: the workspace overlaps g");
-    PIV_REQUIRE(!pr_overlap(ws, need, valid, (size_t)F * N), "pressure_setup: the workspace overlaps valid");
+    if (int rc = check_alias_by_input("pressure_setup", {{ws, need, "the workspace"}}, {{g, (size_t)F * 2 * N * 8, "g"}, {valid, (size_t)F * N, "valid"}}, ""))
+        return rc;
     const PrLayout L = pr_layout(ws, F, h, w);
     hipLaunchKernelGGL(pressure_setup_kernel, dim3((unsigned)F * (unsigned)L.ws.NB), dim3(PR_THREADS), 0, st, g, valid, s, L.ws);
     PIV_CHECK_HIP(hipGetLastError());
@@ -527,13 +522,11 @@ int launch_pressure_read(const void *ws, size_t ws_bytes, int F, int h, int w, d
     PIV_REQUIRE(p && flag && status, "pressure_read: null pointer (p, flag and status are required)");
     PR_WORKSPACE("pressure_read", F, h, w, ws, ws_bytes);
     const size_t N = (size_t)h * w, need = pressure_workspace_bytes(F, h, w);
-    const struct { const void *ptr; size_t bytes; const char *name; } outs[] = {{p, (size_t)F * N * 8, "p"}, {flag, (size_t)F * N, "flag"},
-                                                                               {status, (size_t)F * 32, "status"}};
+    const Span outs[] = {{p, (size_t)F * N * 8, "p"}, {flag, (size_t)F * N, "flag"}, {status, (size_t)F * 32, "status"}};
     for (int a = 0; a < 3; ++a) {
-        PIV_REQUIRE(!pr_overlap(outs[a].ptr, outs[a].bytes, ws, need), "pressure_read: %s overlaps the workspace", outs[a].name);
+        if (int rc = check_apart("pressure_read", outs[a], {ws, need, "the workspace"})) return rc;
         for (int b = a + 1; b < 3; ++b)
-            PIV_REQUIRE(!pr_overlap(outs[a].ptr, outs[a].bytes, outs[b].ptr, outs[b].bytes), "pressure_read: %s overlaps %s", outs[a].name,
-                        outs[b].name);
+            if (int rc = check_apart("pressure_read", outs[a], outs[b])) return rc;
     }
     const PrLayout L = pr_layout(const_cast<void *>(ws), F, h, w);
     hipLaunchKernelGGL(pressure_read_kernel, dim3((unsigned)F * (unsigned)L.ws.NB), dim3(PR_THREADS), 0, st, L.ws, p, flag, status);

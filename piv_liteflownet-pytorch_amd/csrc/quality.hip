@@ -13,7 +13,7 @@
 // one) and adds every term it reads to those whose window holds it, the others get + 0.0 -- 4 + 2r LDS reads and products for 4
 // outputs instead of 4 (2r + 1).  The same lane owns the same outputs in all five shifts and keeps their correlations in registers.
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -244,19 +244,12 @@ size_t match_quality_workspace_bytes(int B, int H, int W, int radius)
     return (bytes + 255) / 256 * 256;
 }
 
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
-    return b != nullptr && pa < pb + nb && pb < pa + na;
-}
-
 // The first kernel of match_quality, shared with flow_uncertainty (uncertainty.hip): a, b and the byte of m and k of every pixel.  The
 // caller has checked the arguments (C is 1 or 3, 0 < B <= 65535, H*W < 2^31).
 int launch_quality_warp(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask, double *wa, double *wb,
                         unsigned char *wf, int B, int H, int W, hipStream_t st)
 {
-    const size_t g = ((size_t)H * W + 255) / 256, cap = 16384 / (size_t)B > 64 ? 16384 / (size_t)B : 64;
-    const dim3 wgrid((unsigned)(g > cap ? cap : g), (unsigned)B);
+    const dim3 wgrid(frame_grid((size_t)H * W, B), (unsigned)B);
     if (C == 1)
         hipLaunchKernelGGL(quality_warp_kernel<1>, wgrid, dim3(256), 0, st, img1, img2, flow, mask, wa, wb, wf, H, W);
     else
@@ -272,26 +265,20 @@ int launch_match_quality(const float *img1, const float *img2, int C, const floa
     PIV_REQUIRE(img1 && img2 && flow && quality && flag && ws,
                 "match_quality: null pointer (img1, img2, flow, quality, flag and the workspace are required)");
     PIV_REQUIRE(C == 1 || C == 3, "match_quality: C=%d channels, must be 1 or 3", C);
-    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "match_quality: bad shape B=%d H=%d W=%d (all must be positive)", B, H, W);
-    PIV_REQUIRE((size_t)H * W < ((size_t)1 << 31), "match_quality: H*W=%zu pixels, must stay below 2^31 (32-bit pixel index)",
-                (size_t)H * W);
-    PIV_REQUIRE(B <= 65535, "match_quality: B=%d pairs, at most 65535 per call (grid y dimension)", B);
+    if (int rc = check_shape("match_quality", B, H, W, "pairs")) return rc;
     PIV_REQUIRE(radius >= 1 && radius <= 15, "match_quality: radius=%d must be 1..15", radius);
     const int win = (2 * radius + 1) * (2 * radius + 1);
     PIV_REQUIRE(min_count >= 2 && min_count <= win, "match_quality: min_count=%d must be 2..%d, the pixels of the window", min_count, win);
     PIV_REQUIRE(std::isfinite(floor) && floor >= 0.0, "match_quality: floor=%g must be finite and not negative", floor);
     const size_t px = (size_t)B * H * W, need = match_quality_workspace_bytes(B, H, W, radius);
-    PIV_REQUIRE(((size_t)ws & 7) == 0, "match_quality: the workspace must be 8-byte aligned");
-    PIV_REQUIRE(ws_bytes >= need, "match_quality: workspace of %zu bytes is too small, %zu needed for B=%d H=%d W=%d", ws_bytes, need, B, H,
-                W);
-    const struct { const void *ptr; size_t bytes; const char *name; } ins[] = {
-        {img1, px * C * 4, "img1"}, {img2, px * C * 4, "img2"}, {flow, px * 8, "flow"}, {mask, px, "mask"}, {ws, need, "the workspace"}};
-    for (const auto &in : ins) {
-        PIV_REQUIRE(!ranges_overlap(quality, px * 12, in.ptr, in.bytes), "match_quality: quality overlaps %s (outputs must not alias an input)",
-                    in.name);
-        PIV_REQUIRE(!ranges_overlap(flag, px, in.ptr, in.bytes), "match_quality: flag overlaps %s (outputs must not alias an input)", in.name);
-    }
-    PIV_REQUIRE(!ranges_overlap(quality, px * 12, flag, px), "match_quality: quality overlaps flag");
+    if (int rc = check_workspace("match_quality", ws, ws_bytes, need, "B=%d H=%d W=%d", B, H, W)) return rc;
+    const Span qual = {quality, px * 12, "quality"}, flg = {flag, px, "flag"};
+    if (int rc = check_alias_by_input("match_quality", {qual, flg},
+                                      {{img1, px * C * 4, "img1"}, {img2, px * C * 4, "img2"}, {flow, px * 8, "flow"}, {mask, px, "mask"},
+                                       {ws, need, "the workspace"}},
+                                      " (outputs must not alias an input)"))
+        return rc;
+    if (int rc = check_apart("match_quality", qual, flg)) return rc;
 
     double *wa = (double *)ws, *wb = wa + px;
     unsigned char *wf = (unsigned char *)(wb + px);

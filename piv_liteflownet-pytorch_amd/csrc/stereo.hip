@@ -3,7 +3,7 @@
 // One thread per output pixel, fused with estimate()'s output resize (inference.py:57-61) so the raw network output of an
 // interleaved [L0, R0, L1, R1, ...] batch goes straight to the payload.  Arithmetic contract: include/pivlfn.h.
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 #include "bilinear.h"
 
 namespace pivlfn {
@@ -108,10 +108,7 @@ int launch_stereo_2d3c(const float *flow, float *out, int B, int h, int w, int H
     p.mx = mul ? mul[0] : 1.f;
     p.my = mul ? mul[1] : 1.f;
     p.B = B; p.h = h; p.w = w; p.H = H; p.W = W;
-    size_t g = ((size_t)H * W + 255) / 256;
-    const size_t cap = 16384 / (size_t)B > 64 ? 16384 / (size_t)B : 64;       // about as many workgroups as one flat launch
-    g = g > cap ? cap : g;
-    hipLaunchKernelGGL(stereo_2d3c_kernel, dim3((unsigned)g, (unsigned)B), dim3(256), 0, st, flow, out, p);
+    hipLaunchKernelGGL(stereo_2d3c_kernel, dim3(frame_grid((size_t)H * W, B), (unsigned)B), dim3(256), 0, st, flow, out, p);
     PIV_CHECK_HIP(hipGetLastError());
     return PIVLFN_OK;
 }

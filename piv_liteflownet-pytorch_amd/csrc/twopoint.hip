@@ -18,7 +18,7 @@
 // The flow row, its partner and the mask are read straight from global memory: a frame and its mask stay in L2, and consecutive
 // separations of a row re-read lines the wave has just touched.
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -197,12 +197,6 @@ __global__ __launch_bounds__(TP_THREADS) void twopoint_kernel(const TwoPointPara
         for (int r = r_first, s = 0; r <= p.R; r += r_stride, ++s) out[r * r_pitch] = mine[s * TP_SLOT];
 }
 
-static bool tp_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
-    return b != nullptr && pa < pb + nb && pb < pa + na;
-}
-
 int launch_twopoint_accumulate(const float *flow, const unsigned char *mask, const double *mean, double *acc, int B, int H, int W,
                                int max_sep, int step, hipStream_t st)
 {
@@ -215,10 +209,10 @@ int launch_twopoint_accumulate(const float *flow, const unsigned char *mask, con
     if (B == 0) return PIVLFN_OK;                                              // nothing to add: no pointer is read
     PIV_REQUIRE(flow && acc, "twopoint_accumulate: null pointer (flow and acc are required)");
     const size_t px = (size_t)H * W, acc_bytes = (size_t)2 * (max_sep + 1) * TP_TERMS * H * sizeof(double);
-    const struct { const void *ptr; size_t bytes; const char *name; } ins[] = {{flow, (size_t)B * px * 8, "flow"}, {mask, (size_t)B * px, "mask"},
-                                                                              {mean, px * 16, "mean"}};
-    for (const auto &in : ins)
-        PIV_REQUIRE(!tp_overlap(acc, acc_bytes, in.ptr, in.bytes), "twopoint_accumulate: acc overlaps %s (the sums must not alias an input)", in.name);
+    if (int rc = check_alias_by_input("twopoint_accumulate", {{acc, acc_bytes, "acc"}},
+                                      {{flow, (size_t)B * px * 8, "flow"}, {mask, (size_t)B * px, "mask"}, {mean, px * 16, "mean"}},
+                                      " (the sums must not alias an input)"))
+        return rc;
 
     TwoPointParams p = {flow, mask, mean, acc, B, H, W, max_sep, step, 0, 1, 1};
     while ((1 << p.levels) < W) ++p.levels;

@@ -16,7 +16,7 @@
 // valid pixel is 1.0, a valid x pair 1024.0, a valid y pair 1048576.0: a window holds at most 961 of each, the sum is exact in any
 // order and is taken apart again as an integer).  At r = 15 the plane and its row sums take 46 KB of LDS: three workgroups on a CU.
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -274,12 +274,6 @@ size_t flow_uncertainty_workspace_bytes(int B, int H, int W, int radius, int lag
     return (bytes + 255) / 256 * 256;
 }
 
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
-    return b != nullptr && pa < pb + nb && pb < pa + na;
-}
-
 int launch_flow_uncertainty(const float *img1, const float *img2, int C, const float *flow, const unsigned char *mask, float *unc,
                             unsigned char *flag, int B, int H, int W, int radius, int lag, int min_count, double floor, void *ws,
                             size_t ws_bytes, hipStream_t st)
@@ -287,10 +281,7 @@ int launch_flow_uncertainty(const float *img1, const float *img2, int C, const f
     PIV_REQUIRE(img1 && img2 && flow && unc && flag && ws,
                 "flow_uncertainty: null pointer (img1, img2, flow, unc, flag and the workspace are required)");
     PIV_REQUIRE(C == 1 || C == 3, "flow_uncertainty: C=%d channels, must be 1 or 3", C);
-    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "flow_uncertainty: bad shape B=%d H=%d W=%d (all must be positive)", B, H, W);
-    PIV_REQUIRE((size_t)H * W < ((size_t)1 << 31), "flow_uncertainty: H*W=%zu pixels, must stay below 2^31 (32-bit pixel index)",
-                (size_t)H * W);
-    PIV_REQUIRE(B <= 65535, "flow_uncertainty: B=%d pairs, at most 65535 per call (grid y dimension)", B);
+    if (int rc = check_shape("flow_uncertainty", B, H, W, "pairs")) return rc;
     PIV_REQUIRE(radius >= 1 && radius <= 15, "flow_uncertainty: radius=%d must be 1..15", radius);
     PIV_REQUIRE(lag >= 0 && lag <= 4, "flow_uncertainty: lag=%d must be 0..4", lag);
     const int win = (2 * radius + 1) * (2 * radius + 1);
@@ -298,18 +289,14 @@ int launch_flow_uncertainty(const float *img1, const float *img2, int C, const f
                 win);
     PIV_REQUIRE(std::isfinite(floor) && floor >= 0.0, "flow_uncertainty: floor=%g must be finite and not negative", floor);
     const size_t px = (size_t)B * H * W, need = flow_uncertainty_workspace_bytes(B, H, W, radius, lag);
-    PIV_REQUIRE(((size_t)ws & 7) == 0, "flow_uncertainty: the workspace must be 8-byte aligned");
-    PIV_REQUIRE(ws_bytes >= need, "flow_uncertainty: workspace of %zu bytes is too small, %zu needed for B=%d H=%d W=%d", ws_bytes, need,
-                B, H, W);
-    const struct { const void *ptr; size_t bytes; const char *name; } ins[] = {
-        {img1, px * C * 4, "img1"}, {img2, px * C * 4, "img2"}, {flow, px * 8, "flow"}, {mask, px, "mask"}, {ws, need, "the workspace"}};
-    for (const auto &in : ins) {
-        PIV_REQUIRE(!ranges_overlap(unc, px * 8, in.ptr, in.bytes), "flow_uncertainty: unc overlaps %s (outputs must not alias an input)",
-                    in.name);
-        PIV_REQUIRE(!ranges_overlap(flag, px, in.ptr, in.bytes), "flow_uncertainty: flag overlaps %s (outputs must not alias an input)",
-                    in.name);
-    }
-    PIV_REQUIRE(!ranges_overlap(unc, px * 8, flag, px), "flow_uncertainty: unc overlaps flag");
+    if (int rc = check_workspace("flow_uncertainty", ws, ws_bytes, need, "B=%d H=%d W=%d", B, H, W)) return rc;
+    const Span uq = {unc, px * 8, "unc"}, flg = {flag, px, "flag"};
+    if (int rc = check_alias_by_input("flow_uncertainty", {uq, flg},
+                                      {{img1, px * C * 4, "img1"}, {img2, px * C * 4, "img2"}, {flow, px * 8, "flow"}, {mask, px, "mask"},
+                                       {ws, need, "the workspace"}},
+                                      " (outputs must not alias an input)"))
+        return rc;
+    if (int rc = check_apart("flow_uncertainty", uq, flg)) return rc;
 
     // wa and wb hold a and b until the high-pass has read them, then g_x and g_y
     double *wa = (double *)ws, *wb = wa + px, *ha = wb + px, *hb = ha + px, *pp = hb + px, *sx = pp + px, *sy = sx + px, *dx = sy + px,
@@ -323,9 +310,8 @@ int launch_flow_uncertainty(const float *img1, const float *img2, int C, const f
     hipLaunchKernelGGL(unc_highpass_kernel, tgrid, dim3(UQ_THREADS), unc_lds_bytes(radius), st, p);
     PIV_CHECK_HIP(hipGetLastError());
 
-    const size_t g = ((size_t)H * W + 255) / 256, cap = 16384 / (size_t)B > 64 ? 16384 / (size_t)B : 64;
-    hipLaunchKernelGGL(unc_fields_kernel, dim3((unsigned)(g > cap ? cap : g), (unsigned)B), dim3(256), 0, st, ha, hb, wf, pp, sx, sy, dx,
-                       dy, code, H, W);
+    hipLaunchKernelGGL(unc_fields_kernel, dim3(frame_grid((size_t)H * W, B), (unsigned)B), dim3(256), 0, st, ha, hb, wf, pp, sx, sy, dx, dy,
+                       code, H, W);
     PIV_CHECK_HIP(hipGetLastError());
 
     p.a = dx, p.b = dy, p.f = code, p.o0 = wa, p.o1 = wb, p.r = lag;
@@ -341,9 +327,7 @@ int launch_flow_uncertainty(const float *img1, const float *img2, int C, const f
 int launch_uncertainty_accumulate(const float *unc, const unsigned char *flag, double *sums, int B, int H, int W, hipStream_t st)
 {
     PIV_REQUIRE(unc && flag && sums, "uncertainty_accumulate: null pointer (unc, flag and sums are required)");
-    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "uncertainty_accumulate: bad shape B=%d H=%d W=%d (all must be positive)", B, H, W);
-    PIV_REQUIRE((size_t)H * W < ((size_t)1 << 31), "uncertainty_accumulate: H*W=%zu pixels, must stay below 2^31 (32-bit pixel index)",
-                (size_t)H * W);
+    if (int rc = check_shape("uncertainty_accumulate", B, H, W, "frames", false)) return rc;
     PIV_REQUIRE(((size_t)sums & 7) == 0, "uncertainty_accumulate: sums must be 8-byte aligned");
     const size_t px = (size_t)B * H * W, hw = (size_t)H * W;
     PIV_REQUIRE(!ranges_overlap(sums, hw * 24, unc, px * 8) && !ranges_overlap(sums, hw * 24, flag, px),

@@ -10,7 +10,7 @@
 // pruned at compile time to the compare-exchanges its two middle outputs depend on.
 #include <cmath>
 #include <utility>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -275,13 +275,6 @@ __global__ __launch_bounds__(256) void validate_replace_kernel(const float *__re
     }
 }
 
-static unsigned validate_grid(int H, int W, int B)
-{
-    const size_t g = ((size_t)H * W + 255) / 256;
-    const size_t cap = 16384 / (size_t)B > 64 ? 16384 / (size_t)B : 64;
-    return (unsigned)(g > cap ? cap : g);
-}
-
 int launch_flow_validate(const float *flow, float *out, unsigned char *flag, float *resid, int B, int H, int W, int radius,
                          int spacing, float eps, float thresh, int mode, hipStream_t st)
 {
@@ -290,17 +283,14 @@ int launch_flow_validate(const float *flow, float *out, unsigned char *flag, flo
                 "flow_validate: unknown mode=%d (PIVLFN_VALIDATE_FLAG 0, PIVLFN_VALIDATE_MASK 1 or PIVLFN_VALIDATE_REPLACE 2)", mode);
     PIV_REQUIRE(out || mode == PIVLFN_VALIDATE_FLAG, "flow_validate: null out (only PIVLFN_VALIDATE_FLAG has no flow output)");
     PIV_REQUIRE(out != flow, "flow_validate: out == flow (pass 2 reads the neighbours of what it writes; out must not overlap flow)");
-    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "flow_validate: bad shape B=%d H=%d W=%d (all must be positive)", B, H, W);
-    PIV_REQUIRE((size_t)H * W < ((size_t)1 << 31), "flow_validate: H*W=%zu pixels, must stay below 2^31 (32-bit pixel index)",
-                (size_t)H * W);
-    PIV_REQUIRE(B <= 65535, "flow_validate: B=%d frames, at most 65535 per call (grid y dimension)", B);
+    if (int rc = check_shape("flow_validate", B, H, W, "frames")) return rc;
     PIV_REQUIRE(radius == 1 || radius == 2, "flow_validate: radius=%d must be 1 or 2", radius);
     PIV_REQUIRE(spacing >= 1 && (long)radius * spacing < (1L << 15), "flow_validate: spacing=%d must be >= 1 and radius*spacing below 2^15",
                 spacing);
     PIV_REQUIRE(std::isfinite(eps) && eps >= 0.0f, "flow_validate: eps=%g must be finite and not negative", (double)eps);
     PIV_REQUIRE(std::isfinite(thresh) && thresh > 0.0f, "flow_validate: thresh=%g must be finite and positive", (double)thresh);
     const ValidateParams p = {H, W, spacing, eps, thresh};
-    const dim3 grid(validate_grid(H, W, B), (unsigned)B);
+    const dim3 grid(frame_grid((size_t)H * W, B), (unsigned)B);
     float *masked = mode == PIVLFN_VALIDATE_MASK ? out : nullptr;
     if (radius == 1)
         hipLaunchKernelGGL(validate_detect_kernel<1>, grid, dim3(256), 0, st, flow, flag, resid, masked, p);

@@ -9,7 +9,7 @@
 // group when the output pointer is not 4-byte aligned.  Loads take 16 bytes per plane where H*W is a multiple of 4 and the planes are
 // 16-byte aligned (a group then lies inside one image), single floats otherwise.
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -294,14 +294,6 @@ __global__ __launch_bounds__(VZ_THREADS) void flow_decimate_kernel(const float *
     }
 }
 
-static int viz_check_shape(const char *what, int B, int H, int W)
-{
-    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d (all must be positive)", what, B, H, W);
-    PIV_REQUIRE((size_t)H * W < ((size_t)1 << 31), "%s: H*W=%zu pixels, must stay below 2^31 (32-bit pixel index)", what, (size_t)H * W);
-    PIV_REQUIRE(B <= 65535, "%s: B=%d images, at most 65535 per call (grid y dimension)", what, B);
-    return PIVLFN_OK;
-}
-
 static unsigned viz_blocks(size_t items)
 {
     const size_t g = (items + VZ_THREADS - 1) / VZ_THREADS;
@@ -313,8 +305,7 @@ static bool aligned_to(const void *p, size_t a) { return p == nullptr || ((size_
 int launch_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, hipStream_t st)
 {
     PIV_REQUIRE(flow && maxrad, "flow_maxrad: null pointer (flow and maxrad are required)");
-    const int rc = viz_check_shape("flow_maxrad", B, H, W);
-    if (rc != PIVLFN_OK) return rc;
+    if (int rc = check_shape("flow_maxrad", B, H, W, "images")) return rc;
     const unsigned HW = (unsigned)H * (unsigned)W;
     const int vec = HW % 4 == 0 && aligned_to(flow, 16) && aligned_to(mask, 4);
     PIV_CHECK_HIP(hipMemsetAsync(maxrad, 0, (size_t)B * sizeof(float), st));
@@ -328,8 +319,7 @@ int launch_flow_to_color(const float *flow, const float *norm, const unsigned ch
                          int wheel, int order, hipStream_t st)
 {
     PIV_REQUIRE(flow && norm && out, "flow_to_color: null pointer (flow, norm and out are required)");
-    const int rc = viz_check_shape("flow_to_color", B, H, W);
-    if (rc != PIVLFN_OK) return rc;
+    if (int rc = check_shape("flow_to_color", B, H, W, "images")) return rc;
     PIV_REQUIRE(wheel == PIVLFN_WHEEL_INTERP || wheel == PIVLFN_WHEEL_ORIGINAL, "flow_to_color: wheel=%d must be 0 (interpolated) or 1 (original)",
                 wheel);
     PIV_REQUIRE(order == PIVLFN_ORDER_RGB || order == PIVLFN_ORDER_BGR, "flow_to_color: order=%d must be 0 (rgb) or 1 (bgr)", order);
@@ -345,8 +335,7 @@ int launch_flow_to_color(const float *flow, const float *norm, const unsigned ch
 int launch_field_absmax(const void *field, int is_f64, const unsigned char *mask, double *absmax, int B, int H, int W, hipStream_t st)
 {
     PIV_REQUIRE(field && absmax, "field_absmax: null pointer (field and absmax are required)");
-    const int rc = viz_check_shape("field_absmax", B, H, W);
-    if (rc != PIVLFN_OK) return rc;
+    if (int rc = check_shape("field_absmax", B, H, W, "images")) return rc;
     PIV_REQUIRE(is_f64 == 0 || is_f64 == 1, "field_absmax: is_f64=%d must be 0 or 1", is_f64);
     const unsigned HW = (unsigned)H * (unsigned)W;
     PIV_CHECK_HIP(hipMemsetAsync(absmax, 0, (size_t)B * sizeof(double), st));
@@ -364,8 +353,7 @@ int launch_scalar_to_color(const void *field, int is_f64, const unsigned char *m
                            int H, int W, double vmin, double vmax, int bad_rgb, hipStream_t st)
 {
     PIV_REQUIRE(field && lut && out, "scalar_to_color: null pointer (field, lut and out are required)");
-    const int rc = viz_check_shape("scalar_to_color", B, H, W);
-    if (rc != PIVLFN_OK) return rc;
+    if (int rc = check_shape("scalar_to_color", B, H, W, "images")) return rc;
     PIV_REQUIRE(is_f64 == 0 || is_f64 == 1, "scalar_to_color: is_f64=%d must be 0 or 1", is_f64);
     PIV_REQUIRE(std::isfinite(vmin) && std::isfinite(vmax), "scalar_to_color: vmin=%g vmax=%g must be finite", vmin, vmax);
     PIV_REQUIRE(vmax != vmin, "scalar_to_color: vmax == vmin = %g leaves no range to map", vmin);
@@ -389,8 +377,7 @@ int launch_flow_decimate(const float *flow, const unsigned char *mask, float *me
                          hipStream_t st)
 {
     PIV_REQUIRE(flow && mean && count, "flow_decimate: null pointer (flow, mean and count are required)");
-    const int rc = viz_check_shape("flow_decimate", B, H, W);
-    if (rc != PIVLFN_OK) return rc;
+    if (int rc = check_shape("flow_decimate", B, H, W, "images")) return rc;
     PIV_REQUIRE(cell > 0 && cell <= 32768, "flow_decimate: cell=%d must be 1..32768", cell);
     const int ch = cdiv(H, cell), cw = cdiv(W, cell);
     const size_t ncells = (size_t)B * ch * cw;

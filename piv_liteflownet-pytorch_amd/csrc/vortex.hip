@@ -14,7 +14,7 @@
 // Gamma1 sum.  Pass 2, which needs the mean of pass 1: the Gamma2 sum, one fp64 square root and one fp64 division per neighbour --
 // that arithmetic, not LDS, is what the kernel's time goes to.
 #include <cmath>
-#include "common.h"
+#include "launch_checks.h"
 
 namespace pivlfn {
 
@@ -207,37 +207,26 @@ size_t vortex_gamma_workspace_bytes(int B, int H, int W, int radius, int spacing
     return (bytes + 255) / 256 * 256;
 }
 
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
-    return b != nullptr && pa < pb + nb && pb < pa + na;
-}
-
 int launch_vortex_gamma(const float *flow, const unsigned char *mask, float *gamma, unsigned char *flag, int B, int H, int W, int radius,
                         int spacing, int min_count, void *ws, size_t ws_bytes, hipStream_t st)
 {
     PIV_REQUIRE(flow && gamma && flag && ws, "vortex_gamma: null pointer (flow, gamma, flag and the workspace are required)");
-    PIV_REQUIRE(B > 0 && H > 0 && W > 0, "vortex_gamma: bad shape B=%d H=%d W=%d (all must be positive)", B, H, W);
-    PIV_REQUIRE((size_t)H * W < ((size_t)1 << 31), "vortex_gamma: H*W=%zu pixels, must stay below 2^31 (32-bit pixel index)", (size_t)H * W);
-    PIV_REQUIRE(B <= 65535, "vortex_gamma: B=%d pairs, at most 65535 per call (grid y dimension)", B);
+    if (int rc = check_shape("vortex_gamma", B, H, W, "pairs")) return rc;
     PIV_REQUIRE(radius >= 1 && radius <= 15, "vortex_gamma: radius=%d must be 1..15", radius);
     PIV_REQUIRE(spacing >= 1 && spacing <= 16, "vortex_gamma: spacing=%d must be 1..16", spacing);
     const int nb = (2 * radius + 1) * (2 * radius + 1) - 1;
     PIV_REQUIRE(min_count >= 1 && min_count <= nb, "vortex_gamma: min_count=%d must be 1..%d, the neighbours of the window", min_count, nb);
     const size_t px = (size_t)B * H * W, need = vortex_gamma_workspace_bytes(B, H, W, radius, spacing);
-    PIV_REQUIRE(((size_t)ws & 7) == 0, "vortex_gamma: the workspace must be 8-byte aligned");
-    PIV_REQUIRE(ws_bytes >= need, "vortex_gamma: workspace of %zu bytes is too small, %zu needed for B=%d H=%d W=%d", ws_bytes, need, B, H, W);
-    const struct { const void *ptr; size_t bytes; const char *name; } ins[] = {{flow, px * 8, "flow"}, {mask, px, "mask"}, {ws, need, "the workspace"}};
-    for (const auto &in : ins) {
-        PIV_REQUIRE(!ranges_overlap(gamma, px * 8, in.ptr, in.bytes), "vortex_gamma: gamma overlaps %s (outputs must not alias an input)", in.name);
-        PIV_REQUIRE(!ranges_overlap(flag, px, in.ptr, in.bytes), "vortex_gamma: flag overlaps %s (outputs must not alias an input)", in.name);
-    }
-    PIV_REQUIRE(!ranges_overlap(gamma, px * 8, flag, px), "vortex_gamma: gamma overlaps flag");
+    if (int rc = check_workspace("vortex_gamma", ws, ws_bytes, need, "B=%d H=%d W=%d", B, H, W)) return rc;
+    const Span gam = {gamma, px * 8, "gamma"}, flg = {flag, px, "flag"};
+    if (int rc = check_alias_by_input("vortex_gamma", {gam, flg}, {{flow, px * 8, "flow"}, {mask, px, "mask"}, {ws, need, "the workspace"}},
+                                      " (outputs must not alias an input)"))
+        return rc;
+    if (int rc = check_apart("vortex_gamma", gam, flg)) return rc;
 
     double *wx = (double *)ws, *wy = wx + px;
     unsigned char *wk = (unsigned char *)(wy + px);
-    const size_t g = ((size_t)H * W + 255) / 256, cap = 16384 / (size_t)B > 64 ? 16384 / (size_t)B : 64;
-    hipLaunchKernelGGL(vortex_stage_kernel, dim3((unsigned)(g > cap ? cap : g), (unsigned)B), dim3(256), 0, st, flow, mask, wx, wy, wk, H, W);
+    hipLaunchKernelGGL(vortex_stage_kernel, dim3(frame_grid((size_t)H * W, B), (unsigned)B), dim3(256), 0, st, flow, mask, wx, wy, wk, H, W);
     PIV_CHECK_HIP(hipGetLastError());
 
     VortParams p = {flow, wx, wy, wk, gamma, flag, H, W, radius, spacing, min_count, cdiv(cdiv(W, spacing), VX_TX)};

@@ -22,8 +22,7 @@ from typing import Dict, List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib
-from .postpro import _check_flows
+from . import _args, _lib
 
 FIELDS = ("n", "l1", "epe", "sq", "du", "dv", "max")         # the seven entries of a pair's sums, in order
 STAGES = ("M", "S", "R")
@@ -69,7 +68,7 @@ def _from_sums(sums: torch.Tensor, emap: Optional[torch.Tensor] = None) -> FlowE
 
 
 def _pool_exponent(pool) -> int:
-    if isinstance(pool, bool) or not isinstance(pool, int) or pool not in (1, 2, 4, 8, 16, 32):
+    if not _args.is_int(pool) or pool not in (1, 2, 4, 8, 16, 32):
         raise ValueError(f"pool={pool!r} must be a power of two from 1 to 32 (the pooled window's side)")
     return pool.bit_length() - 1
 
@@ -82,19 +81,6 @@ def _check_truth(truth: torch.Tensor, flow: torch.Tensor, what: str) -> torch.Te
         raise ValueError(f"{what}: truth {tuple(truth.shape)} on {truth.device} does not belong to flows {tuple(flow.shape)} on "
                          f"{flow.device}")
     return truth.detach().contiguous()
-
-
-def _check_mask(mask, truth: torch.Tensor, what: str) -> Optional[torch.Tensor]:
-    if mask is None:
-        return None
-    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
-        raise TypeError(f"{what}: expected a uint8 or bool mask [B,H,W], got "
-                        f"{mask.dtype if isinstance(mask, torch.Tensor) else type(mask).__name__}")
-    if mask.device != truth.device or tuple(mask.shape) != (truth.size(0), truth.size(2), truth.size(3)):
-        raise ValueError(f"{what}: mask {tuple(mask.shape)} on {mask.device} does not belong to truth {tuple(truth.shape)} on "
-                         f"{truth.device}")
-    mask = mask.detach().contiguous()
-    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
 
 
 def _workspace(B: int, H: int, W: int, device) -> torch.Tensor:
@@ -110,9 +96,9 @@ def flow_errors(flow: torch.Tensor, truth: torch.Tensor, mask: Optional[torch.Te
     (NaN or beyond 1e9 in magnitude) or a nonzero byte of `mask` [B,H,W]; a non-finite estimated flow is not left out and makes the
     sums non-finite."""
     k = _pool_exponent(pool)
-    flow = _check_flows(flow, "flow_errors")
+    flow = _args.check_flows(flow, "flow_errors")
     truth = _check_truth(truth, flow, "flow_errors")
-    mask = _check_mask(mask, truth, "flow_errors")
+    mask = _args.check_mask(mask, "flow_errors", truth=truth)
     B, _, H, W = truth.shape
     if H % pool or W % pool or tuple(flow.shape[2:]) != (H // pool, W // pool):
         raise ValueError(f"flow_errors: flows {tuple(flow.shape)} are not truth {tuple(truth.shape)} pooled by {pool}")
@@ -139,9 +125,9 @@ def level_errors(net_or_lowest_level, levels, truth: torch.Tensor, div_flow: flo
     nlev = 7 - lowest
     if not isinstance(levels, (list, tuple)) or len(levels) != nlev or any(not isinstance(t, (list, tuple)) or len(t) != 3 for t in levels):
         raise ValueError(f"level_errors: expected {nlev} levels of three flows (M, S, R), coarsest first")
-    flat = [_check_flows(f, "level_errors") for trio in levels for f in trio]
+    flat = [_args.check_flows(f, "level_errors") for trio in levels for f in trio]
     truth = _check_truth(truth, flat[0], "level_errors")
-    mask = _check_mask(mask, truth, "level_errors")
+    mask = _args.check_mask(mask, "level_errors", truth=truth)
     B, _, H, W = truth.shape
     if H % 32 or W % 32:
         raise ValueError(f"level_errors: truth {H} x {W} must be multiples of 32 (level 6 averages 32 x 32 windows)")
@@ -201,9 +187,9 @@ class ErrorStats:
 
     def update(self, flow: torch.Tensor, truth: torch.Tensor, mask: Optional[torch.Tensor] = None) -> None:
         """Add the frames of `flow` against `truth` (both [B,2,H,W] float32 on this device), in batch order; `mask` as flow_errors."""
-        flow = _check_flows(flow, "ErrorStats.update")
+        flow = _args.check_flows(flow, "ErrorStats.update")
         truth = _check_truth(truth, flow, "ErrorStats.update")
-        mask = _check_mask(mask, truth, "ErrorStats.update")
+        mask = _args.check_mask(mask, "ErrorStats.update", truth=truth)
         if tuple(flow.shape[2:]) != (self.H, self.W) or truth.shape != flow.shape or flow.device != self.device:
             raise ValueError(f"ErrorStats.update: flows {tuple(flow.shape)} and truth {tuple(truth.shape)} on {flow.device}, accumulators "
                              f"[{self.H},{self.W}] on {self.device}")

@@ -28,9 +28,7 @@ from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _lib
-from .evaluate import _check_mask
-from .postpro import _check_flows
+from . import _args, _lib
 
 OUT, LOST, UNDEFINED = 1, 2, 4          # the bits of a flag byte (PIVLFN_FLOWMAP_*)
 
@@ -38,14 +36,12 @@ OUT, LOST, UNDEFINED = 1, 2, 4          # the bits of a flag byte (PIVLFN_FLOWMA
 def check_params(H, W, spacing=1, iters=8) -> Tuple[int, int]:
     """The parameter checks of FlowMap (ValueError), usable before any tensor exists; H and W may be None where the frame size is not
     known yet.  Returns the lattice size (h, w) -- (None, None) without a frame size."""
-    if isinstance(spacing, bool) or not isinstance(spacing, int) or not 1 <= spacing <= 32768:
-        raise ValueError(f"FlowMap: spacing={spacing!r} must be an integer 1..32768, the distance between seeds in pixels")
-    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= 32:
-        raise ValueError(f"FlowMap: iters={iters!r} must be an integer 1..32, the fixed-point iterations of a backward step")
+    _args.check_int("FlowMap", "spacing", spacing, 1, 32768, ", the distance between seeds in pixels")
+    _args.check_int("FlowMap", "iters", iters, 1, 32, ", the fixed-point iterations of a backward step")
     if H is None and W is None:
         return None, None
     for name, v in (("H", H), ("W", W)):
-        if isinstance(v, bool) or not isinstance(v, int) or v < 2:
+        if not _args.is_int(v, 2):
             raise ValueError(f"FlowMap: {name}={v!r} must be an integer >= 2 (a bilinear sample needs 2 x 2 vectors)")
     if H * W >= 1 << 31:
         raise ValueError(f"FlowMap: H*W={H * W} pixels, must stay below 2^31")
@@ -134,8 +130,8 @@ class FlowMap:
         `backward` -- in one launch, and adds B to `steps`.  `mask` [B,H,W] uint8 or bool: nonzero vectors are not to be used (the flag
         of validate_flow); unknown vectors (NaN, inf, 1e10) are left out by themselves.  With `trace`: returns the positions after
         every field, [B,2,h,w] or [B,2,N] float64."""
-        flow = _check_flows(flow, "FlowMap.update")
-        mask = _check_mask(mask, flow, "FlowMap.update")
+        flow = _args.check_flows(flow, "FlowMap.update")
+        mask = _args.check_mask(mask, "FlowMap.update", truth=flow)
         B = flow.size(0)
         if tuple(flow.shape[2:]) != (self.H, self.W) or flow.device != self.device:
             raise ValueError(f"FlowMap.update: flows {tuple(flow.shape)} on {flow.device} do not belong to a map of {self.H} x {self.W} "

@@ -28,7 +28,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 LOST, BAD = 2, 8                        # the bits of a particle's flag byte (PIVLFN_PARTICLES_*)
 METHODS = {"bilinear": 0, "cubic": 1}
@@ -49,10 +49,6 @@ class PairParticles(NamedTuple):
     flag: torch.Tensor            # uint8 [2B,N]: 0 in the first frames; LOST | BAD of the displacement in the second
 
 
-def _is_int(v) -> bool:
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-
-
 def _is_real(v) -> bool:
     return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
 
@@ -66,7 +62,7 @@ def check_method(method) -> int:
 def check_image(H, W, radius=4, what="render_particles") -> None:
     """The size and radius checks of the renderer (ValueError / TypeError), usable before any tensor exists."""
     for name, v in (("H", H), ("W", W), ("radius", radius)):
-        if not _is_int(v):
+        if not _args.is_integer(v):
             raise TypeError(f"{what}: {name}={v!r} must be an integer")
     if H < 1 or W < 1:
         raise ValueError(f"{what}: H={H} W={W} must both be positive")
@@ -86,10 +82,6 @@ def _check_tensor(t, name, dtype, what):
 def _check_cuda(t, what):
     if not t.is_cuda:
         raise NotImplementedError(f"{what}: GPU tensors only")
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
 
 
 def displace_particles(pos: torch.Tensor, flow: torch.Tensor, mask: Optional[torch.Tensor] = None, method: str = "bilinear",
@@ -130,7 +122,7 @@ def displace_particles(pos: torch.Tensor, flow: torch.Tensor, mask: Optional[tor
     oflag = flag.detach().clone() if flag is not None else torch.zeros([N], dtype=torch.uint8, device=pos.device)
     out = torch.empty_like(pos)
     with torch.cuda.device(pos.device):
-        _lib.check(_lib.load().pivlfn_particles_displace(pos.data_ptr(), flow.data_ptr(), _ptr(mask), H, W, N, code, oflag.data_ptr(),
+        _lib.check(_lib.load().pivlfn_particles_displace(pos.data_ptr(), flow.data_ptr(), _args.ptr(mask), H, W, N, code, oflag.data_ptr(),
                                                          out.data_ptr(), _lib.stream_ptr(pos.device)), what)
     return out, oflag
 
@@ -171,7 +163,7 @@ def render_particles(pos: torch.Tensor, diam: torch.Tensor, amp: torch.Tensor, H
     image = torch.empty([B, H, W], dtype=torch.uint8, device=pos.device)
     ws = torch.empty(lib.pivlfn_particles_render_workspace_bytes(B, N, H, W, radius), dtype=torch.uint8, device=pos.device)
     with torch.cuda.device(pos.device):
-        _lib.check(lib.pivlfn_particles_render(pos.data_ptr(), diam.data_ptr(), amp.data_ptr(), _ptr(flag), B, N, H, W, radius,
+        _lib.check(lib.pivlfn_particles_render(pos.data_ptr(), diam.data_ptr(), amp.data_ptr(), _args.ptr(flag), B, N, H, W, radius,
                                                intensity.data_ptr(), image.data_ptr(), ws.data_ptr(), ws.numel(),
                                                _lib.stream_ptr(pos.device)), what)
     return ParticleImages(image[0], intensity[0]) if single else ParticleImages(image, intensity)
@@ -194,7 +186,7 @@ class ParticleImageGen:
             raise ValueError("ParticleImageGen: avg_diameter and std_diameter are both 0: the particles would have no size")
         if laser_thickness <= 0:
             raise ValueError(f"ParticleImageGen: laser_thickness={laser_thickness!r} must be positive")
-        if not _is_int(seed):
+        if not _args.is_integer(seed):
             raise TypeError(f"ParticleImageGen: seed={seed!r} must be an integer")
         self.p_density, self.p_avg_d, self.p_std_d, self.lt = float(density), float(avg_diameter), float(std_diameter), float(laser_thickness)
         self.seed = int(seed)
@@ -204,7 +196,7 @@ class ParticleImageGen:
     def count(self, H: int, W: int, pad: int = 0) -> int:
         """floor(density * area) over the padded area, as the reference counts."""
         check_image(H, W, 4, "ParticleImageGen")
-        if not _is_int(pad):
+        if not _args.is_integer(pad):
             raise TypeError(f"ParticleImageGen: pad={pad!r} must be an integer")
         if not 0 <= pad <= 1 << 20:
             raise ValueError(f"ParticleImageGen: pad={pad} must be 0..2^20 pixels")
@@ -260,7 +252,7 @@ class ParticleImageGen:
             raise TypeError(f"create_pair_from_flow: out_of_plane={out_of_plane!r} must be a number")
         if not math.isfinite(out_of_plane) or out_of_plane < 0:
             raise ValueError(f"create_pair_from_flow: out_of_plane={out_of_plane!r} must be finite and not negative")
-        if not _is_int(pad):
+        if not _args.is_integer(pad):
             raise TypeError(f"create_pair_from_flow: pad={pad!r} must be an integer")
         if not 0 <= pad <= 1 << 20:
             raise ValueError(f"create_pair_from_flow: pad={pad} must be 0..2^20 pixels")

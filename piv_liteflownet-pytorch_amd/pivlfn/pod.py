@@ -19,7 +19,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 MAX_SNAPSHOTS = 4096          # PIVLFN_POD_MAX_SNAPSHOTS
 MAX_MODES = 64
@@ -46,7 +46,7 @@ class PODResult:
         """Snapshot i from the mean and its first r modes (all kept modes by default): [2,ch,cw]."""
         K = self.modes.shape[0]
         r = K if r is None else r
-        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= r <= K:
+        if not _args.is_integer(r) or not 0 <= r <= K:
             raise ValueError(f"reconstruct: r={r!r} must be 0..{K}, the modes kept")
         if not -self.coeff.shape[0] <= i < self.coeff.shape[0]:
             raise IndexError(f"reconstruct: snapshot {i} of {self.coeff.shape[0]}")
@@ -59,7 +59,7 @@ class PODResult:
 
 
 def check_capacity(capacity) -> int:
-    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 2 <= capacity <= MAX_SNAPSHOTS:
+    if not _args.is_int(capacity, 2, MAX_SNAPSHOTS):
         raise ValueError(f"FlowPOD: capacity={capacity!r} must be an integer from 2 to {MAX_SNAPSHOTS} snapshots (the Gram matrix is "
                          "solved on the host)")
     return capacity
@@ -73,7 +73,7 @@ def check_solve(n: int, modes, empty: int) -> int:
     if n < 2:
         raise ValueError(f"FlowPOD.solve: {n} snapshot(s) stored, at least 2 are needed")
     top = min(MAX_MODES, n - 1)
-    if isinstance(modes, bool) or not isinstance(modes, int) or not 1 <= modes <= top:
+    if not _args.is_int(modes, 1, top):
         raise ValueError(f"FlowPOD.solve: modes={modes!r} must be 1..{top} (at most {MAX_MODES}, and n - 1 = {n - 1}: centring takes one "
                          "degree of freedom)")
     return modes
@@ -146,7 +146,7 @@ class FlowPOD:
 
     def __init__(self, H: int, W: int, capacity: int, cell: int = 1, device=None):
         check_capacity(capacity)
-        if isinstance(cell, bool) or not isinstance(cell, int) or not 1 <= cell <= 32768:
+        if not _args.is_int(cell, 1, 32768):
             raise ValueError(f"FlowPOD: cell={cell!r} must be an integer from 1 to 32768")
         if H < 1 or W < 1:
             raise ValueError(f"FlowPOD: bad flow size {H} x {W}")

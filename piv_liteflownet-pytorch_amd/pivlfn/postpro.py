@@ -17,37 +17,17 @@ GPU only, like the rest of the package: there is no CPU path.
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 KINDS = {"calc_vorticity": 0, "de_vort": 1}          # PIVLFN_FIELDS_CALC_VORTICITY, PIVLFN_FIELDS_DE_VORT
 PLANES = {"calc_vorticity": ("vort", "shear", "normal"), "de_vort": ("vort", "uy", "vx")}
 SUMS = ("sum_u", "sum_v", "sum_uu", "sum_vv", "sum_uv", "sum_w", "sum_ww")     # the planes of FlowStats.acc, in order
 RESULT = ("count", "mean_u", "mean_v", "rms_u", "rms_v", "cov_uv", "mean_vort", "rms_vort")
-
-
-def _calib(calib) -> float:
-    c = float(calib)
-    if not math.isfinite(c) or c == 0.0:
-        raise ValueError(f"calib={c!r} must be finite and non-zero")
-    return c
-
-
-def _check_flows(flow: torch.Tensor, what: str) -> torch.Tensor:
-    if not isinstance(flow, torch.Tensor):
-        raise TypeError(f"{what}: expected a torch tensor [B,2,H,W], got {type(flow).__name__}")
-    if flow.dtype != torch.float32:
-        raise TypeError(f"{what}: expected float32 flows, got {flow.dtype}")
-    if not flow.is_cuda:
-        raise NotImplementedError(f"{what}: GPU tensors only")
-    if flow.dim() != 4 or flow.size(1) != 2:
-        raise ValueError(f"{what}: expected [B,2,H,W], got {tuple(flow.shape)}")
-    return flow.detach().contiguous()
 
 
 def flow_fields(flow: torch.Tensor, calib=1.0, kind: str = "calc_vorticity", dtype: torch.dtype = torch.float32) -> torch.Tensor:
@@ -58,13 +38,13 @@ def flow_fields(flow: torch.Tensor, calib=1.0, kind: str = "calc_vorticity", dty
         raise ValueError(f"flow_fields: unknown kind {kind!r} (one of {', '.join(KINDS)})")
     if dtype not in (torch.float32, torch.float64):
         raise TypeError(f"flow_fields: dtype must be torch.float32 or torch.float64, got {dtype}")
-    flow = _check_flows(flow, "flow_fields")
+    flow = _args.check_flows(flow, "flow_fields")
     B, _, H, W = flow.shape
     out = torch.empty([B, 3, H, W], dtype=dtype, device=flow.device)
     if B == 0:
         return out
     with torch.cuda.device(flow.device):
-        _lib.check(_lib.load().pivlfn_flow_fields(flow.data_ptr(), out.data_ptr(), B, H, W, _calib(calib), KINDS[kind],
+        _lib.check(_lib.load().pivlfn_flow_fields(flow.data_ptr(), out.data_ptr(), B, H, W, _args.check_calib(calib), KINDS[kind],
                                                   int(dtype == torch.float64), _lib.stream_ptr(flow.device)), "flow_fields")
     return out
 
@@ -117,7 +97,7 @@ class FlowStats:
     count.  update() enqueues one kernel on the current stream and never synchronises the host; result() / save() do."""
 
     def __init__(self, H: int, W: int, calib=1.0, device=None):
-        self.H, self.W, self.calib = int(H), int(W), _calib(calib)
+        self.H, self.W, self.calib = int(H), int(W), _args.check_calib(calib)
         if self.H <= 0 or self.W <= 0:
             raise ValueError(f"FlowStats: bad size {H} x {W}")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -128,7 +108,7 @@ class FlowStats:
 
     def update(self, flow: torch.Tensor) -> None:
         """Add the frames of `flow` [B,2,H,W] (float32, on this device), in batch order."""
-        flow = _check_flows(flow, "FlowStats.update")
+        flow = _args.check_flows(flow, "FlowStats.update")
         if tuple(flow.shape[2:]) != (self.H, self.W) or flow.device != self.device:
             raise ValueError(f"FlowStats.update: flows {tuple(flow.shape)} on {flow.device}, accumulators [{self.H},{self.W}] on "
                              f"{self.device}")

@@ -23,14 +23,14 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 
 def check_params(minmax, floor) -> None:
     """The parameter checks of preprocess_frames (ValueError), usable before any frame exists."""
-    if isinstance(minmax, bool) or not isinstance(minmax, int) or not (minmax == 0 or (3 <= minmax <= 31 and minmax % 2 == 1)):
+    if not (_args.is_int(minmax) and (minmax == 0 or (3 <= minmax <= 31 and minmax % 2 == 1))):
         raise ValueError(f"preprocess_frames: minmax={minmax!r} must be 0 (no normalisation) or an odd window size in 3..31")
-    if isinstance(floor, bool) or not isinstance(floor, int) or not 1 <= floor <= 255:
+    if not _args.is_int(floor, 1, 255):
         raise ValueError(f"preprocess_frames: floor={floor!r} must be an integer number of grey levels in 1..255")
 
 

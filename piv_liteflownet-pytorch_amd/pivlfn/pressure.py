@@ -26,15 +26,11 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, viz
+from . import _args, _lib, viz
 
 RUNNING, CONVERGED, BREAKDOWN = 1, 2, 3                  # PIVLFN_PRESSURE_*: the state of a frame
 OK, INVALID, ISOLATED = 0, 1, 2                          # the flag of a node
 WS_B, WS_X, WS_ADJ = 0, 1, 2
-
-
-def _is_int(x) -> bool:
-    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
 
 
 def _is_real(x) -> bool:
@@ -43,22 +39,22 @@ def _is_real(x) -> bool:
 
 def check_params(cell=4, calib=1.0, dt=1.0, rho=1.0, nu=0.0, tol=1e-8, max_iter=None, sync_every=64) -> None:
     """The parameter checks of PressureField (ValueError), usable before any tensor exists."""
-    if not _is_int(cell) or not 1 <= cell <= 32768:
+    if not _args.is_integer(cell) or not 1 <= cell <= 32768:
         raise ValueError(f"PressureField: cell={cell!r} must be an integer from 1 to 32768, the pixels per lattice node")
     for name, v in (("calib", calib), ("dt", dt), ("rho", rho), ("tol", tol)):
         if not _is_real(v) or not v > 0:
             raise ValueError(f"PressureField: {name}={v!r} must be finite and positive")
     if not _is_real(nu) or nu < 0:
         raise ValueError(f"PressureField: nu={nu!r} must be finite and not negative")
-    if max_iter is not None and (not _is_int(max_iter) or max_iter < 0):
+    if max_iter is not None and (not _args.is_integer(max_iter) or max_iter < 0):
         raise ValueError(f"PressureField: max_iter={max_iter!r} must be a non-negative integer or None")
-    if sync_every is not None and (not _is_int(sync_every) or sync_every < 1):
+    if sync_every is not None and (not _args.is_integer(sync_every) or sync_every < 1):
         raise ValueError(f"PressureField: sync_every={sync_every!r} must be a positive integer or None")
 
 
 def check_size(H, W, cell=4) -> Tuple[int, int]:
     """(ch, cw), the lattice of an H x W flow."""
-    if not _is_int(H) or not _is_int(W) or H < 1 or W < 1:
+    if not _args.is_integer(H) or not _args.is_integer(W) or H < 1 or W < 1:
         raise ValueError(f"PressureField: bad flow size {H!r} x {W!r}")
     ch, cw = -(-int(H) // cell), -(-int(W) // cell)
     if ch * cw >= 1 << 31:
@@ -69,7 +65,7 @@ def check_size(H, W, cell=4) -> Tuple[int, int]:
 def _check_reference(reference, ch, cw):
     if reference is None:
         return None
-    if (not isinstance(reference, (tuple, list)) or len(reference) != 2 or not all(_is_int(k) for k in reference)
+    if (not isinstance(reference, (tuple, list)) or len(reference) != 2 or not all(_args.is_integer(k) for k in reference)
             or not (0 <= reference[0] < ch and 0 <= reference[1] < cw)):
         raise ValueError(f"PressureField: reference={reference!r} must be a node (j, i) of the {ch} x {cw} lattice")
     return int(reference[0]), int(reference[1])

@@ -19,9 +19,7 @@ from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
-from . import _lib
-from .evaluate import _check_mask
-from .postpro import _check_flows
+from . import _args
 
 FEW, FLAT, NO_PEAK, CENTRE_OUT = 1, 2, 4, 8          # the bits of a flag byte (PIVLFN_QUALITY_*)
 FLAG_NAMES = ("few", "flat", "no_peak", "centre_out")
@@ -34,15 +32,11 @@ def default_min_count(radius: int) -> int:
 
 def check_params(radius, floor, min_count) -> int:
     """The parameter checks of match_quality (ValueError), usable before any image exists; returns the min_count in effect."""
-    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= 15:
-        raise ValueError(f"match_quality: radius={radius!r} must be an integer 1..15 (a window of 3 x 3 to 31 x 31 pixels)")
+    _args.check_int("match_quality", "radius", radius, 1, 15, " (a window of 3 x 3 to 31 x 31 pixels)")
     if min_count is None:
         min_count = default_min_count(radius)
-    if isinstance(min_count, bool) or not isinstance(min_count, int) or not 2 <= min_count <= (2 * radius + 1) ** 2:
-        raise ValueError(f"match_quality: min_count={min_count!r} must be an integer 2..{(2 * radius + 1) ** 2}, the pixels of the window")
-    floor = float(floor)
-    if not math.isfinite(floor) or floor < 0.0:
-        raise ValueError(f"match_quality: floor={floor!r} must be finite and not negative")
+    _args.check_int("match_quality", "min_count", min_count, 2, (2 * radius + 1) ** 2, ", the pixels of the window")
+    _args.check_not_negative("match_quality", "floor", floor)
     return min_count
 
 
@@ -91,18 +85,6 @@ def summarize(row) -> Dict[str, float]:
     return out
 
 
-def _check_images(img1, img2, what: str):
-    for name, t in (("img1", img1), ("img2", img2)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError(f"{what}: expected a float32 tensor [B,C,H,W] for {name}, got "
-                            f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
-    if img1.dim() != 4 or img1.size(1) not in (1, 3):
-        raise ValueError(f"{what}: expected images [B,C,H,W] with C = 1 or 3, got {tuple(img1.shape)}")
-    if img2.shape != img1.shape or img2.device != img1.device:
-        raise ValueError(f"{what}: img2 {tuple(img2.shape)} on {img2.device} does not belong to img1 {tuple(img1.shape)} on {img1.device}")
-    return img1.detach().contiguous(), img2.detach().contiguous()
-
-
 def match_quality(img1: torch.Tensor, img2: torch.Tensor, flow: torch.Tensor, radius: int = 8, mask: Optional[torch.Tensor] = None,
                   floor: float = 1.0 / 255.0, min_count: Optional[int] = None) -> MatchQuality:
     """Windowed correlation between img1 and img2 warped back by `flow`, and the sub-pixel residual of its peak, on the device;
@@ -117,23 +99,13 @@ def match_quality(img1: torch.Tensor, img2: torch.Tensor, flow: torch.Tensor, ra
     positive maximum of the five values, so the error of the vector is beyond half a pixel or the match is noise; CENTRE_OUT -- the
     pixel itself is masked or warps outside.  `residual` is the peak position by a three-point Gaussian fit per axis."""
     min_count = check_params(radius, floor, min_count)
-    img1, img2 = _check_images(img1, img2, "match_quality")
-    if isinstance(flow, torch.Tensor) and flow.dtype == torch.float32 and (
-            flow.dim() != 4 or flow.size(1) != 2 or flow.device != img1.device or flow.size(0) != img1.size(0)
-            or tuple(flow.shape[2:]) != tuple(img1.shape[2:])):
-        raise ValueError(f"match_quality: flows {tuple(flow.shape)} on {flow.device} do not belong to images {tuple(img1.shape)} on "
-                         f"{img1.device}")
-    flow = _check_flows(flow, "match_quality")
-    mask = _check_mask(mask, flow, "match_quality")
+    img1, img2 = _args.check_images(img1, img2, "match_quality")
+    flow = _args.check_flows(flow, "match_quality", images=img1)
+    mask = _args.check_mask(mask, "match_quality", truth=flow)
     B, C, H, W = img1.shape
     quality = torch.empty([B, 3, H, W], dtype=torch.float32, device=flow.device)
     flag = torch.empty([B, H, W], dtype=torch.uint8, device=flow.device)
     if B > 0:
-        with torch.cuda.device(flow.device):
-            lib = _lib.load()
-            ws = torch.empty(lib.pivlfn_match_quality_workspace_bytes(B, H, W, radius), dtype=torch.uint8, device=flow.device)
-            _lib.check(lib.pivlfn_match_quality(img1.data_ptr(), img2.data_ptr(), C, flow.data_ptr(),
-                                                mask.data_ptr() if mask is not None else None, quality.data_ptr(), flag.data_ptr(),
-                                                B, H, W, radius, min_count, float(floor), ws.data_ptr(), ws.numel(),
-                                                _lib.stream_ptr(flow.device)), "match_quality")
+        _args.call_with_workspace("match_quality", flow.device, (B, H, W, radius), img1.data_ptr(), img2.data_ptr(), C, flow.data_ptr(),
+                                  _args.ptr(mask), quality.data_ptr(), flag.data_ptr(), B, H, W, radius, min_count, float(floor))
     return MatchQuality(quality[:, 0], quality[:, 1:], flag)

@@ -27,7 +27,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 MAX_SEGMENT = 1024
 WINDOWS = ("hann", "boxcar")
@@ -42,19 +42,15 @@ class Launch(NamedTuple):
     first: int          # ring row of the segment's sample 0
 
 
-def _is_int(x) -> bool:
-    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
-
-
 def check_params(segment=256, overlap=None, window="hann", detrend="constant", cell=1, fs=1.0, kmax=None) -> Tuple[int, int]:
     """The parameter checks of TemporalSpectrum (ValueError), usable before any tensor exists: (overlap, kmax) with the defaults filled in."""
-    if not _is_int(segment) or not 2 <= segment <= MAX_SEGMENT:
+    if not _args.is_integer(segment) or not 2 <= segment <= MAX_SEGMENT:
         raise ValueError(f"TemporalSpectrum: segment={segment!r} must be an integer 2..{MAX_SEGMENT}, the frames of a segment")
     overlap = segment // 2 if overlap is None else overlap
-    if not _is_int(overlap) or not 0 <= overlap <= segment - 1:
+    if not _args.is_integer(overlap) or not 0 <= overlap <= segment - 1:
         raise ValueError(f"TemporalSpectrum: overlap={overlap!r} must be an integer 0..segment-1 = {segment - 1}")
     kmax = segment // 2 if kmax is None else kmax
-    if not _is_int(kmax) or not 1 <= kmax <= segment // 2:
+    if not _args.is_integer(kmax) or not 1 <= kmax <= segment // 2:
         raise ValueError(f"TemporalSpectrum: kmax={kmax!r} must be an integer 1..segment//2 = {segment // 2}, the highest frequency index kept")
     if window not in WINDOWS:
         raise ValueError(f"TemporalSpectrum: window={window!r} must be one of {', '.join(WINDOWS)}")
@@ -62,13 +58,13 @@ def check_params(segment=256, overlap=None, window="hann", detrend="constant", c
         raise ValueError(f"TemporalSpectrum: detrend={detrend!r} must be 'constant', 'linear' or None")
     if isinstance(fs, bool) or not isinstance(fs, (int, float, np.integer, np.floating)) or not (fs > 0 and math.isfinite(fs)):
         raise ValueError(f"TemporalSpectrum: fs={fs!r} must be a positive sampling rate")
-    if not _is_int(cell) or not 1 <= cell <= 32768:
+    if not _args.is_integer(cell) or not 1 <= cell <= 32768:
         raise ValueError(f"TemporalSpectrum: cell={cell!r} must be an integer from 1 to 32768")
     return int(overlap), int(kmax)
 
 
 def check_size(H, W, cell=1) -> Tuple[int, int]:
-    if not _is_int(H) or not _is_int(W) or H < 1 or W < 1:
+    if not _args.is_integer(H) or not _args.is_integer(W) or H < 1 or W < 1:
         raise ValueError(f"TemporalSpectrum: bad flow size {H!r} x {W!r}")
     ch, cw = -(-int(H) // cell), -(-int(W) // cell)
     if 2 * ch * cw >= 1 << 31:

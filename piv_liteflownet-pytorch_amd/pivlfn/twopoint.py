@@ -26,9 +26,7 @@ from typing import Dict, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib
-from .evaluate import _check_mask
-from .postpro import _check_flows
+from . import _args, _lib
 
 TERMS = ("n", "ua", "va", "ub", "vb", "uaua", "vava", "ubub", "vbvb", "uaub", "vavb", "uavb", "vaub", "lll", "ltt")    # acc[d, r, :, y]
 T = {name: i for i, name in enumerate(TERMS)}
@@ -40,10 +38,8 @@ WHICH = {"uu": ("uaub", "ua", "ub", "uaua", "ubub"), "vv": ("vavb", "va", "vb", 
 
 def check_params(max_sep, step) -> None:
     """The parameter checks of TwoPointStats (ValueError), usable before any tensor exists."""
-    if isinstance(max_sep, bool) or not isinstance(max_sep, int) or not 0 <= max_sep <= 255:
-        raise ValueError(f"TwoPointStats: max_sep={max_sep!r} must be an integer 0..255, the largest separation index")
-    if isinstance(step, bool) or not isinstance(step, int) or not 1 <= step <= 16:
-        raise ValueError(f"TwoPointStats: step={step!r} must be an integer 1..16, the pixels between two separations")
+    _args.check_int("TwoPointStats", "max_sep", max_sep, 0, 255, ", the largest separation index")
+    _args.check_int("TwoPointStats", "step", step, 1, 16, ", the pixels between two separations")
 
 
 def _axis(axis) -> int:
@@ -255,11 +251,11 @@ class TwoPointStats:
 
     def update(self, flows: torch.Tensor, mask: Optional[torch.Tensor] = None) -> None:
         """Add the frames of `flows` [B,2,H,W] (float32, on this device), in batch order; `mask` [B,H,W]: nonzero = leave the vector out."""
-        flows = _check_flows(flows, "TwoPointStats.update")
+        flows = _args.check_flows(flows, "TwoPointStats.update")
         if tuple(flows.shape[2:]) != (self.H, self.W) or flows.device != self.device:
             raise ValueError(f"TwoPointStats.update: flows {tuple(flows.shape)} on {flows.device}, accumulators for [{self.H},{self.W}] on "
                              f"{self.device}")
-        mask = _check_mask(mask, flows, "TwoPointStats.update")
+        mask = _args.check_mask(mask, "TwoPointStats.update", truth=flows)
         B = flows.size(0)
         if B == 0:
             return

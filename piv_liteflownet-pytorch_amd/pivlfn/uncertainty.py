@@ -27,10 +27,8 @@ from typing import Dict, List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib
-from .evaluate import _check_mask
-from .postpro import _check_flows
-from .quality import _check_images, default_min_count
+from . import _args, _lib
+from .quality import default_min_count
 
 FEW, FLAT, NO_PEAK, NO_VARIANCE, CENTRE_OUT = 1, 2, 4, 8, 16          # the bits of a flag byte (PIVLFN_UNCERTAINTY_*)
 UNUSABLE = FEW | FLAT | NO_PEAK | NO_VARIANCE                         # any of these: the vector has no uncertainty (NaN)
@@ -42,19 +40,12 @@ UNKNOWN = 1e9                                                         # |truth| 
 
 def check_params(radius, lag, floor, min_count) -> int:
     """The parameter checks of flow_uncertainty (ValueError), usable before any image exists; returns the min_count in effect."""
-    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= 15:
-        raise ValueError(f"flow_uncertainty: radius={radius!r} must be an integer 1..15 (a window of 3 x 3 to 31 x 31 pixels)")
-    if isinstance(lag, bool) or not isinstance(lag, int) or not 0 <= lag <= 4:
-        raise ValueError(f"flow_uncertainty: lag={lag!r} must be an integer 0..4 (the covariance of the contributions is summed over "
-                         "(2 lag + 1)^2 offsets)")
+    _args.check_int("flow_uncertainty", "radius", radius, 1, 15, " (a window of 3 x 3 to 31 x 31 pixels)")
+    _args.check_int("flow_uncertainty", "lag", lag, 0, 4, " (the covariance of the contributions is summed over (2 lag + 1)^2 offsets)")
     if min_count is None:
         min_count = default_min_count(radius)
-    if isinstance(min_count, bool) or not isinstance(min_count, int) or not 2 <= min_count <= (2 * radius + 1) ** 2:
-        raise ValueError(f"flow_uncertainty: min_count={min_count!r} must be an integer 2..{(2 * radius + 1) ** 2}, the pixels of the "
-                         "window")
-    floor = float(floor)
-    if not math.isfinite(floor) or floor < 0.0:
-        raise ValueError(f"flow_uncertainty: floor={floor!r} must be finite and not negative")
+    _args.check_int("flow_uncertainty", "min_count", min_count, 2, (2 * radius + 1) ** 2, ", the pixels of the window")
+    _args.check_not_negative("flow_uncertainty", "floor", floor)
     return min_count
 
 
@@ -112,25 +103,16 @@ def flow_uncertainty(img1: torch.Tensor, img2: torch.Tensor, flow: torch.Tensor,
     floor^2 per pixel; NO_PEAK -- zero shift is not a positive maximum; NO_VARIANCE -- the variance estimate is not positive (the
     estimate of a sum of covariances can be); CENTRE_OUT -- the pixel itself is masked or warps outside."""
     min_count = check_params(radius, lag, floor, min_count)
-    img1, img2 = _check_images(img1, img2, "flow_uncertainty")
-    if isinstance(flow, torch.Tensor) and flow.dtype == torch.float32 and (
-            flow.dim() != 4 or flow.size(1) != 2 or flow.device != img1.device or flow.size(0) != img1.size(0)
-            or tuple(flow.shape[2:]) != tuple(img1.shape[2:])):
-        raise ValueError(f"flow_uncertainty: flows {tuple(flow.shape)} on {flow.device} do not belong to images {tuple(img1.shape)} on "
-                         f"{img1.device}")
-    flow = _check_flows(flow, "flow_uncertainty")
-    mask = _check_mask(mask, flow, "flow_uncertainty")
+    img1, img2 = _args.check_images(img1, img2, "flow_uncertainty")
+    flow = _args.check_flows(flow, "flow_uncertainty", images=img1)
+    mask = _args.check_mask(mask, "flow_uncertainty", truth=flow)
     B, C, H, W = img1.shape
     u = torch.empty([B, 2, H, W], dtype=torch.float32, device=flow.device)
     flag = torch.empty([B, H, W], dtype=torch.uint8, device=flow.device)
     if B > 0:
-        with torch.cuda.device(flow.device):
-            lib = _lib.load()
-            ws = torch.empty(lib.pivlfn_flow_uncertainty_workspace_bytes(B, H, W, radius, lag), dtype=torch.uint8, device=flow.device)
-            _lib.check(lib.pivlfn_flow_uncertainty(img1.data_ptr(), img2.data_ptr(), C, flow.data_ptr(),
-                                                   mask.data_ptr() if mask is not None else None, u.data_ptr(), flag.data_ptr(),
-                                                   B, H, W, radius, lag, min_count, float(floor), ws.data_ptr(), ws.numel(),
-                                                   _lib.stream_ptr(flow.device)), "flow_uncertainty")
+        _args.call_with_workspace("flow_uncertainty", flow.device, (B, H, W, radius, lag), img1.data_ptr(), img2.data_ptr(), C,
+                                  flow.data_ptr(), _args.ptr(mask), u.data_ptr(), flag.data_ptr(), B, H, W, radius, lag, min_count,
+                                  float(floor))
     return FlowUncertainty(u, flag)
 
 

@@ -23,8 +23,8 @@ from typing import Dict, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib
-from .postpro import SUMS, _calib, _check_flows
+from . import _args, _lib
+from .postpro import SUMS
 
 MODES = {"flag": 0, "mask": 1, "replace": 2}         # PIVLFN_VALIDATE_FLAG, PIVLFN_VALIDATE_MASK, PIVLFN_VALIDATE_REPLACE
 OUTLIER, UNKNOWN, NOT_REPLACED = 1, 2, 4             # the bits of a flag byte
@@ -44,9 +44,9 @@ def check_params(radius, spacing, eps, thresh, mode) -> None:
     """The parameter checks of validate_flow (ValueError), usable before any flow exists."""
     if mode not in MODES:
         raise ValueError(f"validate_flow: unknown mode {mode!r} (one of {', '.join(MODES)})")
-    if isinstance(radius, bool) or not isinstance(radius, int) or radius not in (1, 2):
+    if not _args.is_int(radius, 1, 2):
         raise ValueError(f"validate_flow: radius={radius!r} must be 1 (3 x 3 neighbourhood) or 2 (5 x 5)")
-    if isinstance(spacing, bool) or not isinstance(spacing, int) or spacing < 1 or radius * spacing >= 1 << 15:
+    if not _args.is_int(spacing, 1) or radius * spacing >= 1 << 15:
         raise ValueError(f"validate_flow: spacing={spacing!r} must be an integer >= 1 with radius*spacing below 2^15")
     eps, thresh = float(eps), float(thresh)
     if not math.isfinite(eps) or eps < 0.0:
@@ -75,7 +75,7 @@ def validate_flow(flow: torch.Tensor, radius: int = 1, spacing: int = 1, eps: fl
     pivlfn.flo needs nothing for masked flows: 1e10 round-trips through a .flo like any float, and the reference's readers treat
     anything above 1e9 as unknown."""
     check_params(radius, spacing, eps, thresh, mode)
-    given, flow = flow, _check_flows(flow, "validate_flow")
+    given, flow = flow, _args.check_flows(flow, "validate_flow")
     B, _, H, W = flow.shape
     flag = torch.empty([B, H, W], dtype=torch.uint8, device=flow.device)
     out = given if mode == "flag" else torch.empty_like(flow)
@@ -121,7 +121,7 @@ class MaskedFlowStats:
     whole 3 x 3 stencil are 0.  update() enqueues one kernel on the current stream and never synchronises the host."""
 
     def __init__(self, H: int, W: int, calib=1.0, device=None):
-        self.H, self.W, self.calib = int(H), int(W), _calib(calib)
+        self.H, self.W, self.calib = int(H), int(W), _args.check_calib(calib)
         if self.H <= 0 or self.W <= 0:
             raise ValueError(f"MaskedFlowStats: bad size {H} x {W}")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -133,7 +133,7 @@ class MaskedFlowStats:
 
     def update(self, flow: torch.Tensor, flag: torch.Tensor) -> None:
         """Add the frames of `flow` [B,2,H,W] (float32, the flows validate_flow was given) under `flag` [B,H,W], in batch order."""
-        flow = _check_flows(flow, "MaskedFlowStats.update")
+        flow = _args.check_flows(flow, "MaskedFlowStats.update")
         flag = _check_flags(flag, flow, "MaskedFlowStats.update")
         if tuple(flow.shape[2:]) != (self.H, self.W) or flow.device != self.device:
             raise ValueError(f"MaskedFlowStats.update: flows {tuple(flow.shape)} on {flow.device}, accumulators [{self.H},{self.W}] on "

@@ -27,8 +27,8 @@ from typing import Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import _lib
-from .postpro import _check_flows, flow_fields
+from . import _args, _lib
+from .postpro import flow_fields
 
 WHEELS = {"interp": 0, "original": 1}          # PIVLFN_WHEEL_INTERP, PIVLFN_WHEEL_ORIGINAL
 ORDERS = {"rgb": 0, "bgr": 1}                  # PIVLFN_ORDER_RGB, PIVLFN_ORDER_BGR
@@ -67,23 +67,6 @@ def _lut_on(cmap, device) -> torch.Tensor:
     return cmap.to(device).contiguous()
 
 
-def _check_mask(mask, shape, device, what: str) -> Optional[torch.Tensor]:
-    """A uint8 or bool [B,H,W] mask on `device` (validate_flow's flag), or None."""
-    if mask is None:
-        return None
-    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
-        raise TypeError(f"{what}: expected a uint8 or bool mask [B,H,W], got "
-                        f"{mask.dtype if isinstance(mask, torch.Tensor) else type(mask).__name__}")
-    if mask.device != device or tuple(mask.shape) != tuple(shape):
-        raise ValueError(f"{what}: mask {tuple(mask.shape)} on {mask.device} does not belong to {tuple(shape)} on {device}")
-    mask = mask.detach().contiguous()
-    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
-
-
 def _maxmotion(maxmotion) -> float:
     m = float(maxmotion)
     if not math.isfinite(m) or m < 0.0:
@@ -94,13 +77,13 @@ def _maxmotion(maxmotion) -> float:
 def flow_maxrad(flow: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[B,2,H,W] float32 flows on the device -> float32 [B]: the largest vector length of each image over the vectors that are
     neither unknown nor masked (0 where none is left).  Enqueued on the current stream."""
-    flow = _check_flows(flow, "flow_maxrad")
+    flow = _args.check_flows(flow, "flow_maxrad")
     B, _, H, W = flow.shape
-    mask = _check_mask(mask, (B, H, W), flow.device, "flow_maxrad")
+    mask = _args.check_mask(mask, "flow_maxrad", shape=(B, H, W), device=flow.device)
     out = torch.empty([B], dtype=torch.float32, device=flow.device)
     if B > 0:
         with torch.cuda.device(flow.device):
-            _lib.check(_lib.load().pivlfn_flow_maxrad(flow.data_ptr(), _ptr(mask), out.data_ptr(), B, H, W, _lib.stream_ptr(flow.device)),
+            _lib.check(_lib.load().pivlfn_flow_maxrad(flow.data_ptr(), _args.ptr(mask), out.data_ptr(), B, H, W, _lib.stream_ptr(flow.device)),
                        "flow_maxrad")
     return out
 
@@ -118,9 +101,9 @@ def flow_to_color(flow: torch.Tensor, maxmotion=None, scope: str = "image", whee
         raise ValueError(f"flow_to_color: unknown wheel {wheel!r} (one of {', '.join(WHEELS)})")
     if order not in ORDERS:
         raise ValueError(f"flow_to_color: unknown order {order!r} (one of {', '.join(ORDERS)})")
-    flow = _check_flows(flow, "flow_to_color")
+    flow = _args.check_flows(flow, "flow_to_color")
     B, _, H, W = flow.shape
-    mask = _check_mask(mask, (B, H, W), flow.device, "flow_to_color")
+    mask = _args.check_mask(mask, "flow_to_color", shape=(B, H, W), device=flow.device)
     out = torch.empty([B, H, W, 3], dtype=torch.uint8, device=flow.device)
     if B == 0:
         return out
@@ -131,7 +114,7 @@ def flow_to_color(flow: torch.Tensor, maxmotion=None, scope: str = "image", whee
         if scope == "batch":
             norm = norm.max().expand(B).contiguous()
     with torch.cuda.device(flow.device):
-        _lib.check(_lib.load().pivlfn_flow_to_color(flow.data_ptr(), norm.data_ptr(), _ptr(mask), out.data_ptr(), B, H, W, WHEELS[wheel],
+        _lib.check(_lib.load().pivlfn_flow_to_color(flow.data_ptr(), norm.data_ptr(), _args.ptr(mask), out.data_ptr(), B, H, W, WHEELS[wheel],
                                                     ORDERS[order], _lib.stream_ptr(flow.device)), "flow_to_color")
     return out
 
@@ -179,11 +162,11 @@ def field_absmax(field: torch.Tensor, mask: Optional[torch.Tensor] = None) -> to
     image (0 where none is left).  Enqueued on the current stream."""
     field = _check_field(field, "field_absmax")
     B, H, W = field.shape
-    mask = _check_mask(mask, (B, H, W), field.device, "field_absmax")
+    mask = _args.check_mask(mask, "field_absmax", shape=(B, H, W), device=field.device)
     out = torch.empty([B], dtype=torch.float64, device=field.device)
     if B > 0:
         with torch.cuda.device(field.device):
-            _lib.check(_lib.load().pivlfn_field_absmax(field.data_ptr(), int(field.dtype == torch.float64), _ptr(mask), out.data_ptr(),
+            _lib.check(_lib.load().pivlfn_field_absmax(field.data_ptr(), int(field.dtype == torch.float64), _args.ptr(mask), out.data_ptr(),
                                                        B, H, W, _lib.stream_ptr(field.device)), "field_absmax")
     return out
 
@@ -206,7 +189,7 @@ def scalar_to_color(field: torch.Tensor, vmin=None, vmax=None, cmap: Union[str, 
     takes its own largest magnitude (field_absmax; that reads B numbers back, the only host synchronisation here; 0 stands for 1)."""
     field = _check_field(field, "scalar_to_color")
     B, H, W = field.shape
-    mask = _check_mask(mask, (B, H, W), field.device, "scalar_to_color")
+    mask = _args.check_mask(mask, "scalar_to_color", shape=(B, H, W), device=field.device)
     lut = _lut_on(cmap, field.device)
     bad_rgb = _bad_rgb(bad)
     if symmetric:
@@ -230,11 +213,11 @@ def scalar_to_color(field: torch.Tensor, vmin=None, vmax=None, cmap: Union[str, 
     with torch.cuda.device(field.device):
         st = _lib.stream_ptr(field.device)
         if all(r == ranges[0] for r in ranges):
-            _lib.check(lib.pivlfn_scalar_to_color(field.data_ptr(), is_f64, _ptr(mask), lut.data_ptr(), out.data_ptr(), B, H, W,
+            _lib.check(lib.pivlfn_scalar_to_color(field.data_ptr(), is_f64, _args.ptr(mask), lut.data_ptr(), out.data_ptr(), B, H, W,
                                                   ranges[0][0], ranges[0][1], bad_rgb, st), "scalar_to_color")
         else:
             for b, (lo, hi) in enumerate(ranges):
-                _lib.check(lib.pivlfn_scalar_to_color(field[b].data_ptr(), is_f64, _ptr(mask[b]) if mask is not None else None,
+                _lib.check(lib.pivlfn_scalar_to_color(field[b].data_ptr(), is_f64, _args.ptr(mask[b]) if mask is not None else None,
                                                       lut.data_ptr(), out[b].data_ptr(), 1, H, W, lo, hi, bad_rgb, st), "scalar_to_color")
     return out
 
@@ -250,17 +233,17 @@ def vorticity_image(flow: torch.Tensor, calib=1.0, kind: str = "calc_vorticity",
 def decimate_flow(flow: torch.Tensor, cell: int, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """[B,2,H,W] float32 flows on the device -> (float32 [B,2,ceil(H/cell),ceil(W/cell)] cell means, int32 [B,.,.] counts of the
     vectors averaged).  Unknown and masked vectors are left out; a cell with none is 1e10 in both components."""
-    if isinstance(cell, bool) or not isinstance(cell, int) or not 1 <= cell <= 32768:
+    if not _args.is_int(cell, 1, 32768):
         raise ValueError(f"decimate_flow: cell={cell!r} must be an integer from 1 to 32768")
-    flow = _check_flows(flow, "decimate_flow")
+    flow = _args.check_flows(flow, "decimate_flow")
     B, _, H, W = flow.shape
-    mask = _check_mask(mask, (B, H, W), flow.device, "decimate_flow")
+    mask = _args.check_mask(mask, "decimate_flow", shape=(B, H, W), device=flow.device)
     ch, cw = -(-H // cell), -(-W // cell)
     mean = torch.empty([B, 2, ch, cw], dtype=torch.float32, device=flow.device)
     count = torch.empty([B, ch, cw], dtype=torch.int32, device=flow.device)
     if B > 0:
         with torch.cuda.device(flow.device):
-            _lib.check(_lib.load().pivlfn_flow_decimate(flow.data_ptr(), _ptr(mask), mean.data_ptr(), count.data_ptr(), B, H, W, cell,
+            _lib.check(_lib.load().pivlfn_flow_decimate(flow.data_ptr(), _args.ptr(mask), mean.data_ptr(), count.data_ptr(), B, H, W, cell,
                                                         _lib.stream_ptr(flow.device)), "decimate_flow")
     return mean, count
 
@@ -330,7 +313,7 @@ def draw_quiver(mean: np.ndarray, count: np.ndarray, cell: int, H: int, W: int, 
 def color_wheel_image(size: int = 151, wheel: str = "interp", order: str = "rgb", device=None) -> torch.Tensor:
     """The legend, uint8 [size,size,3] on the device: the vectors of the unit disc (x to the right, y down, as the flows of an image)
     through the kernel that colours the flows, normalised by 1; white outside the disc."""
-    if isinstance(size, bool) or not isinstance(size, int) or size < 1:
+    if not _args.is_int(size, 1):
         raise ValueError(f"color_wheel_image: size={size!r} must be a positive integer")
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if device.type != "cuda":

@@ -23,9 +23,7 @@ from typing import Dict, List, NamedTuple, Optional
 import torch
 import torch.nn.functional as F
 
-from . import _lib
-from .evaluate import _check_mask
-from .postpro import _check_flows
+from . import _args
 
 FEW, CENTRE_OUT = 1, 2                # the bits of a flag byte (PIVLFN_VORTEX_*)
 CORE = 2.0 / math.pi                  # |Gamma2| above it: rotation dominates shear
@@ -39,14 +37,11 @@ def default_min_count(radius: int) -> int:
 
 def check_params(radius, spacing, min_count) -> int:
     """The parameter checks of vortex_gamma (ValueError), usable before any tensor exists; returns the min_count in effect."""
-    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= 15:
-        raise ValueError(f"vortex_gamma: radius={radius!r} must be an integer 1..15 (3 x 3 to 31 x 31 vectors)")
-    if isinstance(spacing, bool) or not isinstance(spacing, int) or not 1 <= spacing <= 16:
-        raise ValueError(f"vortex_gamma: spacing={spacing!r} must be an integer 1..16, the distance between neighbours in pixels")
+    _args.check_int("vortex_gamma", "radius", radius, 1, 15, " (3 x 3 to 31 x 31 vectors)")
+    _args.check_int("vortex_gamma", "spacing", spacing, 1, 16, ", the distance between neighbours in pixels")
     if min_count is None:
         min_count = default_min_count(radius)
-    if isinstance(min_count, bool) or not isinstance(min_count, int) or not 1 <= min_count <= (2 * radius + 1) ** 2 - 1:
-        raise ValueError(f"vortex_gamma: min_count={min_count!r} must be an integer 1..{(2 * radius + 1) ** 2 - 1}, the neighbours of a vector")
+    _args.check_int("vortex_gamma", "min_count", min_count, 1, (2 * radius + 1) ** 2 - 1, ", the neighbours of a vector")
     return min_count
 
 
@@ -115,7 +110,7 @@ class VortexField(NamedTuple):
         if of not in ("gamma1", "gamma2"):
             raise ValueError(f"peaks: of={of!r} must be 'gamma1' or 'gamma2'")
         distance = self.radius * self.spacing if distance is None else distance
-        if isinstance(distance, bool) or not isinstance(distance, int) or distance < 1:
+        if not _args.is_int(distance, 1):
             raise ValueError(f"peaks: distance={distance!r} must be a positive integer (pixels)")
         field = self.gamma1 if of == "gamma1" else self.gamma2
         B, H, W = field.shape
@@ -148,16 +143,12 @@ def vortex_gamma(flow: torch.Tensor, radius: int = 4, spacing: int = 1, mask: Op
     fewer than `min_count` neighbours left (default: half of them), both fields are NaN there; CENTRE_OUT -- the vector itself is
     masked or invalid (the values are still formed, from its neighbours)."""
     min_count = check_params(radius, spacing, min_count)
-    flow = _check_flows(flow, "vortex_gamma")
-    mask = _check_mask(mask, flow, "vortex_gamma")
+    flow = _args.check_flows(flow, "vortex_gamma")
+    mask = _args.check_mask(mask, "vortex_gamma", truth=flow)
     B, _, H, W = flow.shape
     gamma = torch.empty([B, 2, H, W], dtype=torch.float32, device=flow.device)
     flag = torch.empty([B, H, W], dtype=torch.uint8, device=flow.device)
     if B > 0:
-        with torch.cuda.device(flow.device):
-            lib = _lib.load()
-            ws = torch.empty(lib.pivlfn_vortex_gamma_workspace_bytes(B, H, W, radius, spacing), dtype=torch.uint8, device=flow.device)
-            _lib.check(lib.pivlfn_vortex_gamma(flow.data_ptr(), mask.data_ptr() if mask is not None else None, gamma.data_ptr(),
-                                               flag.data_ptr(), B, H, W, radius, spacing, min_count, ws.data_ptr(), ws.numel(),
-                                               _lib.stream_ptr(flow.device)), "vortex_gamma")
+        _args.call_with_workspace("vortex_gamma", flow.device, (B, H, W, radius, spacing), flow.data_ptr(), _args.ptr(mask), gamma.data_ptr(),
+                                  flag.data_ptr(), B, H, W, radius, spacing, min_count)
     return VortexField(gamma[:, 0], gamma[:, 1], flag, radius, spacing)

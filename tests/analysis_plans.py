@@ -20,11 +20,15 @@ line here, and a case where its plan has a step.
                                   TWOPOINT_CASES, test_gpu_twopoint.py::test_bits_where_the_plan_changes.
   pivlfn_spectrum_accumulate      bounded domain (L <= 1024, K <= 513): ceil(L / 128) staged chunks, ceil((K // 8) / 8) rounds, K % 8
                                   singles.  SPECTRUM_CASES (the corner L = 1024, K = 513) in test_gpu_spectrum.py::test_bits_of_the_restatement.
-  pivlfn_vortex_gamma             vortex_stage_kernel: grid min(ceil(HW / 256), max(16384 / B, 64)) per frame, a grid-stride loop above;
-                                  vortex_window_kernel: flat.  VORTEX_CASES, test_gpu_vortex.py::test_bits_where_the_stage_grid_is_capped.
-  pivlfn_match_quality            quality_warp_kernel: the same cap as the vortex stage; quality_window_kernel: flat.  QUALITY_CASES,
+  pivlfn_vortex_gamma             vortex_stage_kernel: frame_grid of csrc/launch_checks.h, min(ceil(HW / 256), max(16384 / B, 64)) blocks per
+                                  frame and a grid-stride loop above; vortex_window_kernel: flat.  VORTEX_CASES,
+                                  test_gpu_vortex.py::test_bits_where_the_stage_grid_is_capped.
+  pivlfn_match_quality            quality_warp_kernel: frame_grid; quality_window_kernel: flat.  QUALITY_CASES,
                                   test_gpu_quality.py::test_bits_where_the_warp_grid_is_capped.
-  pivlfn_stereo_2d3c              the same cap.  STEREO_CASES in test_gpu_stereo.py::test_kernel_matches_restatement_random (its
+  pivlfn_flow_uncertainty         quality_warp_kernel and unc_fields_kernel: frame_grid; the three tiled kernels: flat.  UNCERTAINTY_CASES,
+                                  test_gpu_uncertainty.py::test_bits_where_the_frame_grid_is_capped.
+  pivlfn_uncertainty_accumulate   none: one thread per pixel, a flat grid, the frames a loop of the kernel.
+  pivlfn_stereo_2d3c              frame_grid.  STEREO_CASES in test_gpu_stereo.py::test_kernel_matches_restatement_random (its
                                   1024 x 1024 case has 4096 blocks, below the cap of 16384).
   pivlfn_field_absmax             grid min(ceil(HW / 256), 256) per image.  VIZ_ABSMAX_CASES, test_gpu_viz.py::test_field_absmax_where_the_grid_is_capped.
   pivlfn_flow_maxrad              grid min(ceil(ceil(HW / 4) / 256), 256) per image.  VIZ_MAXRAD_CASES,
@@ -42,12 +46,19 @@ line here, and a case where its plan has a step.
                                   test_gpu_pod.py::test_gram_of_many_snapshots_adds_its_slabs_itself.
   pivlfn_snapshot_project         none in P (flat); K picks the kernel: K <= 4, <= 16, <= 64.  test_gpu_pod.py::
                                   test_project_equals_the_sequential_loop has K = 1, 3 | 5, 16 | 17, 64 (PROJECT_CASES adds 5 and 16).
-  pivlfn_flow_fields, pivlfn_flow_stats_accumulate(_masked), pivlfn_flow_validate, pivlfn_frames_preprocess (scale),
-  pivlfn_error_stats_accumulate   the cap max(16384 / B, 64) (16384 for the accumulators) of blocks of 256 pixels per frame.  Their largest
-                                  cases are 1024 x 1024 at B <= 5: 4096 blocks (1024 for the vectorised pre-processing), which is BELOW the cap of
-                                  16384 / 3 = 5461, so their grid-stride loops run once in every test so far.  Not part of this list yet.
-  pivlfn_frames_background_min, pivlfn_frames_preprocess (min-max), pivlfn_flow_errors, pivlfn_level_errors   tiles, flat grids; the second
-                                  pass of pivlfn_flow_errors from 32 x 32 tiles: test_gpu_evaluate.py, the 1024 x 1024 cases.
+  pivlfn_flow_fields              frame_grid.  FIELDS_CASES, test_gpu_postpro.py::test_fields_where_the_frame_grid_is_capped.
+  pivlfn_flow_validate            frame_grid, both kernels.  VALIDATE_CASES, test_gpu_validate.py::test_bits_where_the_frame_grid_is_capped.
+  pivlfn_frames_preprocess        k = 0: frame_grid over the pixels of a frame, or over groups of four where H*W is a multiple of 4 and
+                                  the pointers are aligned.  PREPROC_CASES, test_gpu_preproc.py::test_scale_where_the_frame_grid_is_capped.
+                                  Min-max: tiles, a flat grid.
+  pivlfn_flow_stats_accumulate(_masked), pivlfn_error_stats_accumulate   frame_grid with frames = 1 (the frames are a loop of the kernel): capped
+                                  at 16384 blocks.  ACCUMULATOR_CASES, test_gpu_postpro.py::test_stats_where_the_grid_is_capped,
+                                  test_gpu_validate.py::test_masked_stats_where_the_grid_is_capped,
+                                  test_gpu_evaluate.py::test_error_stats_where_the_grid_is_capped.
+  pivlfn_frames_background_min    frame_grid with frames = 1 over the bytes of a frame (or groups of four); 1024 x 1024 x 3 bytes are
+                                  3072 blocks of four-byte groups, below the cap.
+  pivlfn_flow_errors, pivlfn_level_errors   tiles, flat grids; the second pass of pivlfn_flow_errors from 32 x 32 tiles:
+                                  test_gpu_evaluate.py, the 1024 x 1024 cases.
 """
 import os
 import re
@@ -57,6 +68,7 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 # the constexpr values the formulas below depend on, per source file; tests/test_analysis_plans.py reads them back out of the text
 CONSTANTS = {
+    "launch_checks.h": {"FRAME_GRID_THREADS": 256, "FRAME_GRID_BLOCKS": 16384, "FRAME_GRID_MIN_BLOCKS": 64},
     "pressure.hip": {"PR_THREADS": 256, "PR_OWN": 4, "PR_CHUNK": 1024, "PR_MAX_PART": 2048},
     "calibrate.hip": {"TP_BLOCK": 256},
     "twopoint.hip": {"TP_WAVES": 4, "TP_CHUNK": 256, "TP_SLOT": 16},
@@ -64,6 +76,8 @@ CONSTANTS = {
     "particles.hip": {"REN_TILE": 16, "REN_CAP": 2048},
     "spectrum.hip": {"SP_TC": 128, "SP_KG": 8, "SP_WAVES": 8, "SP_TILE": 64},
 }
+FRAME_GRID_THREADS, FRAME_GRID_BLOCKS, FRAME_GRID_MIN_BLOCKS = (CONSTANTS["launch_checks.h"][k] for k in
+                                                                 ("FRAME_GRID_THREADS", "FRAME_GRID_BLOCKS", "FRAME_GRID_MIN_BLOCKS"))
 PR_THREADS, PR_OWN, PR_CHUNK, PR_MAX_PART = (CONSTANTS["pressure.hip"][k] for k in ("PR_THREADS", "PR_OWN", "PR_CHUNK", "PR_MAX_PART"))
 TP_BLOCK = CONSTANTS["calibrate.hip"]["TP_BLOCK"]
 TP_WAVES, TP_CHUNK, TP_SLOT = (CONSTANTS["twopoint.hip"][k] for k in ("TP_WAVES", "TP_CHUNK", "TP_SLOT"))
@@ -134,10 +148,11 @@ def twopoint(H, W, R):
     return {"levels": levels, "chunks": chunks, "z": z, "slots": slots, "lds": TP_WAVES * slots * TP_SLOT * 8}
 
 
-def capped_frame_grid(B, H, W):
-    """vortex_stage_kernel, quality_warp_kernel and stereo_2d3c_kernel: blocks of 256 pixels per frame, capped at max(16384 / B, 64)."""
-    g = cdiv(H * W, 256)
-    cap = max(16384 // B, 64)
+def capped_frame_grid(items, frames):
+    """frame_grid of csrc/launch_checks.h: blocks of 256 items per frame, capped at max(16384 / frames, 64); frames = 1 for a launch that
+    is not per frame."""
+    g = cdiv(items, FRAME_GRID_THREADS)
+    cap = max(FRAME_GRID_BLOCKS // frames, FRAME_GRID_MIN_BLOCKS)
     return {"blocks": g, "cap": cap, "grid": min(g, cap), "visits": cdiv(g, min(g, cap))}
 
 
@@ -211,19 +226,41 @@ TWOPOINT_CASES = [          # (H, W, R, step), B = 2
 
 _over_the_cap = lambda p: p["blocks"] > p["cap"] and p["grid"] == p["cap"] and p["visits"] == 2      # noqa: E731
 VORTEX_CASES = [            # (B, H, W, radius, spacing)
-    _case((260, 130, 128, 2, 1), "65 blocks a frame, capped at 64", lambda B, H, W, r, s: capped_frame_grid(B, H, W),
+    _case((260, 130, 128, 2, 1), "65 blocks a frame, capped at 64", lambda B, H, W, r, s: capped_frame_grid(H * W, B),
           lambda p: _over_the_cap(p) and p["cap"] == 64 and p["blocks"] == 65),
-    _case((1, 2049, 2048, 1, 1), "16392 blocks, capped at 16384", lambda B, H, W, r, s: capped_frame_grid(B, H, W),
+    _case((1, 2049, 2048, 1, 1), "16392 blocks, capped at 16384", lambda B, H, W, r, s: capped_frame_grid(H * W, B),
           lambda p: _over_the_cap(p) and p["cap"] == 16384),
 ]
 QUALITY_CASES = [           # (B, H, W, radius)
-    _case((260, 130, 128, 1), "65 blocks a frame, capped at 64", lambda B, H, W, r: capped_frame_grid(B, H, W),
+    _case((260, 130, 128, 1), "65 blocks a frame, capped at 64", lambda B, H, W, r: capped_frame_grid(H * W, B),
           lambda p: _over_the_cap(p) and p["cap"] == 64),
 ]
 STEREO_CASES = [            # (B, h, w)
-    _case((260, 130, 128), "65 blocks a pair, capped at 64", capped_frame_grid, lambda p: _over_the_cap(p) and p["cap"] == 64),
-    _case((1, 2049, 2048), "16392 blocks, capped at 16384", capped_frame_grid, lambda p: _over_the_cap(p) and p["cap"] == 16384),
+    _case((260, 130, 128), "65 blocks a pair, capped at 64", lambda B, h, w: capped_frame_grid(h * w, B), lambda p: _over_the_cap(p) and p["cap"] == 64),
+    _case((1, 2049, 2048), "16392 blocks, capped at 16384", lambda B, h, w: capped_frame_grid(h * w, B), lambda p: _over_the_cap(p) and p["cap"] == 16384),
 ]
+_frames_of = lambda B, H, W: capped_frame_grid(H * W, B)      # noqa: E731
+FIELDS_CASES = [            # (B, H, W); compared with the same frames in calls of FRAMES_PER_UNCAPPED_CALL, which are not capped
+    _case((260, 130, 128), "65 blocks a frame, capped at 64", _frames_of, lambda p: _over_the_cap(p) and p["cap"] == 64 and p["blocks"] == 65),
+]
+VALIDATE_CASES = [          # (B, H, W)
+    _case((260, 130, 128), "65 blocks a frame, capped at 64", _frames_of, lambda p: _over_the_cap(p) and p["cap"] == 64 and p["blocks"] == 65),
+]
+UNCERTAINTY_CASES = [       # (B, H, W, radius, lag)
+    _case((260, 130, 128, 1, 1), "65 blocks a frame, capped at 64", lambda B, H, W, r, lag: capped_frame_grid(H * W, B),
+          lambda p: _over_the_cap(p) and p["cap"] == 64 and p["blocks"] == 65),
+]
+PREPROC_CASES = [           # (n, H, W), k = 0
+    _case((260, 258, 256), "16512 four-pixel items: 65 blocks a frame, capped at 64", lambda n, H, W: capped_frame_grid(H * W // 4, n),
+          lambda p: _over_the_cap(p) and p["cap"] == 64 and p["blocks"] == 65 and 258 * 256 % 4 == 0),
+    _case((260, 129, 129), "16641 pixels, odd: the byte path, 66 blocks a frame, capped at 64", lambda n, H, W: capped_frame_grid(H * W, n),
+          lambda p: _over_the_cap(p) and p["cap"] == 64 and p["blocks"] == 66 and 129 * 129 % 4 != 0),
+]
+ACCUMULATOR_CASES = [       # (B, H, W): flow_stats_accumulate, _masked and error_stats_accumulate
+    _case((2, 2049, 2048), "16392 blocks, capped at 16384", lambda B, H, W: capped_frame_grid(H * W, 1),
+          lambda p: _over_the_cap(p) and p["cap"] == 16384 and p["blocks"] == 16392),
+]
+FRAMES_PER_UNCAPPED_CALL = 52     # 52 frames are capped at 315 blocks a frame: the five calls a batch of 260 is compared with are not capped
 
 VIZ_ABSMAX_CASES = [        # (B, H, W)
     _case((1, 257, 256), "257 blocks, capped at 256: one block comes round again", lambda B, H, W: viz_absmax(H, W),
@@ -259,7 +296,9 @@ PROJECT_CASES = [(9, 5, 70), (9, 16, 300)]              # (n, K, P): the first a
 
 ALL_CASES = {"pressure": PRESSURE_CASES, "target_points": TARGET_POINTS_CASES, "twopoint": TWOPOINT_CASES, "vortex": VORTEX_CASES,
              "quality": QUALITY_CASES, "stereo": STEREO_CASES, "field_absmax": VIZ_ABSMAX_CASES, "flow_maxrad": VIZ_MAXRAD_CASES,
-             "viz_color": VIZ_COLOR_CASES, "particles": PARTICLES_CASES, "spectrum": SPECTRUM_CASES}
+             "viz_color": VIZ_COLOR_CASES, "particles": PARTICLES_CASES, "spectrum": SPECTRUM_CASES, "flow_fields": FIELDS_CASES,
+             "flow_validate": VALIDATE_CASES, "flow_uncertainty": UNCERTAINTY_CASES, "frames_preprocess": PREPROC_CASES,
+             "accumulators": ACCUMULATOR_CASES}
 
 
 def shapes(cases):

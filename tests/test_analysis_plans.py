@@ -29,9 +29,19 @@ def test_the_formulas_are_the_sources():
         "twopoint.hip": ["p.chunks = (1 << p.levels) > TP_CHUNK ? (1 << p.levels) / TP_CHUNK : 1",
                          "groups = cdiv(max_sep + 1, TP_WAVES), want = cdiv(4096, H)", "z = want < groups ? want : groups",
                          "p.slots = cdiv(max_sep + 1, TP_WAVES * z)", "lds = (size_t)TP_WAVES * p.slots * TP_SLOT * sizeof(double)"],
-        "vortex.hip": ["g = ((size_t)H * W + 255) / 256, cap = 16384 / (size_t)B > 64 ? 16384 / (size_t)B : 64"],
-        "quality.hip": ["g = ((size_t)H * W + 255) / 256, cap = 16384 / (size_t)B > 64 ? 16384 / (size_t)B : 64"],
-        "stereo.hip": ["cap = 16384 / (size_t)B > 64 ? 16384 / (size_t)B : 64"],
+        # the frame-grid rule stands once, in the header; each of its nine call sites calls it (no private copy can come back unnoticed)
+        "launch_checks.h": ["g = (items + FRAME_GRID_THREADS - 1) / FRAME_GRID_THREADS",
+                            "cap = FRAME_GRID_BLOCKS / (size_t)frames > FRAME_GRID_MIN_BLOCKS ? FRAME_GRID_BLOCKS / (size_t)frames : FRAME_GRID_MIN_BLOCKS",
+                            "return (unsigned)(g > cap ? cap : g)"],
+        "postpro.hip": ["dim3 grid(frame_grid((size_t)H * W, B), (unsigned)B)", "flow_stats_kernel, dim3(frame_grid((size_t)H * W, 1))",
+                        "flow_stats_masked_kernel, dim3(frame_grid((size_t)H * W, 1))"],
+        "validate.hip": ["dim3 grid(frame_grid((size_t)H * W, B), (unsigned)B)"],
+        "quality.hip": ["dim3 wgrid(frame_grid((size_t)H * W, B), (unsigned)B)"],
+        "vortex.hip": ["vortex_stage_kernel, dim3(frame_grid((size_t)H * W, B), (unsigned)B)"],
+        "stereo.hip": ["stereo_2d3c_kernel, dim3(frame_grid((size_t)H * W, B), (unsigned)B)"],
+        "uncertainty.hip": ["unc_fields_kernel, dim3(frame_grid((size_t)H * W, B), (unsigned)B)"],
+        "preproc.hip": ["dim3 grid(frame_grid(vec ? HW / 4 : HW, n), (unsigned)n)", "blocks = frame_grid(vec ? bytes / 4 : bytes, 1)"],
+        "evaluate.hip": ["error_stats_kernel, dim3(frame_grid((size_t)H * W, 1))"],
         "viz.hip": ["g = (items + VZ_THREADS - 1) / VZ_THREADS", "g > VZ_MAX_BLOCKS ? VZ_MAX_BLOCKS : (g ? g : 1)", "gx = viz_blocks((HW + 3) / 4)",
                     "gx = viz_blocks(HW)", "gx > 256 ? 256 : gx", "viz_blocks((npix + 3) / 4)", "viz_blocks(ncells)"],
         "particles.hip": ["tiles = (size_t)B * cdiv(H, REN_TILE) * cdiv(W, REN_TILE)", "tb = (unsigned)((tiles + 255) / 256)"],
@@ -42,6 +52,9 @@ def test_the_formulas_are_the_sources():
         text = squeeze(open(os.path.join(ap.CSRC, name)).read())
         for line in lines:
             assert squeeze(line) in text, f"csrc/{name} no longer holds `{line}`: restate the plan in tests/analysis_plans.py and revisit its cases"
+    for name in sorted(os.listdir(ap.CSRC)):
+        if name.endswith(".hip"):
+            assert "16384/(size_t)" not in squeeze(open(os.path.join(ap.CSRC, name)).read()), f"csrc/{name} has a frame-grid cap of its own"
 
 
 @pytest.mark.parametrize("op,case", [(op, c) for op, cases in ap.ALL_CASES.items() for c in cases], ids=lambda v: v if isinstance(v, str) else str(v.shape))
@@ -58,8 +71,10 @@ def test_the_smaller_neighbour_of_a_case_stays_below_its_branch():
     assert ap.tp_scan(256, 256)["per"] == 1 and ap.tp_scan(192, 320) == {"nblk": 240, "per": 1, "short": [], "empty": list(range(240, 256))}
     assert ap.twopoint(65, 300, 255)["slots"] == 1 and ap.twopoint(70, 131, 16)["slots"] == 1 and ap.twopoint(20, 300, 255)["chunks"] == 2
     assert ap.twopoint(5, 512, 8)["chunks"] == 2 and ap.twopoint(1024, 1024, 64) == {"levels": 10, "chunks": 4, "z": 4, "slots": 5, "lds": 2560}
-    assert ap.capped_frame_grid(256, 128, 128)["visits"] == 1 and ap.capped_frame_grid(1, 2048, 2048)["visits"] == 1
-    assert ap.capped_frame_grid(3, 1024, 1024)["visits"] == 1            # the largest case of the older analysis ops: below the cap
+    assert ap.capped_frame_grid(128 * 128, 256)["visits"] == 1 and ap.capped_frame_grid(2048 * 2048, 1)["visits"] == 1
+    assert ap.capped_frame_grid(1024 * 1024, 3)["visits"] == 1           # the largest case of the older analysis ops: below the cap
+    assert ap.capped_frame_grid(130 * 128, 52)["visits"] == 1            # the five calls of 52 frames the capped cases are compared with
+    assert ap.capped_frame_grid(256 * 256 // 4, 260)["visits"] == 1 and ap.capped_frame_grid(128 * 128, 260)["visits"] == 1
     assert ap.viz_absmax(256, 256)["blocks"] == 256 and ap.viz_maxrad(512, 512)["blocks"] == 256
     assert ap.viz_color(4, 1024, 1024)["blocks"] == ap.VZ_MAX_BLOCKS and ap.viz_color(1, 67, 131)["grid"] == 9
     assert ap.particles_tiles(1, 37, 53)["tiles"] == 12 and ap.particles_tiles(1, 16, 1024)["waves"] == 1
@@ -87,6 +102,8 @@ def test_the_table_names_every_analysis_entry_point():
     first, last = names.index("pivlfn_stereo_2d3c"), names.index("pivlfn_create")
     analysis = [n for n in names[first:last] if not n.endswith("_workspace_bytes") and not n.endswith("_workspace_offset")]
     assert len(analysis) >= 33 and "pivlfn_dewarp_frames" in analysis and "pivlfn_pressure_cg" in analysis
+    analysis += ["pivlfn_flow_uncertainty", "pivlfn_uncertainty_accumulate"]          # declared at the end of the header
+    assert set(analysis[-2:]) <= set(names)
     doc = ap.__doc__
     expand = {"pivlfn_pressure_setup / _cg / _read": ["pivlfn_pressure_setup", "pivlfn_pressure_cg", "pivlfn_pressure_read"],
               "pivlfn_flowmap_advect / _seed / _ftle": ["pivlfn_flowmap_advect", "pivlfn_flowmap_seed", "pivlfn_flowmap_ftle"],

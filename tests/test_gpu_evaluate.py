@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_plans as ap
 import evaluate_restatement as er
 import pivlfn
 from guarded import KINDS, check_guards, guarded, poison, same_bits
@@ -186,6 +187,15 @@ def test_megapixel_error_stats(dev, megapixel):
             st.update(est[k:k + c], _t(truth[k:k + c], dev), _t(mask[k:k + c], dev))
             k += c
         assert st.count == 3 and er.same_bits(st.acc.cpu().numpy(), want), splits
+
+
+@pytest.mark.parametrize("B,H,W", ap.shapes(ap.ACCUMULATOR_CASES))
+def test_error_stats_where_the_grid_is_capped(dev, B, H, W):
+    """More blocks than the flat cap of the accumulator's launch, with unknown truth and a mask: the restatement's sums, bit for bit."""
+    flow, truth, mask = _case(np.random.default_rng(H + W), B, H, W, 0)
+    st = E.ErrorStats(H, W, dev)
+    st.update(_t(flow, dev), _t(truth, dev), _t(mask, dev))
+    assert st.count == B and er.same_bits(st.acc.cpu().numpy(), er.accumulate_errors(np.zeros((6, H, W)), flow, truth, mask))
 
 
 MODELS = [("piv", 1), ("hui", 1), ("hui", 2)]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_plans as ap
 import pivlfn
 from pivlfn import postpro, synth
 from pivlfn.flo import read_flow
@@ -99,6 +100,28 @@ def test_guarded_buffers(dev, H, W):
     check_guards(fl, "stats flow")
     check_guards(acc, "stats acc")
     assert same_bits(acc.cpu().numpy(), accumulate(np.zeros((7, H, W)), src.cpu().numpy(), 1.0))
+
+
+@pytest.mark.parametrize("B,H,W", ap.shapes(ap.FIELDS_CASES))
+def test_fields_where_the_frame_grid_is_capped(dev, B, H, W):
+    """More blocks a frame than the launch's cap, so the kernel's grid-stride loop comes round: the bits of the same frames in calls
+    that are not capped."""
+    gen = torch.Generator(device=dev).manual_seed(B + H)
+    flows = torch.randn([B, 2, H, W], generator=gen, device=dev) * 6
+    step = ap.FRAMES_PER_UNCAPPED_CALL
+    for kind in KINDS:
+        whole = postpro.flow_fields(flows, 0.37, kind)
+        parts = torch.cat([postpro.flow_fields(flows[k:k + step], 0.37, kind) for k in range(0, B, step)])
+        assert torch.equal(whole, parts), kind
+
+
+@pytest.mark.parametrize("B,H,W", ap.shapes(ap.ACCUMULATOR_CASES))
+def test_stats_where_the_grid_is_capped(dev, B, H, W):
+    """More blocks than the flat cap of the accumulator's launch: the sequential numpy loop, bit for bit."""
+    host = np.random.default_rng(H + W).normal(0, 5, (B, 2, H, W)).astype(np.float32)
+    st = postpro.FlowStats(H, W, 0.37, dev)
+    st.update(torch.from_numpy(host).to(dev))
+    assert same_bits(st.acc.cpu().numpy(), accumulate(np.zeros((7, H, W)), host, 0.37))
 
 
 def _lib_fields(flow, out, kind):

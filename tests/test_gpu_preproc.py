@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_plans as ap
 import pivlfn
 import preproc_restatement as pr
 from guarded import check_guards, guarded, holds
@@ -184,6 +185,22 @@ def test_batch_invariance_and_python_entry(dev):
         P.preprocess_frames(t[..., :2])
     with pytest.raises(ValueError):
         P.preprocess_frames(t[0])
+
+
+@pytest.mark.parametrize("n,H,W", ap.shapes(ap.PREPROC_CASES))
+def test_scale_where_the_frame_grid_is_capped(dev, n, H, W):
+    """minmax = 0 with more blocks a frame than the launch's cap, on the four-pixel path (H*W a multiple of 4) and the byte path: the
+    kernel's grid-stride loop comes round, and the frames equal the same frames in calls that are not capped, with and without a
+    background."""
+    rng = np.random.default_rng(H)
+    t = torch.from_numpy(rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8)).to(dev)
+    b = torch.from_numpy(rng.integers(0, 100, (H, W, 3), dtype=np.uint8)).to(dev)
+    step = ap.FRAMES_PER_UNCAPPED_CALL
+    for bg in (b, None):
+        whole = P.preprocess_frames(t, bg, 0)
+        for k in range(0, n, step):
+            assert torch.equal(_bits(P.preprocess_frames(t[k:k + step], bg, 0)), _bits(whole[k:k + step])), (k, bg is None)
+    assert torch.equal(_bits(whole), _bits(pipeline.u8_to_input(t)))
 
 
 def test_plain_path_equals_u8_to_input(dev):

@@ -149,7 +149,7 @@ def test_bits_where_the_warp_grid_is_capped(B, H, W, r, dev):
     the same pair in a call of its own, whose grid is not capped."""
     from pivlfn import match_quality
     import analysis_plans as ap
-    plan = ap.capped_frame_grid(B, H, W)
+    plan = ap.capped_frame_grid(H * W, B)
     assert plan["blocks"] > plan["cap"] == plan["grid"]
     base = _case(8, H, W, 1, 700)
     img1, img2, flow = (np.stack([np.roll(x[b % 8], b // 8, axis=-1) for b in range(B)]) for x in base)

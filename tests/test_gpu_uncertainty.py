@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_plans as ap
 import quality_restatement as qr
 import uncertainty_restatement as ur
 from guarded import check_guards, guarded, same_bits
@@ -175,7 +176,7 @@ def test_bits_where_the_pixel_grids_are_capped(B, H, W, r, lag, dev):
     its own, whose grid is not capped."""
     from pivlfn import flow_uncertainty
     import analysis_plans as ap
-    plan = ap.capped_frame_grid(B, H, W)
+    plan = ap.capped_frame_grid(H * W, B)
     assert plan["blocks"] > plan["cap"] == plan["grid"]
     base = _case(8, H, W, 1, 700, r)
     img1, img2, flow = (np.stack([np.roll(x[b % 8], b // 8, axis=-1) for b in range(B)]) for x in base)
@@ -188,6 +189,21 @@ def test_bits_where_the_pixel_grids_are_capped(B, H, W, r, lag, dev):
     for b in [0, 1, 2, 63, 64, 65, 127, 128, 129, 130, 191, 192, 255, 256, 258, 259]:
         one = flow_uncertainty(i1[b:b + 1], i2[b:b + 1], fl[b:b + 1], r, lag, mk[b:b + 1])
         assert same_bits(one.u, whole.u[b:b + 1]) and torch.equal(one.flag, whole.flag[b:b + 1]), b
+
+
+@pytest.mark.parametrize("B,H,W,r,lag", ap.shapes(ap.UNCERTAINTY_CASES))
+def test_bits_where_the_frame_grid_is_capped(B, H, W, r, lag, dev):
+    """The same capped grids against the same pairs in five calls that are not capped: every uncertainty and every flag byte."""
+    from pivlfn import flow_uncertainty
+    base = _case(8, H, W, 1, 900, r)
+    img1, img2, flow = (np.stack([np.roll(x[b % 8], b // 8, axis=-1) for b in range(B)]) for x in base)
+    mask = qr.speckle_mask(B, H, W, 9, 2 * r + 4)
+    i1, i2, fl, mk = (torch.from_numpy(x).to(dev) for x in (img1, img2, flow, mask))
+    whole = flow_uncertainty(i1, i2, fl, r, lag, mk)
+    step = ap.FRAMES_PER_UNCAPPED_CALL
+    parts = [flow_uncertainty(i1[k:k + step], i2[k:k + step], fl[k:k + step], r, lag, mk[k:k + step]) for k in range(0, B, step)]
+    assert same_bits(whole.u, torch.cat([p.u for p in parts])) and torch.equal(whole.flag, torch.cat([p.flag for p in parts]))
+    assert 0 < int(((whole.flag & UNUSABLE) == 0).sum()) < whole.flag.numel()
 
 
 def _call(lib, ins, outs, ws, B, C, H, W, r, lag, stream, ws_bytes=None):

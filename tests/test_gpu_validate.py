@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import analysis_plans as ap
 import pivlfn
 import validate_restatement as vr
 from guarded import check_guards, guarded, holds
@@ -154,6 +155,37 @@ def test_megapixel_estimate_output_and_batch_invariance(dev):
     empty = V.validate_flow(t[:0], residual=True)
     assert empty.flow.shape == (0, 2, S, S) and empty.flag.shape == (0, S, S) and empty.flag.dtype == torch.uint8
     assert empty.residual.shape == (0, 2, S, S)
+
+
+@pytest.mark.parametrize("B,H,W", ap.shapes(ap.VALIDATE_CASES))
+def test_bits_where_the_frame_grid_is_capped(dev, B, H, W):
+    """More blocks a frame than the cap of both launches (detect and replace), so their grid-stride loops come round: a smooth flow
+    with planted outliers in every frame gives the bits of the same frames in calls that are not capped."""
+    yy, xx = np.mgrid[0:H, 0:W]
+    base = np.stack([np.sin(xx / 17.0) + 0.01 * yy, np.cos(yy / 13.0) - 0.01 * xx]).astype(np.float32)
+    frames, planted = zip(*(vr.plant(base, 20, 3, 1000 + b) for b in range(B)))
+    t = torch.from_numpy(np.stack(frames)).to(dev)
+    whole = V.validate_flow(t, 1, 1, mode="replace", residual=True)
+    flagged = whole.flag.cpu().numpy() != 0
+    assert np.array_equal(flagged, np.stack(planted)) and not torch.equal(_bits(whole.flow), _bits(t))
+    step = ap.FRAMES_PER_UNCAPPED_CALL
+    parts = [V.validate_flow(t[k:k + step], 1, 1, mode="replace", residual=True) for k in range(0, B, step)]
+    assert torch.equal(whole.flag, torch.cat([p.flag for p in parts]))
+    assert torch.equal(_bits(whole.flow), _bits(torch.cat([p.flow for p in parts])))
+    assert torch.equal(_bits(whole.residual), _bits(torch.cat([p.residual for p in parts])))
+
+
+@pytest.mark.parametrize("B,H,W", ap.shapes(ap.ACCUMULATOR_CASES))
+def test_masked_stats_where_the_grid_is_capped(dev, B, H, W):
+    """More blocks than the flat cap of the masked accumulator's launch: the restatement's sums, bit for bit, and its exact counts."""
+    rng = np.random.default_rng(H + W)
+    host = rng.normal(0, 5, (B, 2, H, W)).astype(np.float32)
+    fh = (rng.random((B, H, W)) < 0.1).astype(np.uint8) * rng.integers(1, 8, (B, H, W), dtype=np.uint8)
+    st = V.MaskedFlowStats(H, W, 0.37, dev)
+    st.update(torch.from_numpy(host).to(dev), torch.from_numpy(fh).to(dev))
+    want_acc, want_cnt = vr.accumulate_masked(np.zeros((7, H, W)), np.zeros((2, H, W)), host, fh, 0.37)
+    assert same_bits(st.acc.cpu().numpy(), want_acc)
+    assert np.array_equal(st.cnt.cpu().numpy(), want_cnt) and want_cnt[0].min() < want_cnt[0].max() == B
 
 
 def _lib_validate(flow, out, flag, resid, r, s, mode):

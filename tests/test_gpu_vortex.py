@@ -103,7 +103,7 @@ def test_bits_where_the_stage_grid_is_capped(B, H, W, r, s, dev):
     in a call of its own, whose grid is not capped (65 blocks under a cap of 16384) or, for the one frame, against a second run."""
     import types
     import analysis_plans as ap
-    plan = ap.capped_frame_grid(B, H, W)
+    plan = ap.capped_frame_grid(H * W, B)
     assert plan["blocks"] > plan["cap"] == plan["grid"]
     flow, mask = vr.random_case(np.random.default_rng(1000 * r + B), B, H, W)
     v = _run(dev, flow, r, s, mask)
