@@ -1018,6 +1018,57 @@ int pivlfn_flow_uncertainty(const float *img1, const float *img2, int C, const f
 int pivlfn_uncertainty_accumulate(const float *unc, const unsigned char *flag, double *sums /* [3,H,W]: sum ux^2, sum uy^2, n */, int B,
                                   int H, int W, void *stream);
 
+/* ---- velocity distributions of a flow SEQUENCE: per-pixel sums up to the fourth order with the quadrant split of U*V, and pooled
+ * histograms (marginal, joint, and of the sub-pixel fraction of the raw displacement: peak locking).  Added without an ABI bump
+ * (additive).
+ * Common to both entry points.  flow: NCHW [B,2,H,W] fp32;  mask: [B,H,W] bytes or NULL, nonzero = leave the vector out;  mean: [2,H,W]
+ * fp64 (the planes of u and v) or NULL.  One launch, only on `stream`; no allocation, no workspace, no host synchronisation, no
+ * floating-point atomics; can be captured into a graph.  A vector at pixel p is LEFT OUT iff its mask byte is nonzero, or
+ * !(|u| <= 1e9 && |v| <= 1e9) (NaN compares false; the 1e10 of a masked flow is invalid by itself), or a given mean or scale value at p
+ * is not finite, or a scale is given and !(scale_u(p) > 0 && scale_v(p) > 0).  All arithmetic is fp64, every operation rounded on its
+ * own (no fma; (double) of a float is exact):
+ *   U = (double)u - mean_u(p), V = (double)v - mean_v(p);  with a NULL mean U = (double)u, V = (double)v.
+ *
+ * pivlfn_flow_moments_accumulate.  acc: [PIVLFN_MOMENT_TERMS, H, W] fp64, read once and written once per call;  thr: [H,W] fp64 or NULL
+ * (0.0), the hole of the quadrant analysis.  Per pixel, frame by frame in frame order, acc[t][p] = acc[t][p] + term_t:
+ *   0: 1 (the count);  1, 2: U, V;  3..5: U*U, V*V, U*V;  6..9: (U*U)*U, (V*V)*V, (U*U)*V, (V*V)*U;
+ *   10..12: (U*U)*(U*U), (V*V)*(V*V), (U*U)*(V*V);  13..16: 1 for the quadrant of the vector;  17..20: P = U*V for that quadrant.
+ *   Quadrants: Q1 U > 0 && V > 0, Q2 U < 0 && V > 0, Q3 U < 0 && V < 0, Q4 U > 0 && V < 0.  A vector takes part in its quadrant iff
+ *   fabs(P) > thr(p) (a NaN thr admits nothing); the terms of the other quadrants, and all eight where it takes part in none, are not
+ *   added to (no + 0.0).  A vector that is left out is skipped: its pixel's 21 values keep their bits.
+ *   B frames in one call give the bits of B calls of one frame; no value depends on the launch geometry.
+ *
+ * pivlfn_flow_hist_accumulate.  scale: [2,H,W] fp64 or NULL;  hist: PIVLFN_HIST_WORDS(nbins, jbins, fbins) unsigned 64-bit counters, added
+ * to with integer atomics and never reset, so the result has the same bits whatever the launch geometry, the arrival order or the
+ * cutting of the sequence.  nbins 1..4096, jbins 0..256 (0: no joint histogram), fbins 0..1024 (0: none), hi > lo, both finite.
+ *   s = (double)nbins / (hi - lo) and sj = (double)jbins / (hi - lo), each formed once on the host.
+ *   samples:   X = U / scale_u(p), Y = V / scale_v(p);  with a NULL scale X = U, Y = V.
+ *   marginal:  t = (X - lo) * s;  t < 0: the underflow slot;  t >= nbins: the overflow slot;  otherwise slot (int)t.  (A NaN t, which
+ *              needs an s or a difference beyond the range of a double, counts as overflow.)
+ *   layout:    1. u marginal, nbins + 2 words (under, the bins, over);  2. v marginal, the same;  3. joint, jbins * jbins words, row = the
+ *              bin of Y, column = the bin of X, binned like a marginal with sj;  4. one word: the vectors outside the joint range in
+ *              either component (with jbins = 0: every vector counted);  5. the fraction histogram of u, then of v, fbins words each;
+ *              6. two words: the vectors counted, the vectors left out.
+ *   fraction:  of the RAW displacement -- mean and scale do not enter:  d = (double)u;  f = d - floor(d);
+ *              k = min((int)(f * (double)fbins), fbins - 1)  (a tiny negative d has f = 1.0 and lands in the last bin).
+ *   Every vector adds 1 to exactly one word of each of the parts 1, 2, 3 + 4, 5u, 5v and to the first word of 6, or, if it is left out,
+ *   to the last word alone.
+ * pivlfn_flow_hist_plan (host only, nothing launched): what the launcher picks for such a call -- plan[0] the persistent workgroups of
+ * the histogram launch, plan[1] the 32-bit counters of a workgroup's private table in LDS, plan[2] 1 if the joint table is part of it
+ * and 0 if the joint histogram is updated in global memory directly, plan[3] PIVLFN_HIST_WORDS, plan[4] the workgroups of
+ * pivlfn_flow_moments_accumulate at the same H and W.  It refuses what pivlfn_flow_hist_accumulate refuses before its pointers.
+ * Errors (PIVLFN_ERR_ARG, before any launch), in this order: H < 1, W < 1, B < 0 or H*W >= 2^31;  (hist) nbins, jbins or fbins out of
+ * range;  (hist) hi <= lo or either not finite;  then B == 0 succeeds, launches nothing and reads no pointer;  otherwise null flow, acc
+ * or hist;  acc or hist overlapping flow, mask, mean, thr or scale. */
+#define PIVLFN_MOMENT_TERMS 21
+#define PIVLFN_HIST_WORDS(nbins, jbins, fbins) (2 * ((size_t)(nbins) + 2) + (size_t)(jbins) * (size_t)(jbins) + 1 + 2 * (size_t)(fbins) + 2)
+int pivlfn_flow_moments_accumulate(const float *flow, const unsigned char *mask, const double *mean, const double *thr, double *acc,
+                                   int B, int H, int W, void *stream);
+int pivlfn_flow_hist_accumulate(const float *flow, const unsigned char *mask, const double *mean, const double *scale,
+                                unsigned long long *hist, int B, int H, int W, double lo, double hi, int nbins, int jbins, int fbins,
+                                void *stream);
+int pivlfn_flow_hist_plan(int B, int H, int W, int nbins, int jbins, int fbins, int plan[5]);
+
 #ifdef __cplusplus
 }
 #endif

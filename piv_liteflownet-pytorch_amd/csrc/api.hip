@@ -283,6 +283,28 @@ int pivlfn_twopoint_accumulate(const float *flow, const unsigned char *mask, con
     return launch_twopoint_accumulate(flow, mask, mean, acc, B, H, W, max_sep, step, (hipStream_t)stream);
 }
 
+int pivlfn_flow_moments_accumulate(const float *flow, const unsigned char *mask, const double *mean, const double *thr, double *acc,
+                                   int B, int H, int W, void *stream)
+{
+    return launch_flow_moments(flow, mask, mean, thr, acc, B, H, W, (hipStream_t)stream);
+}
+
+int pivlfn_flow_hist_accumulate(const float *flow, const unsigned char *mask, const double *mean, const double *scale,
+                                unsigned long long *hist, int B, int H, int W, double lo, double hi, int nbins, int jbins, int fbins,
+                                void *stream)
+{
+    return launch_flow_hist(flow, mask, mean, scale, hist, B, H, W, lo, hi, nbins, jbins, fbins, (hipStream_t)stream);
+}
+
+int pivlfn_flow_hist_plan(int B, int H, int W, int nbins, int jbins, int fbins, int plan[5])
+{
+    PIV_REQUIRE(plan, "flow_hist_plan: bad arguments");
+    HistPlan pl;
+    if (int rc = choose_flow_hist(B, H, W, nbins, jbins, fbins, pl)) return rc;
+    plan[0] = pl.groups; plan[1] = pl.lds_words; plan[2] = pl.joint_in_lds; plan[3] = (int)pl.words; plan[4] = pl.moment_blocks;
+    return PIVLFN_OK;
+}
+
 int pivlfn_spectrum_accumulate(const float *X, int L, int first, long N, long ldx, const double *basis, int K, double *acc, int *count,
                                void *stream)
 {

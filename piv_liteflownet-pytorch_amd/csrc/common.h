@@ -367,6 +367,15 @@ int launch_snapshot_project(const float *X, int n, long P, long ldx, const doubl
 int launch_twopoint_accumulate(const float *flow, const unsigned char *mask, const double *mean, double *acc, int B, int H, int W,
                                int max_sep, int step, hipStream_t st);
 
+// ---- velocity distributions (distribution.hip): per-pixel sums up to the fourth order with the quadrant split; pooled histograms ---------
+// What launch_flow_hist runs for a call (pivlfn_flow_hist_plan): the launcher's decision from the sizes alone.
+struct HistPlan { int groups, lds_words, joint_in_lds; size_t words; int moment_blocks; };
+int choose_flow_hist(int B, int H, int W, int nbins, int jbins, int fbins, HistPlan &pl);
+int launch_flow_moments(const float *flow, const unsigned char *mask, const double *mean, const double *thr, double *acc, int B, int H,
+                        int W, hipStream_t st);
+int launch_flow_hist(const float *flow, const unsigned char *mask, const double *mean, const double *scale, unsigned long long *hist,
+                     int B, int H, int W, double lo, double hi, int nbins, int jbins, int fbins, hipStream_t st);
+
 // ---- temporal spectra (spectrum.hip): one Welch segment of every vector's time series projected on K basis pairs, quadratic forms summed --
 int launch_spectrum_accumulate(const float *X, int L, int first, long N, long ldx, const double *basis, int K, double *acc, int *count,
                                hipStream_t st);

@@ -18,6 +18,7 @@ from .vortex import VortexField, vortex_gamma                           # noqa: 
 from .flowmap import LOST, OUT, UNDEFINED, FlowMap, FTLEField           # noqa: F401
 from .pod import FlowPOD, PODResult                                     # noqa: F401
 from .twopoint import TwoPointResult, TwoPointStats                     # noqa: F401
+from .distribution import DistributionResult, FlowDistribution          # noqa: F401
 from .spectrum import TemporalSpectrum, TemporalSpectrumResult          # noqa: F401
 from .pressure import PressureField, PressureResult                     # noqa: F401
 from .calibrate import (calibrate_camera, dewarp_frames, find_markers, fit_mapping, gen_template, index_lattice,  # noqa: F401
@@ -33,6 +34,7 @@ __all__ = ["FunctionCorrelation", "ModuleCorrelation", "LiteFlowNet", "LiteFlowN
            "write_png", "PngWriter", "write_png_gray", "GrayPngWriter", "match_quality", "MatchQuality", "FEW", "FLAT", "NO_PEAK", "CENTRE_OUT",
            "flow_uncertainty", "FlowUncertainty", "UncertaintyStats", "uncertainty_coverage",
            "vortex_gamma", "VortexField", "FlowMap", "FTLEField", "OUT", "LOST", "UNDEFINED", "FlowPOD", "PODResult", "TwoPointStats", "TwoPointResult",
+           "FlowDistribution", "DistributionResult",
            "TemporalSpectrum", "TemporalSpectrumResult", "PressureField", "PressureResult",
            "gen_template", "template_match", "target_points", "find_markers", "index_lattice", "fit_mapping", "dewarp_frames", "calibrate_camera",
            "write_coeff", "ParticleImageGen", "ParticleImages", "PairParticles", "displace_particles", "render_particles", "BAD"]

@@ -73,6 +73,10 @@ SIGNATURES = {
     "pivlfn_particles_render": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3
                                 + [ctypes.c_size_t, ctypes.c_void_p]),
     "pivlfn_twopoint_accumulate": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    "pivlfn_flow_moments_accumulate": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
+    "pivlfn_flow_hist_accumulate": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_double] * 2 + [ctypes.c_int] * 3
+                                    + [ctypes.c_void_p]),
+    "pivlfn_flow_hist_plan": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)]),
     "pivlfn_spectrum_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,
                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pivlfn_pressure_gradient": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_double] * 2 + [ctypes.c_void_p] * 3),

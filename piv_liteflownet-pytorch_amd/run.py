@@ -9,6 +9,7 @@
                 [--vortex [R] [--vortex-spacing S] [--vortex-image]] [--pod K [--pod-cell C]]
                 [--ftle [SPACING] [--ftle-steps T] [--ftle-image [--ftle-max X]]]
                 [--twopoint [R] [--twopoint-step S] [--twopoint-mean FILE]]
+                [--pdf [BINS] [--pdf-range LO HI] [--pdf-mean FILE [--pdf-normalise]] [--pdf-hole H] [--pdf-image]]
                 [--spectrum [L] [--spectrum-overlap O] [--spectrum-cell C] [--spectrum-fps F] [--spectrum-image]]
                 [--pressure [CELL] [--pressure-rho R] [--pressure-nu NU] [--pressure-dt DT] [--pressure-calib C] [--pressure-tol T]
                  [--pressure-image]]
@@ -62,6 +63,13 @@ Differences, all deliberate:
     0..R times `--twopoint-step S` pixels along x and along y; with --validate flag|mask the rejected vectors are left out) and
     writes <save>/twopoint.npz and <save>/twopoint.json with the integral scales, Taylor microscales and noise shares;
     `--twopoint-mean FILE` takes the per-pixel mean of a --stats run out first (flows that are not homogeneous along a row);
+  * `--pdf [BINS]` accumulates the velocity distributions of the flows of every input directory on the device
+    (pivlfn.distribution.FlowDistribution: the histograms of u and v over `--pdf-range LO HI`, their joint histogram, the histogram
+    of the sub-pixel fraction of the displacement, and per pixel the sums up to the fourth order with the quadrant split of u'v' at
+    the hole `--pdf-hole H`; with --validate flag|mask the rejected vectors are left out) and writes <save>/pdf.npz and
+    <save>/pdf.json with the peak-locking degree, the pooled skewness and flatness and the shares outside the range;
+    `--pdf-mean FILE` takes the per-pixel mean of a --stats run out first, `--pdf-normalise` also divides by its rms;
+    `--pdf-image` adds <save>/pdf_joint.png, the joint density on a logarithmic gray scale over four decades, empty bins red;
   * `--spectrum [L]` estimates the temporal spectra of the flows of every input directory, which must be a time-resolved frame
     sequence (not -p), on the device (pivlfn.spectrum.TemporalSpectrum, Welch's method: Hann-windowed segments of L pairs that
     overlap by `--spectrum-overlap O` (default L/2), mean removed; `--spectrum-cell C` analyses the means over C x C blocks of
@@ -128,6 +136,8 @@ from pivlfn.pressure import PressureField                # noqa: E402
 from pivlfn.pressure import check_params as check_pressure               # noqa: E402
 from pivlfn.postpro import FlowStats                     # noqa: E402
 from pivlfn.preproc import FrameBackground, Preprocessor                 # noqa: E402
+from pivlfn.distribution import FlowDistribution         # noqa: E402
+from pivlfn.distribution import check_params as check_pdf                # noqa: E402
 from pivlfn.spectrum import TemporalSpectrum             # noqa: E402
 from pivlfn.spectrum import check_params as check_spectrum               # noqa: E402
 from pivlfn.twopoint import TwoPointStats                # noqa: E402
@@ -270,6 +280,26 @@ parser.add_argument("--twopoint-step", type=int, default=None, metavar="S",
 parser.add_argument("--twopoint-mean", type=str, default=None, metavar="FILE",
                     help="with --twopoint: a stats.npz of an earlier --stats run over the same frames; its mean_u and mean_v are taken "
                          "out of every vector before the sums are formed")
+parser.add_argument("--pdf", type=int, nargs="?", const=256, default=None, metavar="BINS",
+                    help="accumulate the velocity distributions of the flows of each input directory on the device "
+                         "(pivlfn.distribution.FlowDistribution; not a reference flag; not with -b/-c, single process only): the "
+                         "histograms of u and v with BINS bins (1..4096, default 256), their joint histogram, the histogram of the "
+                         "sub-pixel fraction (peak locking) and the per-pixel sums up to the fourth order with the quadrant split, "
+                         "written to <save>/pdf.npz, the scalar results to <save>/pdf.json")
+parser.add_argument("--pdf-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="with --pdf: the range of the histograms in pixels (default -8 8), with --pdf-normalise in units of the local "
+                         "rms (default -6 6)")
+parser.add_argument("--pdf-mean", type=str, default=None, metavar="FILE",
+                    help="with --pdf: a stats.npz of an earlier --stats run over the same frames; its mean_u and mean_v are taken out "
+                         "of every vector first (the accurate form of the higher moments)")
+parser.add_argument("--pdf-normalise", action="store_true",
+                    help="with --pdf and --pdf-mean: the samples of the histograms are divided by rms_u and rms_v of that file, and "
+                         "the hole is in units of rms_u * rms_v")
+parser.add_argument("--pdf-hole", type=float, default=None, metavar="H",
+                    help="with --pdf: the hole size of the quadrant analysis, an event needs |U*V| > H (default 0)")
+parser.add_argument("--pdf-image", action="store_true",
+                    help="with --pdf: also <save>/pdf_joint.png, the joint density of (u, v) in gray on a logarithmic scale")
+PDF_FLAGS = ("pdf", "pdf_range", "pdf_mean", "pdf_normalise", "pdf_hole", "pdf_image")
 parser.add_argument("--spectrum", type=int, nargs="?", const=256, default=None, metavar="L",
                     help="estimate the temporal spectra of the flows of each input directory, read as a frame sequence, on the device "
                          "(pivlfn.spectrum.TemporalSpectrum, Welch's method; not a reference flag; not with -p or -b/-c, single process "
@@ -306,7 +336,7 @@ UNCERTAINTY_FLAGS = ("uncertainty", "uncertainty_lag", "uncertainty_image", "unc
 VORTEX_FLAGS = ("vortex", "vortex_spacing", "vortex_image")
 PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
 FTLE_FLAGS = ("ftle", "ftle_steps", "ftle_image", "ftle_max")
-VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + UNCERTAINTY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + SPECTRUM_FLAGS + PRESSURE_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + UNCERTAINTY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + PDF_FLAGS + SPECTRUM_FLAGS + PRESSURE_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -558,6 +588,61 @@ class TwoPoint(Stage):
         scales = ", ".join(f"{key} {summary[key]['integral_scale']:.2f}{'+' if summary[key]['truncated'] else ''}"
                            for key in ("uu_x", "uu_y", "vv_x", "vv_y"))
         print(f"Two-point statistics of {self.stats.count} flows: integral scales in pixels {scales} ('+': the correlation did not reach zero)")
+
+
+def pdf_params(args):
+    """(bins, range, joint_bins, frac_bins, hole) of the --pdf flags with the defaults filled in."""
+    rng = tuple(args.pdf_range) if args.pdf_range is not None else ((-6.0, 6.0) if args.pdf_normalise else (-8.0, 8.0))
+    return args.pdf, rng, 64, 64, 0.0 if args.pdf_hole is None else args.pdf_hole
+
+
+class Distribution(Stage):
+    """Adds every batch of flows to a FlowDistribution, created at the first batch's size and fed like Stats: after "flag" and "mask" the
+    raw flow with the flags as the mask, otherwise the written flow.  finish() writes the sums and what follows from them."""
+
+    def __init__(self, params, mean, normalise, image, file, json_file, image_file):
+        self.params, self.mean, self.normalise, self.image = params, mean, normalise, image
+        self.file, self.json_file, self.image_file = file, json_file, image_file
+        self.dist, self.mode = None, None
+
+    def __call__(self, batch):
+        flow, flag = batch.masked()
+        if self.dist is None:
+            bins, rng, joint_bins, frac_bins, hole = self.params
+            try:
+                self.dist = FlowDistribution(flow.size(2), flow.size(3), bins, rng, joint_bins, frac_bins, mean=self.mean,
+                                             scale=self.mean if self.normalise else None, hole=hole, device=flow.device)
+            except (ValueError, KeyError) as e:
+                raise SystemExit(f"run.py: --pdf: {e}")
+            self.mode = batch.mode
+        self.dist.update(flow, flag)
+
+    def finish(self, names, ctx):
+        """<save>/pdf.npz (DistributionResult.save) and <save>/pdf.json: the parameters, the validation the flows went through and
+        DistributionResult.summary(); one line with the peak-locking degrees, the pooled skewness and flatness and the share outside
+        the range; with `image` <save>/pdf_joint.png."""
+        if self.dist is None:
+            return
+        res = self.dist.result()
+        res.save(self.file, **({} if self.mode is None else {"validation": self.mode}))
+        summary = res.summary()
+        bins, rng, joint_bins, frac_bins, hole = self.params
+        write_json(self.json_file, json_strict({"bins": bins, "range": list(rng), "joint_bins": joint_bins, "frac_bins": frac_bins,
+                                                "hole": hole, "mean": self.mean, "normalise": bool(self.normalise),
+                                                "validation": self.mode, "summary": summary}))
+        pooled = summary["pooled"]
+        out = max(sum(summary[f"outside_{c}"].values()) for c in "uv")
+        print(f"Velocity distributions of {res.frames} flows ({res.counted} vectors, {res.left_out} left out): peak locking u "
+              f"{summary['peak_locking_u']:.3f}, v {summary['peak_locking_v']:.3f}; skewness u {pooled['skewness_u']:.3f}, v "
+              f"{pooled['skewness_v']:.3f}; flatness u {pooled['flatness_u']:.3f}, v {pooled['flatness_v']:.3f}; "
+              f"{100.0 * out:.2f} % outside [{rng[0]:g}, {rng[1]:g})")
+        if self.image:
+            _, density = res.joint()
+            with np.errstate(divide="ignore", invalid="ignore"):
+                logd = np.where(density > 0, np.log10(density), np.nan)            # empty bins and a histogram without vectors: bad
+            top = float(np.nanmax(logd)) if np.isfinite(logd).any() else 0.0
+            rgb = viz.scalar_to_color(torch.from_numpy(logd[None]).to(self.dist.device), top - 4.0, top, cmap="gray", bad=QUALITY_BAD_RGB)
+            viz.write_png(self.image_file, rgb[0].cpu().numpy())
 
 
 class Spectrum(Stage):
@@ -1121,6 +1206,9 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
     if args.twopoint is not None:
         stages.append(TwoPoint(args.twopoint, args.twopoint_step or 1, args.twopoint_mean, layout.sibling("twopoint.npz"),
                                layout.sibling("twopoint.json")))
+    if args.pdf is not None:
+        stages.append(Distribution(pdf_params(args), args.pdf_mean, args.pdf_normalise, args.pdf_image, layout.sibling("pdf.npz"),
+                                   layout.sibling("pdf.json"), layout.sibling("pdf_joint.png")))
     if args.spectrum is not None:
         stages.append(Spectrum(args.spectrum, args.spectrum_overlap, args.spectrum_cell or 1, 1.0 if args.spectrum_fps is None else args.spectrum_fps,
                                args.spectrum_image, layout.sibling("spectrum.npz"), layout.sibling("spectrum.json"),
@@ -1296,6 +1384,7 @@ def args_lines(args) -> List[str]:
                     (args.quality is None and k in QUALITY_FLAGS) or (args.vortex is None and k in VORTEX_FLAGS) or
                     (args.uncertainty is None and k in UNCERTAINTY_FLAGS) or
                     (args.pod is None and k in POD_FLAGS) or (args.ftle is None and k in FTLE_FLAGS) or
+                    (args.pdf is None and k in PDF_FLAGS) or
                     (args.twopoint is None and k in TWOPOINT_FLAGS) or (args.spectrum is None and k in SPECTRUM_FLAGS) or
                     (args.pressure is None and k in PRESSURE_FLAGS))]
 
@@ -1334,6 +1423,16 @@ def main(argv: Optional[List[str]] = None) -> int:
         checked("--twopoint: ", check_twopoint, args.twopoint, 1 if args.twopoint_step is None else args.twopoint_step)
         if args.twopoint_mean is not None and not os.path.isfile(args.twopoint_mean):
             raise SystemExit(f"run.py: --twopoint-mean '{args.twopoint_mean}' is not a file")
+    if _used(args, PDF_FLAGS[1:]) and args.pdf is None:
+        raise SystemExit("run.py: --pdf-range, --pdf-mean, --pdf-normalise, --pdf-hole and --pdf-image need --pdf")
+    if args.pdf is not None:
+        refuse_mods(args, "--pdf is")
+        refuse_sharded("--pdf", "run.py has no process group to merge the sums of the ranks")
+        if args.pdf_normalise and args.pdf_mean is None:
+            raise SystemExit("run.py: --pdf-normalise needs --pdf-mean (the rms of a --stats run)")
+        checked("--pdf: ", check_pdf, *pdf_params(args))
+        if args.pdf_mean is not None and not os.path.isfile(args.pdf_mean):
+            raise SystemExit(f"run.py: --pdf-mean '{args.pdf_mean}' is not a file")
     if _used(args, SPECTRUM_FLAGS[1:]) and args.spectrum is None:
         raise SystemExit("run.py: --spectrum-overlap, --spectrum-cell, --spectrum-fps and --spectrum-image need --spectrum")
     if args.spectrum is not None:

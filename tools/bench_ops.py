@@ -3,6 +3,7 @@
 
   python tools/bench_ops.py warp_corr [--batch 1] [--variants 0,8,9]   (0 shipped policy, 8 v7, 9 v6)
   python tools/bench_ops.py twopoint                                  (pivlfn_twopoint_accumulate against its HBM and fp64 bounds)
+  python tools/bench_ops.py distribution                              (pivlfn_flow_hist_accumulate and _moments_accumulate against torch.bincount / elementwise torch)
   python tools/bench_ops.py spectrum                                  (pivlfn_spectrum_accumulate, and the same sums from snapshot_project + torch)
   python tools/bench_ops.py pressure                                  (pivlfn_pressure_cg: us per iteration at 256^2 x 8 and 1024^2 x 1)
   python tools/bench_ops.py calibrate                                 (pivlfn_template_match, _target_points, _dewarp_frames at --size squared)
@@ -421,6 +422,111 @@ def bench_twopoint(args):
               flush=True)
 
 
+def _torch_hist(flow, lo, hi, nbins, jbins, fbins):
+    """What a user writes without the kernel: the histograms of pivlfn_flow_hist_accumulate from torch.bincount on fp64 copies, no mask,
+    mean or scale.  Returns the words in the layout of include/pivlfn.h."""
+    u, v = flow[:, 0].reshape(-1).double(), flow[:, 1].reshape(-1).double()
+    ok = (u.abs() <= 1e9) & (v.abs() <= 1e9)
+    u, v = u[ok], v[ok]
+
+    def slots(x, n):
+        t = (x - lo) * (n / (hi - lo))
+        return t, torch.where(t < 0, 0, torch.where(t < n, 1 + t.clamp(0, n - 1).long(), n + 1))
+    parts = [torch.bincount(slots(u, nbins)[1], minlength=nbins + 2), torch.bincount(slots(v, nbins)[1], minlength=nbins + 2)]
+    tu, tv = slots(u, jbins)[0], slots(v, jbins)[0]
+    inside = (tu >= 0) & (tu < jbins) & (tv >= 0) & (tv < jbins)
+    parts.append(torch.bincount(tv[inside].long() * jbins + tu[inside].long(), minlength=jbins * jbins))
+    parts.append((~inside).sum().reshape(1))
+    for d in (u, v):
+        parts.append(torch.bincount(((d - d.floor()) * fbins).long().clamp(max=fbins - 1), minlength=fbins))
+    parts.append(torch.stack([ok.sum(), (~ok).sum()]))
+    return torch.cat(parts)
+
+
+def _torch_moments(flow, acc):
+    """The 21 sums of pivlfn_flow_moments_accumulate from elementwise torch operations, frame by frame, no mask, mean or thr."""
+    for b in range(flow.size(0)):
+        U, V = flow[b, 0].double(), flow[b, 1].double()
+        ok = (U.abs() <= 1e9) & (V.abs() <= 1e9)
+        uu, vv, P = U * U, V * V, U * V
+        terms = [torch.ones_like(U), U, V, uu, vv, P, uu * U, vv * V, uu * V, vv * U, uu * uu, vv * vv, uu * vv]
+        event = ok & (P.abs() > 0)
+        quads = [event & (U > 0) & (V > 0), event & (U < 0) & (V > 0), event & (U < 0) & (V < 0), event & (U > 0) & (V < 0)]
+        for t, term in enumerate(terms):
+            acc[t] = torch.where(ok, acc[t] + term, acc[t])
+        for q, inq in enumerate(quads):
+            acc[13 + q] = torch.where(inq, acc[13 + q] + 1.0, acc[13 + q])
+            acc[17 + q] = torch.where(inq, acc[17 + q] + P, acc[17 + q])
+    return acc
+
+
+def _rounds(fns, n, rounds):
+    """us per call of each function of `fns`: `rounds` windows of n back-to-back calls each, the functions taking turns."""
+    out = [[] for _ in fns]
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(n):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            out[k].append(a.elapsed_time(b) / n * 1e3)
+    return [sorted(t) for t in out]
+
+
+def bench_distribution(args):
+    """pivlfn_flow_hist_accumulate and pivlfn_flow_moments_accumulate (csrc/distribution.hip) at 8 x --size squared on the production
+    library, beside the same results from torch.bincount / elementwise torch operations on the same inputs, timed in alternating
+    windows.  Per frame: the median with the smallest and largest window, the bytes a frame must move (8 bytes of flow a vector; the
+    moments also read and write 21 sums a pixel once per call) and their time at the HBM peak."""
+    from pivlfn import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream(dev).cuda_stream
+    B, S, lo, hi = 8, args.size, -8.0, 8.0
+    g = torch.Generator().manual_seed(2)
+    random = (2.0 * torch.randn(B, 2, S, S, generator=g)).to(dev)
+    constant = torch.full((B, 2, S, S), 0.3, device=dev)
+    for name, flow, table in (("default table", random, (256, 64, 64)), ("largest table", random, (4096, 256, 1024)),
+                              ("one bin, default table", constant, (256, 64, 64))):
+        words = 2 * (table[0] + 2) + table[1] ** 2 + 1 + 2 * table[2] + 2
+        hist = torch.zeros(words, dtype=torch.int64, device=dev)
+
+        def hip(flow=flow, table=table, hist=hist):
+            _lib.check(lib.pivlfn_flow_hist_accumulate(flow.data_ptr(), None, None, None, hist.data_ptr(), B, S, S, lo, hi, *table, st),
+                       "flow_hist_accumulate")
+
+        def composed(flow=flow, table=table):
+            return _torch_hist(flow, lo, hi, *table)
+        hip()
+        assert torch.equal(hist, composed()), f"{name}: the kernel and the torch composition disagree"
+        t_hip, t_torch = _rounds([hip, composed], n=10, rounds=7)
+        bound = 8 * S * S / HBM_BYTES_PER_S * 1e6
+        print(f"flow_hist_accumulate {name:22s} B={B} {S}x{S}: {t_hip[3] / B:8.2f} us/frame ({t_hip[0] / B:.2f} - {t_hip[-1] / B:.2f})  "
+              f"HBM bound {bound:5.2f} us/frame = {100 * bound * B / t_hip[3]:5.1f} %  torch {t_torch[3] / B:9.1f} us/frame "
+              f"({t_torch[0] / B:.1f} - {t_torch[-1] / B:.1f}) = {t_torch[3] / t_hip[3]:6.1f} x", flush=True)
+    for name, flow in (("random", random), ("constant", constant)):
+        acc = torch.zeros(21, S, S, dtype=torch.float64, device=dev)
+        ref = torch.zeros(21, S, S, dtype=torch.float64, device=dev)
+
+        def hip(flow=flow, acc=acc):
+            _lib.check(lib.pivlfn_flow_moments_accumulate(flow.data_ptr(), None, None, None, acc.data_ptr(), B, S, S, st), "flow_moments_accumulate")
+
+        def composed(flow=flow, ref=ref):
+            return _torch_moments(flow, ref)
+        hip()
+        assert torch.equal(acc, composed()), f"{name}: the kernel and the torch composition disagree"
+        t_hip, t_torch = _rounds([hip, composed], n=10, rounds=7)
+        bound = (8 * B + 2 * 21 * 8) * S * S / HBM_BYTES_PER_S * 1e6
+        print(f"flow_moments_accumulate {name:9s} B={B} {S}x{S}: {t_hip[3]:8.1f} us/call ({t_hip[0]:.1f} - {t_hip[-1]:.1f}) = {t_hip[3] / B:7.2f} "
+              f"us/frame  HBM bound {bound:6.1f} us/call = {100 * bound / t_hip[3]:5.1f} %  torch {t_torch[3]:9.1f} us/call "
+              f"({t_torch[0]:.1f} - {t_torch[-1]:.1f}) = {t_torch[3] / t_hip[3]:6.1f} x", flush=True)
+
+
 def bench_spectrum(args):
     """pivlfn_spectrum_accumulate (csrc/spectrum.hip): one segment call at L = 256 with all 129 frequencies of the Hann basis, at
     N = --size squared and at N = 256 squared vectors, on the production library; and the same sums formed from
@@ -598,7 +704,8 @@ def bench_calibrate(args):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate", "twopoint", "spectrum", "pressure", "calibrate"])
+    ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate", "twopoint", "distribution", "spectrum", "pressure",
+                                     "calibrate"])
     ap.add_argument("--once", action="store_true", help="preproc: one launch per shape, for a kernel trace")
     ap.add_argument("--filter", default="")
     ap.add_argument("--tune3", type=int, default=0, help="ablation mask of the fp16 conv kernel (pivlfn_tune(3, mask))")
@@ -612,5 +719,5 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=8, help="interleaved timing rounds per variant (warp_corr)")
     a = ap.parse_args()
     {"conv_stamps": bench_conv_stamps, "warp_corr": bench_warp_corr, "wc_ablate": bench_wc_ablate, "conv": bench_conv, "head": bench_head,
-     "preproc": bench_preproc, "evaluate": bench_evaluate, "twopoint": bench_twopoint, "spectrum": bench_spectrum, "pressure": bench_pressure,
+     "preproc": bench_preproc, "evaluate": bench_evaluate, "twopoint": bench_twopoint, "distribution": bench_distribution, "spectrum": bench_spectrum, "pressure": bench_pressure,
      "calibrate": bench_calibrate}[a.what](a)
