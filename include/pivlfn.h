@@ -739,7 +739,11 @@ int pivlfn_create(const pivlfn_tensor *tensors, int n_tensors, float starting_sc
                   const float rgb_mean[6], pivlfn_net **out);
 int pivlfn_destroy(pivlfn_net *net);
 
-/* Bytes of scratch pivlfn_forward needs for a [B,3,H,W] pair batch (H, W multiples of 32). */
+/* Bytes of scratch pivlfn_forward needs for a [B,3,H,W] pair batch (H, W multiples of 32) in the precision mode set at the time of
+ * the query: ask again after pivlfn_set_precision (a forward whose mode needs more than it is given returns PIVLFN_ERR_WORKSPACE).
+ * In the fp32 Winograd modes (PIVLFN_PRECISION_F32 and _F32_WINO_MFMA32): 5604 MiB per pair at 1024 x 1024 with lowest_level 1
+ * (1788 MiB with lowest_level 2); of that, 672 MiB (160 MiB) hold the flow-independent partial sums of Regularization's first
+ * layer at the levels of at least 256 x 256 pixels.  The other modes do without them: 4932 MiB (1628 MiB). */
 size_t pivlfn_workspace_bytes(const pivlfn_net *net, int B, int H, int W);
 
 /* ---- replaces LiteFlowNet.forward in eval mode, src/models.py:319-370.

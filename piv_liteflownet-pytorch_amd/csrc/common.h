@@ -241,6 +241,7 @@ struct ConvChoiceB3 {
 int choose_conv_wb(const ConvParamsW &p, int cus, ConvChoiceB3 &ch);
 int launch_conv_w(const ConvParamsW &p, hipStream_t st);
 int launch_conv_wb(const ConvParamsW &p, hipStream_t st);      // the same layers with exactly split operands on the bf16 matrix cores (conv_wino_b3.hip)
+int launch_conv_wb(const ConvParamsW &p, int cus, hipStream_t st);      // ... on at most `cus` compute units (0 = the device's): the same bits on any grid
 bool conv_wino_b3_supports(int cout_pad);
 int launch_conv_w_ws(const ConvParamsW &p, hipStream_t st);   // the same layers on persistent workgroups with producer / consumer waves (conv_wino_ws.hip); bit-identical
 long conv_wino_ws_items(const ConvParamsW &p);                // work items such a launch would have (0: not covered)
@@ -284,6 +285,10 @@ int launch_backwarp_nhwc(const float *in, const float *flow4, float scale, float
 int launch_flow_mean(const float *flow4, float *partial, float *mean, int B, int HW, hipStream_t st);
 int launch_reg_prep(const float *img1, const float *img2, const float *flow4, float *mean, const float *partial, float scale,
                     float *misc4, int B, int H, int W, hipStream_t st);
+// conv_R.0's three flow-dependent channels + bias + the precomputed partial sum of its feature channels + LeakyReLU (ops.hip)
+bool reg_r0_tail_supports(int B, int H, int W);
+int launch_reg_r0_tail(const float *misc4, const float *w, const float *bias, const float *part, float *out, int B, int H, int W,
+                       hipStream_t st);
 int launch_reg_tail(const float *dist, int dstride, const float *flow4, const float *wx, const float *wy,
                     float bx, float by, int k, float *out4, float *out_nchw, float out_scale,
                     int B, int H, int W, hipStream_t st);

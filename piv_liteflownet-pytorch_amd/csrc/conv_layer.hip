@@ -165,7 +165,8 @@ int conv(const ConvCtx &ctx, const ConvW &cw, const ConvCall &c, hipStream_t st)
         case CONV_COL7:
             return launch_conv_col7(c.src[0].ptr, c.src[0].stride, cw.wpk_c, cw.bias, c.out, c.out_stride, c.cout_store, cw.cout == 49, c.B, c.H, c.W, st);
         case CONV_ROW7: return launch_conv_row7(c.src[0].ptr, c.src[0].stride, cw.wpk_r, cw.wpk_r12, cw.bias, c.out, c.out_stride, c.B, c.H, c.W, st);
-        case CONV_WINO_B3: return launch_conv_wb(conv_params_w(cw, c, WINO_B3, 6), st);
+        // persistent workgroups: on the side stream they leave the CUs free that the main stream's small kernels need meanwhile
+        case CONV_WINO_B3: return launch_conv_wb(conv_params_w(cw, c, WINO_B3, 6), (ctx.side && st == ctx.side) ? ctx.side_cus : 0, st);
 #ifdef PIVLFN_TOOLS
         case CONV_WINO4: return launch_conv_w4(conv_params_w(cw, c, WINO_F4), st);
 #endif

@@ -776,16 +776,22 @@ int choose_conv_wb(const ConvParamsW &p, int cus, ConvChoiceB3 &ch)
     return PIVLFN_OK;
 }
 
-// p.wpk_b = pack_conv_wb's array
-int launch_conv_wb(const ConvParamsW &p_in, hipStream_t st)
+// p.wpk_b = pack_conv_wb's array.  cus: the compute units the persistent workgroups may take (0 or more than the device has = all of
+// them).  A side-stream launch leaves some free: a workgroup holds its CU's whole register file for the length of the launch, so
+// nothing else can start there.  The tiles are walked by the grid's own size and every output has one fixed summation order (header):
+// the result does not depend on cus.
+int launch_conv_wb(const ConvParamsW &p_in, int cus, hipStream_t st)
 {
     ConvParamsW p = p_in;
     p.stamps = reinterpret_cast<unsigned long long *>(((unsigned long long)(unsigned)PIV_KNOB(6) << 32) | (unsigned)PIV_KNOB(5));   // tools only (0 in production)
     ConvChoiceB3 ch;
-    if (int rc = choose_conv_wb(p, device_cus(), ch)) return rc;
+    const int dev = device_cus();
+    if (int rc = choose_conv_wb(p, cus > 0 ? std::min(cus, dev) : dev, ch)) return rc;
     PIV_REQUIRE(p.wpk_b && p.bias && p.out, "conv_wino_b3: bad arguments");
     for (int s = 0; s < p.nseg; ++s) PIV_REQUIRE(p.seg[s].ptr, "conv_wino_b3: segment %d misaligned", s);
     return ch.run(p, ch.pl.blocks, st);
 }
+
+int launch_conv_wb(const ConvParamsW &p, hipStream_t st) { return launch_conv_wb(p, 0, st); }
 
 }  // namespace pivlfn

@@ -55,6 +55,10 @@ struct ConvW {
 struct LevelW {
     float *upconv = nullptr, *upcorr = nullptr;    // depthwise k4 weights [16 taps][C4]
     ConvW M[6], S[6], R[6], feat, dist0, dist1;   // M/S: nstack hidden 3x3 layers, then the k x k head at index nstack
+    // conv_R.0 once more as two layers (levels < 5): R0a = its 128 moduleFeat input channels, zero bias (flow-independent: net_forward
+    // computes it on the side stream); R0b = its three [difference, flow - mean] channels with the layer's bias, which adds R0a's output
+    ConvW R0a, R0b;
+    float *r0t = nullptr;          // R0b's weights once more as [9 taps][3 channels][128 outputs] for reg_r0_tail_kernel (ops.hip)
     float *headM = nullptr, *headS = nullptr;      // VALU flow-head weights [k*k][8][4][2]
     float hbM[2] = {0.f, 0.f}, hbS[2] = {0.f, 0.f};
     float *wx = nullptr, *wy = nullptr;
@@ -91,6 +95,8 @@ struct pivlfn_net {
     hipStream_t side = nullptr;
     float *fuse1_w = nullptr, *fuse1_b = nullptr;      // level 1: NetC_ext + moduleFeat as 1 x 1 layers inside NetC.conv1's kernel (Conv1Fuse)
     hipEvent_t ev_fork[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, ev_join[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // the flow-independent part of conv_R.0 (R0a) on the side stream: a join per level; one fork, for level 1 behind conv1's fused kernel
+    hipEvent_t ev_pfork = nullptr, ev_pjoin[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // measurement hooks
     int prof_level = 0;
     std::vector<hipEvent_t> ev;
@@ -142,6 +148,8 @@ struct ConvCtx {
     bool no_b3;            // PIVLFN_PRECISION_F32_WINO_MFMA32: precision 0 with every Winograd layer on the fp32 instruction
     float *scratch;        // split-K scratch of the forward in progress, KSPLIT_FLOATS per image (main stream only); nullptr: never split
     hipStream_t side;      // the caller's side stream (it never splits: there is one scratch area), or nullptr
+    int side_cus = 0;      // compute units a persistent kernel may take when it is launched on `side` (0 = all): the rest stay free for
+                           // the main stream's kernels, which cannot share a CU with a workgroup that holds its whole register file
 };
 
 // This layer, called like this.  Every kernel family's parameter block is made from a ConvW and one of these.

@@ -23,8 +23,22 @@ struct Plan {
 struct Buffers {
     float *img[7], *feat[7], *ext[3], *sa, *sb;
     float *flowA, *flowB, *flow_up, *flowM, *flowS, *corr, *corr_up, *t128a, *t128b, *t64a, *t64b, *t32a, *t32b,
-        *f2w, *featR[7], *misc4, *d1, *dist, *partial, *mean, *ksplit;
+        *f2w, *featR[7], *misc4, *d1, *dist, *partial, *mean, *ksplit, *part[7];
 };
+
+// Regularization's first layer, conv_R.0 over {featR[L], misc4} (:280), is nine-tenths flow-independent: eight of its nine 16-channel
+// K steps multiply featR[L], which is ready after NetC.  At the levels where that layer is a Winograd launch of the fp32 modes on a
+// grid of at least 256 x 256 per image (where CONV_WINO_B3 begins; per image, never a function of the batch) the forward computes
+//     part[L] = W[:, feat] * featR[L]                              (R0a, no bias, no activation) on the side stream, and
+//     R.0     = LReLU(W[:, misc] * misc4 + bias + part[L])          (reg_r0_tail_kernel, a streaming pass) on the main stream.
+// Workspace: part[L] is B x h x w x 128 floats per split level -- 512 + 128 + 32 MiB per pair at 1024 x 1024.
+static bool r0_split_level(const pivlfn_net *net, int L, int h, int w)
+{
+    return L >= net->lowest && L < 5 && (long)h * w >= 256 * 256 && (long)16 * w * 128 * 4 < (1L << 31);
+}
+// Compute units a side-stream launch of the persistent Winograd kernel leaves to the main stream's chains of small kernels
+// (measured 0 / 32 / 64 / 96 and steps of 8 between: DESIGN.md 4.2g)
+static const int SIDE_CU_RESERVE = 32;
 
 static void plan(const pivlfn_net *net, int B, int H, int W, Plan &pl, Buffers &bf)
 {
@@ -53,6 +67,11 @@ static void plan(const pivlfn_net *net, int B, int H, int W, Plan &pl, Buffers &
     bf.ksplit = pl.take(KSPLIT_FLOATS * 2 * B);     // per image (NetC runs 2B images): the split never depends on the batch
     bf.partial = pl.take((size_t)B * flow_mean_partials(0) * 2);
     bf.mean = pl.take((size_t)B * 2);
+    // one per split level (not inside featR[1]: the deeper levels' sums are needed first and are computed first), in the modes that
+    // split: the plan follows the precision set when it is made, and a forward in a mode that needs more than it was given is refused
+    const bool splits = net->precision == 0 || net->precision == 5;
+    for (int L = 1; L <= 6; ++L)
+        bf.part[L] = (splits && r0_split_level(net, L, h[L], w[L])) ? pl.take((size_t)B * h[L] * w[L] * 128) : nullptr;
 }
 
 size_t net_workspace_bytes(const pivlfn_net *net, int B, int H, int W)
@@ -87,7 +106,9 @@ int net_forward(pivlfn_net *net, const float *img1, const float *img2, float *fl
     for (int L = 1; L <= 6; ++L) { h[L] = H >> (L - 1); w[L] = W >> (L - 1); }
     const int N2 = 2 * B;
     // what conv() chooses by: PIVLFN_PRECISION_F32_WINO_MFMA32 (5) is precision 0 without the split-bf16 Winograd kernel
-    const ConvCtx ctx{net->precision == 5 ? 0 : net->precision, net->precision == 5, bf.ksplit, net->side};
+    const int reserve = PIV_KNOB(8) ? PIV_KNOB(8) - 1 : SIDE_CU_RESERVE;           // tools A/B: knob 8 = reserve + 1
+    const ConvCtx ctx{net->precision == 5 ? 0 : net->precision, net->precision == 5, bf.ksplit, net->side,
+                      std::max(8, (device_cus() - reserve) / 8 * 8)};
     auto conv = [&ctx](const ConvW &cw, std::initializer_list<ConvSeg> segs, float *out, int out_stride, int cout_store, const float *res,
                        int res_stride, int lrelu, int B, int H, int W, int S, int padY, int padX, hipStream_t st, int in16 = 0, int out16 = 0) {
         return pivlfn::conv(ctx, cw, conv_call(segs.begin(), (int)segs.size(), out, out_stride, cout_store, res, res_stride, lrelu, B, H, W, S,
@@ -110,18 +131,45 @@ int net_forward(pivlfn_net *net, const float *img1, const float *img2, float *fl
     // into the caller's next use of the workspace.
     struct SideJoin {
         hipStream_t st;
-        hipEvent_t *ev;
-        unsigned pending = 0;
+        hipEvent_t *ev, *evp;
+        unsigned pending = 0;         // bit L: ev[L], bit 8 + L: evp[L] (the partial sums of conv_R.0)
         ~SideJoin()
         {
-            for (int L = 0; L < 7; ++L)
+            for (int L = 0; L < 7; ++L) {
                 if (pending & (1u << L)) (void)hipStreamWaitEvent(st, ev[L], 0);
+                if (pending & (256u << L)) (void)hipStreamWaitEvent(st, evp[L], 0);
+            }
         }
-    } side_join{st, net->ev_join};
+    } side_join{st, net->ev_join, net->ev_pjoin};
     const bool side_early = (PIV_KNOB(1) & 4096) != 0;                     // tools A/B: 4096 = each level's share right behind its NetC layer
     bool fused1 = false;          // level 1's two 1 x 1 layers were computed inside NetC.conv1's kernel (below)
+    // conv_R.0's feature part (r0_split_level) on the side stream, directly behind the 1 x 1 layer that makes featR[L] (side_level
+    // below issues it) and in front of the touch pass.  Not in the other modes, and not with everything on one stream: they keep
+    // the single-launch layer.  tools A/B: 16777216 = no split; 33554432 = level 1's share right behind conv1's fused kernel (beside
+    // NetC) instead of after NetC; 67108864 = level 1 keeps the single-launch layer
+    bool split[7] = {false, false, false, false, false, false, false};
+    int last_part = 0;            // the level whose partial sum went to the side stream last: once it is done, all of them are
+    if ((net->precision == 0 || net->precision == 5) && side != st && !(PIV_KNOB(1) & 16777216))
+        for (int L = 1; L <= 6; ++L) split[L] = r0_split_level(net, L, h[L], w[L]) && !(L == 1 && (PIV_KNOB(1) & 67108864));
+    auto part_level = [&](int L) -> int {
+        if (!split[L] || (side_join.pending & (256u << L))) return PIVLFN_OK;
+        // featR[L] is the side stream's own, written by the launch (or the one but last launch) in front of this one: stream order,
+        // with no event wait between producer and consumer (graph capture); part[L]'s last reader, the previous
+        // forward's tail pass, is behind side_level's fork.  Level 1's fused featR is conv1's kernel's, on the main stream: that one
+        // needs a fork of its own.
+        if (L == 1 && fused1) {
+            PIV_CHECK_HIP(hipEventRecord(net->ev_pfork, st));
+            PIV_CHECK_HIP(hipStreamWaitEvent(side, net->ev_pfork, 0));
+        }
+        RUN(conv(net->lv[L].R0a, {{bf.featR[L], 128, 128}}, bf.part[L], 128, 128, nullptr, 0, 0, B, h[L], w[L], 1, 1, 1, side));
+        PIV_CHECK_HIP(hipEventRecord(net->ev_pjoin[L], side));
+        side_join.pending |= 256u << L;
+        last_part = L;
+        return PIVLFN_OK;
+    };
     auto side_level = [&](int L) -> int {
-        if (L < net->lowest || L > 4 || (L == 1 && fused1)) return PIVLFN_OK;
+        if (L < net->lowest || L > 4) return PIVLFN_OK;
+        if (L == 1 && fused1) return part_level(L);
         if (side != st) {
             PIV_CHECK_HIP(hipEventRecord(net->ev_fork[L], st));
             PIV_CHECK_HIP(hipStreamWaitEvent(side, net->ev_fork[L], 0));
@@ -131,7 +179,7 @@ int net_forward(pivlfn_net *net, const float *img1, const float *img2, float *fl
             RUN(conv(net->ext[L], {{bf.feat[L], 32, 32}}, bf.ext[L], 64, 64, nullptr, 0, 1, N2, h[L], w[L], 1, 0, 0, side));
         PIV_CHECK_HIP(hipEventRecord(net->ev_join[L], side));
         if (side != st) side_join.pending |= 1u << L;
-        return PIVLFN_OK;
+        return part_level(L);
     };
     // NetC on both frames as one batch of 2B (:325-326, Features.forward :108-116)
     const ConvW *nc = net->netc;
@@ -147,7 +195,7 @@ int net_forward(pivlfn_net *net, const float *img1, const float *img2, float *fl
         fused1 = rc1 == 0;
     }
     if (!fused1) RUN(conv(nc[0], {{bf.img[1], 4, 4}}, bf.feat[1], 32, 32, nullptr, 0, 1, N2, h[1], w[1], 1, 3, 3, st));
-    if (side_early) RUN(side_level(1));
+    if (fused1 ? (PIV_KNOB(1) & 33554432) != 0 : side_early) RUN(side_level(1));
     RUN(conv(nc[1], {{bf.feat[1], 32, 32}}, bf.sa, 32, 32, nullptr, 0, 1, N2, h[1], w[1], 2, 1, 1, st));
     RUN(conv(nc[2], {{bf.sa, 32, 32}}, bf.sb, 32, 32, nullptr, 0, 1, N2, h[2], w[2], 1, 1, 1, st));
     RUN(conv(nc[3], {{bf.sb, 32, 32}}, bf.feat[2], 32, 32, nullptr, 0, 1, N2, h[2], w[2], 1, 1, 1, st));
@@ -160,8 +208,9 @@ int net_forward(pivlfn_net *net, const float *img1, const float *img2, float *fl
     if (side_early) RUN(side_level(4));
     RUN(conv(nc[8], {{bf.feat[4], 96, 96}}, bf.feat[5], 128, 128, nullptr, 0, 1, N2, h[4], w[4], 2, 1, 1, st));
     RUN(conv(nc[9], {{bf.feat[5], 128, 128}}, bf.feat[6], 192, 192, nullptr, 0, 1, N2, h[5], w[5], 2, 1, 1, st));
-    if (!side_early)
-        for (int L = 4; L >= net->lowest; --L) RUN(side_level(L));
+    // deepest first, the order the main stream wants the partial sums in; each R0a directly behind its level's 1 x 1 layers
+    for (int L = 4; L >= net->lowest; --L)
+        if (!side_early || (L == 1 && fused1)) RUN(side_level(L));
     // The side stream's 1x1 outputs (1.5 GB at 1024^2) pass through the Infinity Cache after NetC wrote the level-3 features and
     // push them out; the level-3 warp+correlation -- one tile per CU, nothing to overlap a miss with -- then gathers from HBM.  A
     // read-only pass over those features at the tail of the side stream (it runs beside levels 6-4, which use a fraction of the
@@ -192,6 +241,14 @@ int net_forward(pivlfn_net *net, const float *img1, const float *img2, float *fl
         // Regularization at levels 3 and 4.  (A cross-queue wait costs a barrier packet and a cold start for the next
         // kernel: in front of the level-3 warp+correlation it cost that launch 2 us.)
         if (L <= 2 && !(L == 1 && fused1)) { PIV_CHECK_HIP(hipStreamWaitEvent(st, net->ev_join[L], 0)); side_join.pending &= ~(1u << L); }
+        // Every partial sum is joined before level 3 starts: its warp+correlation is one tile per CU, and beside a persistent R0a
+        // launch a tile waits for a CU (14 -> 47 us).  The R0a launches fit the window of NetC's tail and levels 6-4 or nearly so;
+        // what is left of them delays level 3 instead of slowing it.  tools A/B: 268435456 = each joined in front of its own tail pass
+        // (one wait, for the launch that went last: the side stream runs them in order; the others are joined in front of their tails)
+        if (!(PIV_KNOB(1) & 268435456) && L == 3 && (side_join.pending & (256u << last_part))) {
+            PIV_CHECK_HIP(hipStreamWaitEvent(st, net->ev_pjoin[last_part], 0));
+            side_join.pending &= ~(256u << last_part);
+        }
         // ---- Matching (:165-187)
         const float *fup = nullptr;
         if (prev) {
@@ -260,7 +317,22 @@ int net_forward(pivlfn_net *net, const float *img1, const float *img2, float *fl
         if (L == 3 || L == 4) { PIV_CHECK_HIP(hipStreamWaitEvent(st, net->ev_join[L], 0)); side_join.pending &= ~(1u << L); }
         const float *fr = L < 5 ? bf.featR[L] : f1raw;
         const int cfr = L < 5 ? 128 : cf;
-        RUN(conv(lw.R[0], {{fr, cfr, cfr}, {bf.misc4, 4, 4}}, bf.t128a, 128, 128, nullptr, 0, 1, B, hh, ww, 1, 1, 1, st, 0, h16));
+        if (split[L]) {
+            // the tail of the split layer: the three flow-dependent channels, the bias, part[L], the LeakyReLU -- a streaming pass
+            // (ops.hip).  Outside that kernel's grid range (more than 65535 pairs or 131070 rows), and under tools knob 512 for A/B runs,
+            // the direct kernel with part[L] as its residual: one K chunk, nothing to split-K, and no scratch is offered.  (R0b comes
+            // from pack_conv, which makes every family's packing of a layer; only the direct one is read.)
+            if (side_join.pending & (256u << L)) { PIV_CHECK_HIP(hipStreamWaitEvent(st, net->ev_pjoin[L], 0)); side_join.pending &= ~(256u << L); }
+            if (lw.r0t && reg_r0_tail_supports(B, hh, ww) && !(PIV_KNOB(1) & 512)) {
+                RUN(launch_reg_r0_tail(bf.misc4, lw.r0t, lw.R0b.bias, bf.part[L], bf.t128a, B, hh, ww, st));
+            } else {
+                const ConvCtx tail_ctx{ctx.precision, ctx.no_b3, nullptr, ctx.side, 0};
+                const ConvSeg sm{bf.misc4, 4, 4};
+                RUN(pivlfn::conv(tail_ctx, lw.R0b, conv_call(&sm, 1, bf.t128a, 128, 128, bf.part[L], 128, 1, B, hh, ww, 1, 1, 1), st));
+            }
+        } else {
+            RUN(conv(lw.R[0], {{fr, cfr, cfr}, {bf.misc4, 4, 4}}, bf.t128a, 128, 128, nullptr, 0, 1, B, hh, ww, 1, 1, 1, st, 0, h16));
+        }
         RUN(conv(lw.R[1], {{bf.t128a, 128, 128}}, bf.t128b, 128, 128, nullptr, 0, 1, B, hh, ww, 1, 1, 1, st, h16, h16));
         RUN(conv(lw.R[2], {{bf.t128b, 128, 128}}, bf.t64a, 64, 64, nullptr, 0, 1, B, hh, ww, 1, 1, 1, st, h16, h16));
         RUN(conv(lw.R[3], {{bf.t64a, 64, 64}}, bf.t64b, 64, 64, nullptr, 0, 1, B, hh, ww, 1, 1, 1, st, h16, h16));

@@ -145,6 +145,19 @@ int pack_conv(pivlfn_net *net, const char *name, const float *w, const float *b,
     return upload(net, bias, &out->bias);
 }
 
+// The OIHW weights of one source of a layer, [cout][creal of the source][taps]: the input channels pack_conv multiplies that
+// source by (SegDef::coff, or the running offset of the sources before it)
+static void seg_weights(const float *w, int cout, int cin, int taps, const std::vector<SegDef> &segs, size_t si, std::vector<float> &out)
+{
+    int run = 0;
+    for (size_t i = 0; i < si; ++i) run += segs[i].creal;
+    const int coff = segs[si].coff >= 0 ? segs[si].coff : run, cr = segs[si].creal;
+    out.assign((size_t)cout * cr * taps, 0.f);
+    for (int n = 0; n < cout; ++n)
+        for (int c = 0; c < cr; ++c)
+            for (int t = 0; t < taps; ++t) out[((size_t)n * cr + c) * taps + t] = w[((size_t)n * cin + coff + c) * taps + t];
+}
+
 // The same from the state dict: the layer's two tensors by name
 static int pack_conv(pivlfn_net *net, const TMap &m, const std::string &name, int cout, int cin, int kh, int kw,
                      const std::vector<SegDef> &segs, ConvW *out)
@@ -227,6 +240,8 @@ int net_destroy(pivlfn_net *net)
     for (hipEvent_t e : net->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : net->ev_fork) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : net->ev_join) if (e) (void)hipEventDestroy(e);
+    if (net->ev_pfork) (void)hipEventDestroy(net->ev_pfork);
+    for (hipEvent_t e : net->ev_pjoin) if (e) (void)hipEventDestroy(e);
     if (net->side) (void)hipStreamDestroy(net->side);
     delete net;
     return PIVLFN_OK;
@@ -332,7 +347,25 @@ int net_create(const pivlfn_tensor *tensors, int n, float starting_scale, int lo
         }
         const int cfr = L < 5 ? 128 : C_FEAT[L];
         if (L < 5) TRY(pack_conv(net, m, pr + "moduleFeat.0", 128, C_FEAT[L], 1, 1, {{C_FEAT[L], C_FEAT[L]}}, &lw.feat));
-        TRY(pack_conv(net, m, pr + "conv_R.0", 128, 3 + cfr, 3, 3, {{cfr, cfr, 3}, {3, 4, 0}}, &lw.R[0]));   // reference order is [norm, rm, feat] (:280)
+        const std::vector<SegDef> r0segs = {{cfr, cfr, 3}, {3, 4, 0}};                                     // reference order is [norm, rm, feat] (:280)
+        TRY(pack_conv(net, m, pr + "conv_R.0", 128, 3 + cfr, 3, 3, r0segs, &lw.R[0]));
+        if (L < 5) {      // the same layer as two, one per source: a convolution is linear in its input channels
+            const pivlfn_tensor *w0 = find(m, pr + "conv_R.0.weight", 128, 3 + cfr, 3, 3, 4), *b0 = find(m, pr + "conv_R.0.bias", 128, 0, 0, 0, 1);
+            if (!w0 || !b0) { net_destroy(net); return PIVLFN_ERR_WEIGHTS; }
+            std::vector<float> ws;
+            const std::vector<float> zero(128, 0.f);
+            seg_weights(w0->data, 128, 3 + cfr, 9, r0segs, 0, ws);
+            TRY(pack_conv(net, "conv_R.0 (features)", ws.data(), zero.data(), 128, r0segs[0].creal, 3, 3, {{r0segs[0].creal, r0segs[0].cload}}, &lw.R0a));
+            seg_weights(w0->data, 128, 3 + cfr, 9, r0segs, 1, ws);
+            TRY(pack_conv(net, "conv_R.0 (flow)", ws.data(), b0->data, 128, r0segs[1].creal, 3, 3, {{r0segs[1].creal, r0segs[1].cload}}, &lw.R0b));
+            if (r0segs[1].creal == 3) {      // the streaming kernel's order: [tap][channel][output]
+                std::vector<float> wt((size_t)9 * 3 * 128);
+                for (int n = 0; n < 128; ++n)
+                    for (int c = 0; c < 3; ++c)
+                        for (int t = 0; t < 9; ++t) wt[((size_t)t * 3 + c) * 128 + n] = ws[((size_t)n * 3 + c) * 9 + t];
+                TRY(upload(net, wt, &lw.r0t));
+            }
+        }
         TRY(pack_conv(net, m, pr + "conv_R.2", 128, 128, 3, 3, {{128, 128}}, &lw.R[1]));
         TRY(pack_conv(net, m, pr + "conv_R.4", 64, 128, 3, 3, {{128, 128}}, &lw.R[2]));
         TRY(pack_conv(net, m, pr + "conv_R.6", 64, 64, 3, 3, {{64, 64}}, &lw.R[3]));
@@ -374,7 +407,9 @@ int net_create(const pivlfn_tensor *tensors, int n, float starting_scale, int lo
     }
     for (int L = lowest; L <= 6; ++L)
         if (hipEventCreateWithFlags(&net->ev_join[L], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&net->ev_fork[L], hipEventDisableTiming) != hipSuccess) {
+            hipEventCreateWithFlags(&net->ev_fork[L], hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&net->ev_pjoin[L], hipEventDisableTiming) != hipSuccess ||
+            (!net->ev_pfork && hipEventCreateWithFlags(&net->ev_pfork, hipEventDisableTiming) != hipSuccess)) {
             set_error("create: event creation failed");
             net_destroy(net);
             return PIVLFN_ERR_HIP;

@@ -388,6 +388,91 @@ int launch_reg_prep(const float *img1, const float *img2, const float *flow4, fl
     return PIVLFN_OK;
 }
 
+// ---- Regularization, conv_R.0's flow-dependent part (:280): out = LReLU(W[:, misc] * misc4 + bias + part) ----------------------
+// part = the layer's 128 feature channels, computed beforehand on the side stream (net.hip, r0_split_level).  27 multiplies per
+// output against 8 bytes of traffic per output: a streaming pass.  The direct kernel ran it at 2.1 x the time of a plain copy of the
+// same bytes (its 16-byte epilogue accesses touch 32 bytes of each of 32 pixels' lines per instruction); here a lane owns four
+// output channels for the whole workgroup -- its 27 x 4 weights stay in registers -- and the two half-waves of a wave take two
+// neighbouring pixels: every load of part and every store is 1 KB contiguous.  One workgroup = 64 pixels x R0T_H rows (8; 2 where 8
+// would leave fewer than 1024 workgroups: a 256 x 256 grid is 128 of them, half the CUs with one each); the misc4 patch
+// ((R0T_H + 2) x 66 pixels) sits in LDS and every read of it is a broadcast.  Summation order per output: bias, then taps row-major,
+// channels ascending inside a tap, then part; no dependence on the tile, the grid or the batch.
+constexpr int R0T_W = 64;
+template <int R0T_H>
+__global__ __launch_bounds__(256) void reg_r0_tail_kernel(const f32x4 *__restrict__ misc4, const f32x4 *__restrict__ w,
+                                                          const f32x4 *__restrict__ bias, const f32x4 *__restrict__ part,
+                                                          f32x4 *__restrict__ out, int H, int W)
+{
+    __shared__ f32x4 patch[R0T_H + 2][R0T_W + 2];
+    const int b = blockIdx.z, y0 = blockIdx.y * R0T_H, x0 = blockIdx.x * R0T_W;
+    const int tid = threadIdx.x, cq = tid & 31, ps = tid >> 5;
+    for (int i = tid; i < (R0T_H + 2) * (R0T_W + 2); i += 256) {
+        const int r = i / (R0T_W + 2), c = i % (R0T_W + 2);
+        const int yy = y0 + r - 1, xx = x0 + c - 1;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = misc4[((size_t)b * H + yy) * W + xx];
+        patch[r][c] = v;
+    }
+    f32x4 wr[27];      // [tap][input channel] -> this lane's four output channels
+#pragma unroll
+    for (int i = 0; i < 27; ++i) wr[i] = w[i * 32 + cq];
+    const f32x4 bs = bias[cq];
+    __syncthreads();
+    // pixel ps + 8 i of the row, i = 0 .. 7; the next row's partial sums are requested before this row's multiplies
+    f32x4 res[R0T_W / 8], nxt[R0T_W / 8];
+    auto load_row = [&](int r, f32x4 *dst) {
+        const size_t row = ((size_t)b * H + (y0 + r)) * W;
+#pragma unroll
+        for (int i = 0; i < R0T_W / 8; ++i) {
+            const int x = x0 + ps + 8 * i;
+            if (y0 + r < H && x < W) dst[i] = part[(row + x) * 32 + cq];
+        }
+    };
+    load_row(0, res);
+    for (int r = 0; r < R0T_H && y0 + r < H; ++r) {
+        if (r + 1 < R0T_H) load_row(r + 1, nxt);
+        const size_t row = ((size_t)b * H + (y0 + r)) * W;
+#pragma unroll
+        for (int i = 0; i < R0T_W / 8; ++i) {
+            const int px = ps + 8 * i;
+            if (x0 + px >= W) continue;
+            f32x4 acc = bs;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const f32x4 in = patch[r + t / 3][px + t % 3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[j] = fmaf(in[c], wr[3 * t + c][j], acc[j]);      // one fma chain per output: the same bits from either tile
+            }
+            acc += res[i];
+            acc[0] = lrelu01(acc[0]); acc[1] = lrelu01(acc[1]); acc[2] = lrelu01(acc[2]); acc[3] = lrelu01(acc[3]);
+            out[(row + x0 + px) * 32 + cq] = acc;
+        }
+#pragma unroll
+        for (int i = 0; i < R0T_W / 8; ++i) res[i] = nxt[i];
+    }
+}
+
+bool reg_r0_tail_supports(int B, int H, int W) { return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && cdiv(H, 2) <= 65535; }
+
+// w: [9 taps][3 input channels][128 outputs], bias: [128]; misc4 [B,H,W,4] (lane 3 is not read), part and out [B,H,W,128]
+int launch_reg_r0_tail(const float *misc4, const float *w, const float *bias, const float *part, float *out, int B, int H, int W,
+                       hipStream_t st)
+{
+    PIV_REQUIRE(misc4 && w && bias && part && out, "reg_r0_tail: null argument");
+    PIV_REQUIRE(reg_r0_tail_supports(B, H, W), "reg_r0_tail: B=%d H=%d W=%d exceed the grid range", B, H, W);
+    const f32x4 *m4 = reinterpret_cast<const f32x4 *>(misc4), *w4 = reinterpret_cast<const f32x4 *>(w), *b4 = reinterpret_cast<const f32x4 *>(bias),
+                *p4 = reinterpret_cast<const f32x4 *>(part);
+    f32x4 *o4 = reinterpret_cast<f32x4 *>(out);
+    if ((long)cdiv(W, R0T_W) * cdiv(H, 8) * B >= 1024)
+        hipLaunchKernelGGL(reg_r0_tail_kernel<8>, dim3(cdiv(W, R0T_W), cdiv(H, 8), B), dim3(256), 0, st, m4, w4, b4, p4, o4, H, W);
+    else
+        hipLaunchKernelGGL(reg_r0_tail_kernel<2>, dim3(cdiv(W, R0T_W), cdiv(H, 2), B), dim3(256), 0, st, m4, w4, b4, p4, o4, H, W);
+    PIV_CHECK_HIP(hipGetLastError());
+    return PIVLFN_OK;
+}
+
 // ---- Regularization tail (:281-302): softmax(-d^2) weighted k x k local average of u and v -----------------------
 // e_c = exp(-d_c^2 - max_c(-d_c^2)); Z = 1/sum e; u' = (bx + sum_c wx[c] e_c u[y+ky-p, x+kx-p]) * Z  (bias inside, :288-300)
 // One workgroup = a 16 x 16 tile of pixels, one pixel per thread.  The k x k neighbourhood of (u, v) every pixel needs (the

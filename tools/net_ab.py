@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """A/B of whole-forward variants in one process through the tools build: ms per 1024x1024 PIV forward for a list of
 pivlfn_tune(1, .) masks (0 = shipped; 2048 = no side stream; 16 = no 16-row conv tiles; ...), interleaved rounds.
-  python tools/net_ab.py --masks 0,2048 [--size 1024] [--batch 1]"""
+  python tools/net_ab.py --masks 0,2048 [--size 1024] [--batch 1]
+A mask may carry a value for knob 8 (the CU reserve of side-stream launches of the persistent Winograd kernel, + 1) after a colon:
+  python tools/net_ab.py --masks 16777216,0:1,0:33,0:65,0:97 --profile-level 3
+Prints every round and, at the end, median and minimum per variant."""
 import argparse
 import os
 import sys
@@ -32,11 +35,14 @@ def main():
     x, y = synth.particle_batch(a.batch, a.size, a.size, seed=1234)
     i1, i2 = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
     net = pivlfn.Network(model="piv", params=synth.generate_weights("piv", 0)).to(dev).eval()
-    masks = [int(m) for m in a.masks.split(",")]
+    masks = [tuple(int(v) for v in (m.split(":") + ["0"])[:2]) for m in a.masks.split(",")]
     ref = None
+    times = {mk: [] for mk in masks}
     for rnd in range(a.rounds):
-        for m in masks:
+        for mk in masks:
+            m, k8 = mk
             lib.pivlfn_tune(a.knob, m)
+            lib.pivlfn_tune(8, k8)
             for _ in range(3):
                 out = net(i1, i2)
             torch.cuda.synchronize()
@@ -55,8 +61,13 @@ def main():
                 extra = f"   level-{a.profile_level} warp+correlation {1e3 * k_ms / max(1, k_n):6.2f} us (n={k_n})"
             if ref is None:
                 ref = out.clone()
-            print(f"round {rnd} mask {m:5d}: {e0.elapsed_time(e1) / a.steps:8.3f} ms / forward   max|diff vs first| {(out - ref).abs().max().item():.2e}" + extra, flush=True)
+            times[mk].append(e0.elapsed_time(e1) / a.steps)
+            print(f"round {rnd} mask {m:5d}" + (f" knob8 {k8:3d}" if k8 else "") + f": {times[mk][-1]:8.3f} ms / forward   max|diff vs first| {(out - ref).abs().max().item():.2e}" + extra, flush=True)
+    for (m, k8), ts in times.items():
+        ts = sorted(ts)
+        print(f"mask {m:5d}" + (f" knob8 {k8:3d}" if k8 else "") + f": median {ts[len(ts) // 2]:8.3f} ms   min {ts[0]:8.3f} ms   ({len(ts)} rounds)", flush=True)
     lib.pivlfn_tune(a.knob, 0)
+    lib.pivlfn_tune(8, 0)
 
 
 if __name__ == "__main__":
