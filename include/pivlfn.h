@@ -36,7 +36,8 @@ typedef struct {
 
 const char *pivlfn_last_error(void);
 /* ABI version.  3 (round 6): + pivlfn_conv2d_nhwc_wino_b3, PIVLFN_PRECISION_F32_WINO_MFMA32; - pivlfn_conv2d_nhwc_wino4 (now exported by the tools build only).  2 (round 4): + pivlfn_warp_corr_nhwc_timed, pivlfn_conv2d_nhwc_wino4, pivlfn_conv_create_cat, pivlfn_conv2d_nhwc_cat; since 1 also pivlfn_conv2d_nhwc_wino and PIVLFN_PRECISION_F32_DIRECT
- * (added in round 3 without a bump); since 3 also the host-only pivlfn_conv2d_nhwc_plan, pivlfn_conv2d_nhwc_kernel_plan and pivlfn_conv_head_nhwc_plan.  No entry point of version 1 changed its signature or meaning. */
+ * (added in round 3 without a bump); since 3 also the host-only pivlfn_conv2d_nhwc_plan, pivlfn_conv2d_nhwc_kernel_plan and pivlfn_conv_head_nhwc_plan, and
+ * pivlfn_conv2d_nhwc_dist_b3 with its host-only pivlfn_conv2d_nhwc_dist_b3_plan.  No entry point of version 1 changed its signature or meaning. */
 int         pivlfn_abi_version(void);
 
 /* The library keeps no process-global mutable state: entry points may be called concurrently from several threads, on
@@ -772,11 +773,14 @@ int pivlfn_forward(pivlfn_net *net, const float *img1, const float *img2, float 
 #define PIVLFN_PRECISION_F32_DIRECT 4
 /* PIVLFN_PRECISION_F32_WINO_MFMA32: the default of rounds 3-5 -- as PIVLFN_PRECISION_F32, but every Winograd layer on the fp32 matrix
  * instruction (csrc/conv_wino.hip).  Since round 6 PIVLFN_PRECISION_F32 runs the Winograd layers with whole 64-channel output groups
- * and >= 64 staged input channels on csrc/conv_wino_b3.hip: the same algorithm and the same fp32 U = G g G^T, each fp32 operand split
+ * and >= 48 staged input channels on csrc/conv_wino_b3.hip: the same algorithm and the same fp32 U = G g G^T, each fp32 operand split
  * EXACTLY into three bf16 pieces (8 + 8 + 8 significand bits, fp32's exponent range: no narrower input domain) and each product
- * formed from six exact bf16 x bf16 products accumulated in fp32 on v_mfma_f32_32x32x16_bf16 -- what is dropped is <= 2^-23 of a
- * product (2^-26 typically), below the rounding of an fp32 fma; measured against float64 the layer error is at or below both
- * fp32-instruction kernels' (tests/test_gpu_wino_b3.py). */
+ * formed from six exact bf16 x bf16 products accumulated in fp32 on v_mfma_f32_32x32x16_bf16 -- what is dropped (ml + lm + ll) is
+ * about 2^-25 of a product under round-to-nearest pieces: of the order of the rounding an fp32 fma commits on the same product (at
+ * most 2^-24 of it), not below every such rounding; measured against float64 the layer error is at or below both
+ * fp32-instruction kernels' (tests/test_gpu_wino_b3.py).  Regularization's (7 x 1) 49 <- 32 and (1 x 7) 49 <- 49 distance layers of
+ * levels 1 and 2 (>= 256 x 256 pixels per image) multiply the same way on v_mfma_f32_16x16x32_bf16 (csrc/conv_dist_b3.hip,
+ * tests/test_gpu_dist_b3.py; their output channel 48 is an fp32 fma chain); under F32_WINO_MFMA32 they stay on v_mfma_f32_16x16x4_f32. */
 #define PIVLFN_PRECISION_F32_WINO_MFMA32 5
 /* PIVLFN_PRECISION_F32_SPLIT: fp32 results from the fp16 matrix cores.  Every fp32 operand is split exactly into three fp16
  * pieces (11 + 11 + 2 significand bits at scales 1, 2^-11, 2^-22) and each product is formed from six exact fp16 x fp16
@@ -807,7 +811,8 @@ size_t pivlfn_levels_floats(const pivlfn_net *net, int B, int H, int W);
  * res (optional): same grid as y, added before the activation; its lanes cout..roundup(cout,4) are added into y's zero lanes, so they
  * must be +0.0 (pivlfn_forward's residuals, upConv_M's flow and the previous flow head's output, hold +0.0 there), and lanes past
  * them are not read; leaky: LeakyReLU(0.1) on the result.
- * Dispatch = the PIVLFN_PRECISION_F32 network's for the shape, except Winograd (own entry point below): the direct kernel
+ * Dispatch = the PIVLFN_PRECISION_F32_WINO_MFMA32 network's for the shape, except Winograd (own entry points below; the split-bf16
+ * distance kernels of PIVLFN_PRECISION_F32 have theirs too, pivlfn_conv2d_nhwc_dist_b3): the direct kernel
  * everywhere, but a 7 x 1 layer (pad 3, 0; no residual, no activation) on an image of >= 256 x 256 pixels runs on the streaming
  * matrix-core kernel pivlfn_forward uses for conv_dist_R.0 there -- not bit-comparable with the F32_DIRECT network's layer.
  * The handle's split-K scratch holds one image's shares: a batch it is too small for runs image by image, so a sample's split factor
@@ -854,10 +859,25 @@ int pivlfn_conv2d_nhwc_wino(const pivlfn_conv *conv, const float *x, int x_strid
                             int B, int H, int W, int leaky, void *stream);
 /* The same layer (3 x 3, stride 1, pad 1, no residual; cout rounded up to 32 a multiple of 64) by Winograd F(2x2, 3x3) with every
  * fp32 operand split exactly into three bf16 pieces (8 + 8 + 8 significand bits, fp32's exponent range) and the products formed
- * on v_mfma_f32_32x32x16_bf16 (csrc/conv_wino_b3.hip): terms = 6 (dropped piece products <= 2^-23 of a product, typically 2^-26), 8
+ * on v_mfma_f32_32x32x16_bf16 (csrc/conv_wino_b3.hip): terms = 6 (dropped piece products about 2^-25 of a product), 8
  * (<= 2^-32) or 9 (the exact product of the two fp32 operands).  fp32 x, fp32 y. */
 int pivlfn_conv2d_nhwc_wino_b3(const pivlfn_conv *conv, const float *x, int x_stride, float *y, int y_stride,
                                int B, int H, int W, int leaky, int terms, void *stream);
+/* Regularization's two 49-channel distance layers -- (7 x 1) from 32 channels (pad 3, 0) and (1 x 7) from 49 channels on 52 staged lanes
+ * (pad 0, 3); stride 1, no residual, no activation, output grid = input grid -- on the streaming kernel PIVLFN_PRECISION_F32 uses for them
+ * on images of >= 256 x 256 pixels (csrc/conv_dist_b3.hip): the structure of the fp32-instruction kernels behind pivlfn_conv2d_nhwc, every
+ * fp32 operand split exactly into three bf16 pieces and the products formed on v_mfma_f32_16x16x32_bf16; terms = 6, 8 or 9 as above.
+ * Output channel 48 is an fp32 fma chain on the vector unit.  Any H, W >= 1.  x: x_stride % 4 == 0 and >= 32 (7 x 1) or >= 52 (1 x 7;
+ * lanes 49..51 are not read); y: y_stride % 4 == 0 and >= 52, lanes 49..51 are written as exact zeros, lanes past them untouched.
+ * One image's loads and stores use 32-bit byte offsets: H * W * max(x_stride, y_stride) * 4 < 2^31.  Other layers are refused. */
+int pivlfn_conv2d_nhwc_dist_b3(const pivlfn_conv *conv, const float *x, int x_stride, float *y, int y_stride,
+                               int B, int H, int W, int terms, void *stream);
+/* What pivlfn_conv2d_nhwc_dist_b3 launches for a layer of this shape and a call of this geometry, from its own checks: nothing is launched,
+ * no handle and no GPU is needed.  plan[0] 0 = the (7 x 1) layer (a wave walks rows), 1 = the (1 x 7) layer (columns); plan[1] terms;
+ * plan[2] the workgroups (four 16 x 16-pixel tiles each); plan[3] the workgroups per CU the kernel is compiled for.
+ * Returns PIVLFN_ERR_ARG, with the same message, for everything the entry point refuses for that geometry (its pointers apart). */
+int pivlfn_conv2d_nhwc_dist_b3_plan(int cout, int cin, int kh, int kw, int B, int H, int W, int terms, int x_stride, int y_stride,
+                                    int plan[4]);
 /* Which kernel pivlfn_conv2d_nhwc_f16 / _split / _wino / _wino_b3 runs for a layer of this shape (as pivlfn_conv_create packs it) and a
  * call of this geometry: the entry point's own checks and the launcher's own decision, made on the host -- nothing is launched, no handle
  * and no GPU is needed.  kernel: PIVLFN_KERNEL_PLAN_F16, _SPLIT, _WINO or _WINO_B3, the entry point asked about.  terms: the split entry

@@ -462,6 +462,17 @@ int pivlfn_conv2d_nhwc_wino_b3(const pivlfn_conv *conv, const float *x, int x_st
     return conv_forward_wb(conv, x, x_stride, y, y_stride, B, H, W, leaky, terms, (hipStream_t)stream);
 }
 
+int pivlfn_conv2d_nhwc_dist_b3(const pivlfn_conv *conv, const float *x, int x_stride, float *y, int y_stride,
+                               int B, int H, int W, int terms, void *stream)
+{
+    return conv_forward_dist_b3(conv, x, x_stride, y, y_stride, B, H, W, terms, (hipStream_t)stream);
+}
+
+int pivlfn_conv2d_nhwc_dist_b3_plan(int cout, int cin, int kh, int kw, int B, int H, int W, int terms, int x_stride, int y_stride, int plan[4])
+{
+    return conv_dist_b3_plan(cout, cin, kh, kw, B, H, W, terms, x_stride, y_stride, plan);
+}
+
 #ifdef PIVLFN_TOOLS
 int pivlfn_conv2d_nhwc_wino4(const pivlfn_conv *conv, const float *x, int x_stride, float *y, int y_stride,
                              int B, int H, int W, int leaky, void *stream)

@@ -5,7 +5,7 @@
 #                     stamps); only tools/*.py load it
 set -e
 cd "$(dirname "$0")"
-SRCS="conv_mfma conv_wino conv_wino_b3 conv_f16 conv_split conv_head warp_corr corr_bwd ops stereo postpro validate preproc evaluate viz quality uncertainty vortex flowmap particles twopoint distribution spectrum pressure calibrate pod net_weights conv_layer net api"
+SRCS="conv_mfma conv_wino conv_wino_b3 conv_dist_b3 conv_f16 conv_split conv_head warp_corr corr_bwd ops stereo postpro validate preproc evaluate viz quality uncertainty vortex flowmap particles twopoint distribution spectrum pressure calibrate pod net_weights conv_layer net api"
 build_one() {   # $1 = object dir, $2 = output .so, $3 = extra flags, $4 = extra sources (research kernels of tools/kernels/)
   local OBJ="$1" OUT="$2" EXTRA="$4"
   mkdir -p "$OBJ"
@@ -25,7 +25,8 @@ build_one() {   # $1 = object dir, $2 = output .so, $3 = extra flags, $4 = extra
       # warp_corr: the SLP vectoriser packs the consumers' fma chains into v_pk_fma_f32 behind 2-4 v_mov each (measured in the ISA)
       # conv_wino_b3: v_pk_add_f32 / v_pk_fma_f32 cost 11 cycles of the wave's issue time against 2 x 4-5 for the scalar pair
       # (tools/micro/mfma_shadow.hip), and that kernel's one wave per SIMD is issue-bound: 1 % (profiles/r06_b3_lds_ring_ab.log)
-      local PERFILE=""; { [ "$f" = "warp_corr" ] || [ "$f" = "conv_wino_b3" ]; } && PERFILE="-fno-slp-vectorize"
+      # conv_dist_b3: the same split arithmetic beside MFMAs of half the length; built like conv_wino_b3 (not measured on its own)
+      local PERFILE=""; { [ "$f" = "warp_corr" ] || [ "$f" = "conv_wino_b3" ] || [ "$f" = "conv_dist_b3" ]; } && PERFILE="-fno-slp-vectorize"
       hipcc $FLAGS $PERFILE -c "$f.hip" -o "$OBJ/$f.o" &
       pids+=($!)
     fi

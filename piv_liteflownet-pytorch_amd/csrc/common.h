@@ -256,6 +256,14 @@ int launch_conv_row7(const float *x, int x_stride, const float *wf, const float 
                      int B, int H, int W, hipStream_t st);
 int check_conv_col7(int x_stride, int out_stride, int cout_store, int single48, int B, int H, int W);   // their argument checks,
 int check_conv_row7(int x_stride, int out_stride, int B, int H, int W);                                  // pointers apart
+// The two 49-channel distance layers with exactly split operands on v_mfma_f32_16x16x32_bf16 (conv_dist_b3.hip): row = 0 the (7 x 1)
+// 49 <- 32 layer, 1 the (1 x 7) 49 <- 49 one; wb = pack_conv_dist_b3's fragments, wf / wf12 = the fp32 kernels' (output channel 48 stays
+// an fp32 fmaf chain); terms = 6, 8 or 9 piece products per product; any H, W >= 1
+int launch_conv_dist_b3(int row, const float *x, int x_stride, const void *wb, const float *wf, const float *wf12, const float *bias,
+                        float *out, int out_stride, int terms, int B, int H, int W, hipStream_t st);
+int check_conv_dist_b3(int row, int x_stride, int out_stride, int terms, int B, int H, int W);           // its argument checks, pointers apart
+long conv_dist_b3_tiles(int row, int B, int H, int W);      // tiles of a call (a workgroup walks four) and the workgroups per CU the
+int conv_dist_b3_occupancy(int row);                        // kernel is compiled for
 int launch_conv_head(const float *x, const float *w, float b0, float b1, const float *res4, float *out4, int B, int H, int W,
                      int k, hipStream_t st);
 // What launch_conv_head runs for a call (pivlfn_conv_head_nhwc_plan): kernel family (PIVLFN_HEAD_PLAN_*), output rows and columns of a

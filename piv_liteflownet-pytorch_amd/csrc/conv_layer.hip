@@ -95,7 +95,7 @@ static bool calls_row7(const ConvCall &c)
 
 // ---- the network's per-layer kernel choice ----------------------------------------------------------------------------------------
 enum ConvFamily {
-    CONV_DIRECT, CONV_F16, CONV_SPLIT, CONV_COL7, CONV_ROW7, CONV_WINO, CONV_WINO_B3,
+    CONV_DIRECT, CONV_F16, CONV_SPLIT, CONV_COL7_B3, CONV_ROW7_B3, CONV_COL7, CONV_ROW7, CONV_WINO, CONV_WINO_B3,
 #ifdef PIVLFN_TOOLS
     CONV_WINO4,
 #endif
@@ -116,6 +116,14 @@ static ConvFamily conv_family(const ConvCtx &ctx, const ConvW &cw, const ConvCal
     if ((ctx.precision == 2 || ctx.precision == 3) && !c.res && cw.wpk_x && conv_split_supports(cw.KH, cw.KW, c.S, cw.cout_pad, ctx.precision == 3 ? 3 : 6) &&
         (long)Ho * Wo >= (PIV_KNOB(11) ? PIV_KNOB(11) : (ctx.precision == 3 ? 64 * 64 : 256 * 256)))
         return CONV_SPLIT;
+    // Default fp32 mode: the two 49-channel distance convolutions of levels 1 and 2 with every operand split exactly into three bf16
+    // pieces on the 16-bit matrix cores (conv_dist_b3.hip: the streaming kernels' structure, six piece products per product; error
+    // against float64 below the fp32 instruction's: tests/test_gpu_dist_b3.py) -- 1.15-1.5 x the speed of the kernels below at 256^2 ...
+    // 1024^2, so the same per-image bound.  PIVLFN_PRECISION_F32_WINO_MFMA32 keeps the fp32 instruction; tools knob bit 2^30 as well.
+    if (ctx.precision == 0 && !ctx.no_b3 && !(PIV_KNOB(1) & 1073741824)) {
+        if (cw.wpk_cb && cw.wpk_c && calls_col7(c) && c.cout_store == 52 && c.out_stride >= 52) return CONV_COL7_B3;
+        if (cw.wpk_rb && cw.wpk_r && calls_row7(c)) return CONV_ROW7_B3;
+    }
     // fp32 mode: the (7 x 1) distance convolution of levels 1 and 2 on its streaming matrix-core kernel (per image: >= 256 x 256)
     if (ctx.precision == 0 && cw.wpk_c && calls_col7(c)) return CONV_COL7;
     if (ctx.precision == 0 && cw.wpk_r && calls_row7(c) && !(PIV_KNOB(1) & 65536)) return CONV_ROW7;
@@ -162,6 +170,10 @@ int conv(const ConvCtx &ctx, const ConvW &cw, const ConvCall &c, hipStream_t st)
             q.scratch_floats = KSPLIT_FLOATS * c.B;
             return launch_conv_x(q, st);
         }
+        case CONV_COL7_B3:
+            return launch_conv_dist_b3(0, c.src[0].ptr, c.src[0].stride, cw.wpk_cb, cw.wpk_c, nullptr, cw.bias, c.out, c.out_stride, 6, c.B, c.H, c.W, st);
+        case CONV_ROW7_B3:
+            return launch_conv_dist_b3(1, c.src[0].ptr, c.src[0].stride, cw.wpk_rb, cw.wpk_r, cw.wpk_r12, cw.bias, c.out, c.out_stride, 6, c.B, c.H, c.W, st);
         case CONV_COL7:
             return launch_conv_col7(c.src[0].ptr, c.src[0].stride, cw.wpk_c, cw.bias, c.out, c.out_stride, c.cout_store, cw.cout == 49, c.B, c.H, c.W, st);
         case CONV_ROW7: return launch_conv_row7(c.src[0].ptr, c.src[0].stride, cw.wpk_r, cw.wpk_r12, cw.bias, c.out, c.out_stride, c.B, c.H, c.W, st);
@@ -495,6 +507,39 @@ int conv_forward_wb(const pivlfn_conv *c, const float *x, int x_stride, float *y
     ConvParamsW q;
     if (int rc = conv_call_wb(c->cw, c->cin, x, x_stride, y, y_stride, B, H, W, leaky, terms, q)) return rc;
     return launch_conv_wb(q, st);
+}
+
+// Standalone (7 x 1) 49 <- 32 / (1 x 7) 49 <- 49 layer on the split-operand streaming kernel (conv_dist_b3.hip): fp32 in, fp32 out, 52
+// stored lanes, output grid = input grid, any H, W >= 1; terms = 6, 8 or 9.  conv_dist_b3_call holds the entry point's checks for a
+// layer shape -- a handle's, or the arguments of pivlfn_conv2d_nhwc_dist_b3_plan: no pointer is followed.
+static int conv_dist_b3_call(int cout, int cin, int kh, int kw, int x_stride, int y_stride, int terms, int B, int H, int W, int &row)
+{
+    const int cload = rup(cin, 4);
+    PIV_REQUIRE(packs_dist_b3(cout, cin, kh, kw, 1, cload),
+                "conv2d_dist_b3: the layer is neither the (7 x 1) 49 <- 32 nor the (1 x 7) 49 <- 49 distance convolution (%d <- %d, k=%dx%d)", cout, cin, kh, kw);
+    row = kw == 7;
+    return check_conv_dist_b3(row, x_stride, y_stride, terms, B, H, W);
+}
+
+int conv_forward_dist_b3(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride, int B, int H, int W, int terms,
+                         hipStream_t st)
+{
+    PIV_REQUIRE(c && x && y, "conv2d_dist_b3: null argument");
+    int row = 0;
+    if (int rc = conv_dist_b3_call(c->cw.cout, c->cin, c->cw.KH, c->cw.KW, x_stride, y_stride, terms, B, H, W, row)) return rc;
+    const ConvW &cw = c->cw;
+    PIV_REQUIRE(c->nsrc == 1 && (row ? cw.wpk_rb && cw.wpk_r : cw.wpk_cb && cw.wpk_c), "conv2d_dist_b3: the layer object carries no split-bf16 fragments");
+    return launch_conv_dist_b3(row, x, x_stride, row ? cw.wpk_rb : cw.wpk_cb, row ? cw.wpk_r : cw.wpk_c, cw.wpk_r12, cw.bias, y, y_stride, terms, B, H, W, st);
+}
+
+// pivlfn_conv2d_nhwc_dist_b3_plan: plan = {0 walks rows (7 x 1) | 1 walks columns (1 x 7), terms, workgroups, workgroups per CU}
+int conv_dist_b3_plan(int cout, int cin, int kh, int kw, int B, int H, int W, int terms, int x_stride, int y_stride, int plan[4])
+{
+    PIV_REQUIRE(plan, "conv2d_dist_b3_plan: null argument");
+    int row = 0;
+    if (int rc = conv_dist_b3_call(cout, cin, kh, kw, x_stride, y_stride, terms, B, H, W, row)) return rc;
+    plan[0] = row; plan[1] = terms; plan[2] = (int)((conv_dist_b3_tiles(row, B, H, W) + 3) / 4); plan[3] = conv_dist_b3_occupancy(row);
+    return PIVLFN_OK;
 }
 
 // pivlfn_conv2d_nhwc_kernel_plan: what pivlfn_conv2d_nhwc_f16 / _split / _wino / _wino_b3 would launch for a layer of this shape, as

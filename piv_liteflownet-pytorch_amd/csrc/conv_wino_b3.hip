@@ -43,6 +43,7 @@
 #include <vector>
 #include "common.h"
 #include "wino_common.h"
+#include "bf16_split.h"      // split8: x[0..7] -> three packed-bf16 operand fragments with x = h + m + l exactly
 
 #ifndef B3_PLANE_ORDER
 #define B3_PLANE_ORDER 0   // 1: plane columns of a step multiplied in the order 0, 2, 1, 3 instead of 0, 3, 1, 2 (1 % slower: see B3_JB)
@@ -51,10 +52,6 @@
 #define B3_GINNER 0      // 1: a workgroup takes the channel groups of a spatial tile one after the other (measured 1-2 % SLOWER: profiles/r06_b3_group_order_ab.log)
 #endif
 namespace pivlfn {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 // LDS image of one K step's patch (18 x 18 pixels x 16 channels fp32): pixel records of 4 channel quads + 1 quad of padding (odd
 // pitch), rows and columns de-interleaved (even then odd) as in conv_wino.hip, row pitch 104 quads = 8 mod 16: the 16 lanes of every
@@ -72,26 +69,6 @@ constexpr int BPH = 18;         // patch rows = columns: 8 tiles x 2 + 2
 constexpr int BPBUF = BPH * BROWQ + 8;      // quads per patch buffer (+ a spare record for slots past the patch)
 constexpr int BPS = 6;          // staging slots per thread: three patch rows each
 constexpr int BWAVE = 4 * 2 * 3 * 64;       // u32x4 per (step, channel group, wave): [plane col 4][channel block 2][piece 3][lane 64]
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b)
-{
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));      // v_cvt_pk_bf16_f32: round to nearest even
-}
-
-// x[0..7] -> three packed-bf16 operand fragments with x = h + m + l exactly
-__device__ __forceinline__ void split8(const float *x, u32x4 &ph, u32x4 &pm, u32x4 &pl)
-{
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const float x0 = x[2 * p], x1 = x[2 * p + 1];
-        const unsigned h = cvt_pk_bf16(x0, x1);
-        const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-        const unsigned m = cvt_pk_bf16(r0, r1);
-        const float l0 = r0 - __builtin_bit_cast(float, m << 16), l1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-        ph[p] = h;
-        pm[p] = m;
-        pl[p] = cvt_pk_bf16(l0, l1);
-    }
-}
 
 // LDS: two patch buffers (both live at a tile boundary: the next tile's first two steps) and the epilogue's exchange area, which takes
 // the accumulators in two halves of 64 KB (one tile block each)
@@ -650,22 +627,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino_b3_kernel(const ConvParamsW 
 #undef B3_MFMAS
 #undef B3_STEP
 #undef B3_STEP_LAST
-}
-
-// fp32 -> bf16 bits, round to nearest even (finite inputs)
-static unsigned short bf16_rne(float f)
-{
-    unsigned u;
-    memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-static float bf16_val(unsigned short h)
-{
-    const unsigned u = (unsigned)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
 }
 
 // OIHW [cout][cin][3][3] -> Winograd-domain weights, each split into three bf16 pieces, in MFMA A-fragment order:

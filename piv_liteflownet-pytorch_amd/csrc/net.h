@@ -33,6 +33,7 @@ void pack_conv_w4(const float *w, int cout, int cin, const int *creal, const int
 #endif
 void pack_conv_wb(const float *w, int cout, int cin, const int *creal, const int *cload, const int *coff, int nseg,
                   std::vector<unsigned short> &pk, int *nstep_out);      // conv_wino_b3.hip
+void pack_conv_dist_b3(const float *w, int cin, std::vector<unsigned short> &pk);      // conv_dist_b3.hip: w = OIHW [49][cin = 32 | 49][7 taps]
 
 struct ConvW {
     float *wpk = nullptr, *bias = nullptr;
@@ -45,6 +46,8 @@ struct ConvW {
     void *wtail_x = nullptr;       // 3 x 3 layers whose staged channels end in a 4-lane tail: that chunk with taps folded into K
     float *wpk_c = nullptr;        // (7 x 1) layers from 32 channels: A fragments of conv_col7_kernel, [4][7][2][64][4]
     float *wpk_r = nullptr, *wpk_r12 = nullptr;   // the (1 x 7) 49 -> 49 layer: A fragments of conv_row7_kernel, [4][7][3][64][4] and [4][7][64]
+    void *wpk_cb = nullptr, *wpk_rb = nullptr;    // the 49-channel ones of those once more as three bf16 pieces per weight: A fragments of
+                                                  // conv_dist_b3_kernel, [3][7][steps 1 | 2][3][64][8] (made where packs_dist_b3 holds)
     float *wpk_w = nullptr;        // 3 x 3 layers: Winograd-domain weights G g G^T in fragment order (conv_wino.hip)
     float *wpk_w4 = nullptr;       // the same for F(4x4, 3x3): 36 planes (conv_wino4.hip)
     int nchunk_w = 0, nchunk_w4 = 0;
@@ -125,6 +128,11 @@ static inline int seg_chunks(int cload) { return (cload + 7) / 8; }
 static inline int seg_tail(int cload) { return cload % 8 != 0 && cload % 8 <= 4; }
 static inline bool packs_col7(int cout, int cin, int kh, int kw, size_t nseg, int cload0) { return kh == 7 && kw == 1 && cin == 32 && cout <= 64 && nseg == 1 && cload0 == 32; }
 static inline bool packs_row7(int cout, int cin, int kh, int kw, size_t nseg, int cload0) { return kh == 1 && kw == 7 && cin == 49 && cout == 49 && nseg == 1 && cload0 == 52; }
+// the split-bf16 packing of the two: where the streaming packing is made and the layer has 49 output channels
+static inline bool packs_dist_b3(int cout, int cin, int kh, int kw, size_t nseg, int cload0)
+{
+    return cout == 49 && (packs_col7(cout, cin, kh, kw, nseg, cload0) || packs_row7(cout, cin, kh, kw, nseg, cload0));
+}
 
 struct SegDef { int creal, cload; int coff = -1; };   // coff: first input channel of this source in the OIHW weight (-1 = running offset)
 
@@ -210,6 +218,9 @@ int conv_forward_w(const pivlfn_conv *c, const float *x, int x_stride, float *y,
                    hipStream_t st, int tile);
 int conv_forward_wb(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride, int B, int H, int W, int leaky,
                     int terms, hipStream_t st);
+int conv_forward_dist_b3(const pivlfn_conv *c, const float *x, int x_stride, float *y, int y_stride, int B, int H, int W, int terms,
+                         hipStream_t st);
+int conv_dist_b3_plan(int cout, int cin, int kh, int kw, int B, int H, int W, int terms, int x_stride, int y_stride, int plan[4]);
 int conv_head_forward(const pivlfn_conv *c, const float *x, const float *res4, float *out4, int B, int H, int W, hipStream_t st);
 
 // ---- workspace plan, forward, per-layer checks of the level pipeline (net.hip) ---------------------------------------------------

@@ -105,6 +105,12 @@ int pack_conv(pivlfn_net *net, const char *name, const float *w, const float *b,
         rc = upload(net, p12, &out->wpk_r12);
         if (rc) return rc;
     }
+    if (packs_dist_b3(cout, cin, kh, kw, segs.size(), segs[0].cload)) {   // both once more as exactly split bf16 pieces (conv_dist_b3.hip)
+        std::vector<unsigned short> pb;
+        pack_conv_dist_b3(w, cin, pb);
+        rc = upload(net, pb, kh == 7 ? &out->wpk_cb : &out->wpk_rb);
+        if (rc) return rc;
+    }
     if (kh == 3 && kw == 3) {      // 3 x 3: the Winograd-domain packing (used by the stride-1 call sites)
         std::vector<float> pw;
         pack_conv_w(w, cout, cin, cr.data(), cl.data(), co.data(), nseg, pw, &out->nchunk_w);

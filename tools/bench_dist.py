@@ -2,7 +2,8 @@
 """Regularization's separable distance convolutions of levels 1 and 2 (7x1 32->49, then 1x7 49->49, no activation): the streaming
 matrix-core kernels (conv_col7 / conv_row7) against the general direct kernel, each checked against a float64 convolution.
 
-  python tools/bench_dist.py [--sizes 1024,512] [--knobs 0,65536]     knob 65536: the general direct kernel"""
+  python tools/bench_dist.py [--sizes 1024,512] [--knobs 0,65536]     knob 65536: the general direct kernel
+  python tools/bench_dist.py --b3 6,8,9       also the split-bf16 kernels (conv_dist_b3.hip, pivlfn_conv2d_nhwc_dist_b3) with these piece-product counts"""
 import argparse
 import ctypes
 import sys
@@ -17,6 +18,7 @@ from bench_ops import _chk, time_it
 ap = argparse.ArgumentParser()
 ap.add_argument("--sizes", default="1024,512")
 ap.add_argument("--knobs", default="0,65536")
+ap.add_argument("--b3", default="", help="also time pivlfn_conv2d_nhwc_dist_b3 with these piece-product counts, e.g. 6 or 6,8,9")
 ap.add_argument("--stamps", action="store_true", help="conv_row7: per-wave timeline of one launch (s_memtime ticks, 100 MHz)")
 args = ap.parse_args()
 lib = _toolslib.load()
@@ -45,6 +47,15 @@ for n in [int(v) for v in args.sizes.split(",")]:
             print(f"{n}x{n} {kh}x{kw} {ci}->{co} knob {v:6d}: min {tmin:7.1f} med {tmed:7.1f} us   {2e-6 * n * n * co * ci * 7 / tmin:6.1f} TFLOP/s real"
                   f"   max err vs float64 {err:.2e}  padding lanes zero: {bool(torch.all(y[..., co:] == 0))}", flush=True)
         lib.pivlfn_tune(1, 0)
+        for t in [int(k) for k in args.b3.split(",") if k]:
+            y = torch.full((1, n, n, 52), float("nan"), device=dev)
+
+            def fn():
+                _chk(lib.pivlfn_conv2d_nhwc_dist_b3(h, xd.data_ptr(), xs, y.data_ptr(), 52, 1, n, n, t, st), "dist_b3")
+            tmin, tmed = time_it(fn, n=20, rounds=4)
+            e = (y.cpu()[..., :co].double() - want).abs()
+            print(f"{n}x{n} {kh}x{kw} {ci}->{co} b3 terms {t}: min {tmin:7.1f} med {tmed:7.1f} us   {2e-6 * n * n * co * ci * 7 / tmin:6.1f} TFLOP/s real"
+                  f"   max err vs float64 {e.max().item():.2e} mean {e.mean().item():.2e}  padding lanes zero: {bool(torch.all(y[..., co:] == 0))}", flush=True)
         if args.stamps and kw == 7:
             import numpy as np
             nwg = -(-(n // 16) * (n // 16) // 4)
