@@ -1093,6 +1093,73 @@ int pivlfn_flow_hist_accumulate(const float *flow, const unsigned char *mask, co
                                 void *stream);
 int pivlfn_flow_hist_plan(int B, int H, int W, int nbins, int jbins, int fbins, int plan[5]);
 
+/* ---- flow smoothing and gap filling: the orthonormal 2-D DCT-II of fp64 planes, and Garcia's penalised least squares (Comput. Stat. Data
+ * Anal. 54, 2010; Exp. Fluids 50, 2011): per frame f and component c the field z that minimises  sum w (y - z)^2 + s |D z|^2,  that is
+ *   A z = W y,   A = W + s D^T D,
+ * W the diagonal of the weights (0 at masked and unknown vectors, so smoothing and gap filling are one solve), D the 5-point Laplacian
+ * with reflecting boundaries.  Solved by conjugate gradients preconditioned with M = I + s D^T D, which the DCT diagonalises.  Added
+ * without an ABI bump (additive).
+ * Every entry point launches only on `stream`, allocates nothing, never synchronises the host, copies nothing from the host, uses no
+ * atomics and can be captured into a graph as one linear chain of kernels; workspaces are 8-byte aligned and need no initial contents.
+ * All arithmetic is fp64, every operation rounded on its own (no fma outside the matrix instruction; (double) of a float is exact).
+ *
+ * Tables, built on the device:  C_N[k][n] = a_k cos(pi m / 2N),  m = ((2n+1) k) mod 4N  reduced in integers and folded into [0, N/2] by
+ *   the symmetries of the cosine (cospi(m/2N), or sinpi((N-m)/2N) past N/2),  a_0 = sqrt(1/N), a_k = sqrt(2/N): the orthonormal DCT-II
+ *   of scipy.fft.dctn(norm="ortho").  lambda_N[k] = 4 sinpi(k/2N)^2 = 2 - 2 cos(pi k/N), the eigenvalues of the negated 1-D Laplacian.
+ *
+ * pivlfn_dct2 -- x, out [P,H,W] fp64;  forward (inverse = 0): out = C_H x C_W^T;  inverse: out = C_H^T x C_W.  Three launches: the
+ *   tables, the product along the rows into the workspace, the product along the columns.  Each product is v_mfma_f64_16x16x4_f64 over
+ *   k in ascending order, four k per instruction, into accumulators that start at +0.0; operands past an edge are +0.0.  An output value
+ *   depends on its own plane alone: not on P, not on the other planes.  1 <= H, W <= PIVLFN_DCT_MAX, 1 <= P <= 65535, P*H*W < 2^31.
+ *   workspace: pivlfn_dct2_workspace_bytes(P,H,W) bytes (0 for arguments out of range).
+ *
+ * T(.) is the tree sum of pivlfn_pressure_*, over the N = H*W nodes of one system (f, c) in row-major order.
+ * Lap(a)(j,i) = ((l + r) + u) + d,  each term (neighbour - centre) for a neighbour inside the frame and +0.0 for one outside.
+ * A a = w*a + s*Lap(Lap(a)).   M^-1 a = IDCT(Gamma o DCT(a)),  Gamma[k][l] = 1.0 / (1.0 + s*(e*e)),  e = lambda_H[k] + lambda_W[l],
+ *   the product with Gamma being the last step of the forward transform.
+ *
+ * pivlfn_smooth_setup -- flows [F,2,H,W] fp32;  weights [F,H,W] fp32 or NULL (all 1);  mask [F,H,W] bytes or NULL.  Thirteen launches.
+ *   w = (double)weight where the vector takes part, else +0.0.  A vector takes part iff its mask byte is zero (or mask is NULL), both its
+ *   components satisfy |x| <= 1e9f (NaN fails: the unknown rule of pivlfn_vortex_gamma) and its weight is positive and finite.  The
+ *   components of a vector that does not take part enter no arithmetic: b = w*(double)y where it takes part, else +0.0.
+ *   x = M^-1 b;  r = b - A x;  z = M^-1 r;  rho = T(r*z);  rr = T(r*r);  bb = T(b*b);  iterations = 0;  state = PIVLFN_SMOOTH_RUNNING,
+ *   or PIVLFN_SMOOTH_EMPTY where !(T(w) > 0): such a frame takes no further part.
+ *
+ * pivlfn_smooth_pcg -- enqueues `iters` iterations for all 2F systems in the same launches, eight launches per iteration.  s must be the
+ *   s of the setup.  Every system has its own scalars and state: a frame's bits are the same alone, in any batch, and however `iters` is
+ *   cut into calls; u and v of a frame share nothing but w.  One iteration of one system:
+ *     1. if state != RUNNING, do nothing (the matrix products skip its planes).
+ *     2. if rr <= (tol*tol)*bb, set state = CONVERGED and change nothing else.
+ *     3. d = z (first iteration) or z + beta*d;  q = A d;  sigma = T(d*q).
+ *     4. if !(sigma > 0), set state = BREAKDOWN and change nothing else (a NaN ends here).
+ *     5. alpha = rho/sigma;  x = x + alpha*d;  r = r - alpha*q;  rr = T(r*r);  z = M^-1 r;  rho' = T(r*z);  beta = rho'/rho;  rho = rho';
+ *        iterations += 1.
+ *   With unit weights and no gap A = M, x from the setup is the solution and the system converges with 0 iterations.  M^-1 assumes
+ *   weights of order 1: the iteration count grows as they leave it.
+ *   iters == 0 succeeds and launches nothing.
+ *
+ * pivlfn_smooth_read -- z [F,2,H,W] fp64: x, or 1e10 in an EMPTY frame;  z32 (may be NULL): the same rounded to fp32;  filled (may be
+ *   NULL) [F,H,W] bytes: 1 where w = 0;  status [F,2,4] fp64: state, iterations, rr, bb of each system.  One launch.  The workspace is not
+ *   changed: iterating can go on afterwards.
+ *
+ * Errors (PIVLFN_ERR_ARG, on the host before any launch, the message names the problem): a null pointer;  H or W outside
+ * 1..PIVLFN_DCT_MAX;  P outside 1..65535;  F outside 1..32767;  P*H*W or 2*F*H*W >= 2^31;  s or tol not finite and positive;  iters < 0;
+ * a workspace that is misaligned or smaller than the query;  dct2: out overlapping x, the workspace overlapping either;  setup: the
+ * workspace overlapping an input;  read: an output overlapping the workspace or another output. */
+#define PIVLFN_DCT_MAX          4096
+#define PIVLFN_SMOOTH_RUNNING   1
+#define PIVLFN_SMOOTH_CONVERGED 2
+#define PIVLFN_SMOOTH_BREAKDOWN 3
+#define PIVLFN_SMOOTH_EMPTY     4
+size_t pivlfn_dct2_workspace_bytes(int P, int H, int W);
+int pivlfn_dct2(const double *x, double *out, int P, int H, int W, int inverse, void *workspace, size_t workspace_bytes, void *stream);
+size_t pivlfn_smooth_workspace_bytes(int F, int H, int W);
+int pivlfn_smooth_setup(const float *flows, const float *weights, const unsigned char *mask, int F, int H, int W, double s,
+                        void *workspace, size_t workspace_bytes, void *stream);
+int pivlfn_smooth_pcg(void *workspace, size_t workspace_bytes, int F, int H, int W, double s, double tol, int iters, void *stream);
+int pivlfn_smooth_read(const void *workspace, size_t workspace_bytes, int F, int H, int W, double *z, float *z32, unsigned char *filled,
+                       double *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -337,6 +337,32 @@ int pivlfn_pressure_read(const void *workspace, size_t workspace_bytes, int F, i
     return launch_pressure_read(workspace, workspace_bytes, F, h, w, p, flag, status, (hipStream_t)stream);
 }
 
+size_t pivlfn_dct2_workspace_bytes(int P, int H, int W) { return dct2_workspace_bytes(P, H, W); }
+
+int pivlfn_dct2(const double *x, double *out, int P, int H, int W, int inverse, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return launch_dct2(x, out, P, H, W, inverse, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t pivlfn_smooth_workspace_bytes(int F, int H, int W) { return smooth_workspace_bytes(F, H, W); }
+
+int pivlfn_smooth_setup(const float *flows, const float *weights, const unsigned char *mask, int F, int H, int W, double s,
+                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    return launch_smooth_setup(flows, weights, mask, F, H, W, s, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int pivlfn_smooth_pcg(void *workspace, size_t workspace_bytes, int F, int H, int W, double s, double tol, int iters, void *stream)
+{
+    return launch_smooth_pcg(workspace, workspace_bytes, F, H, W, s, tol, iters, (hipStream_t)stream);
+}
+
+int pivlfn_smooth_read(const void *workspace, size_t workspace_bytes, int F, int H, int W, double *z, float *z32, unsigned char *filled,
+                       double *status, void *stream)
+{
+    return launch_smooth_read(workspace, workspace_bytes, F, H, W, z, z32, filled, status, (hipStream_t)stream);
+}
+
 int pivlfn_flow_maxrad(const float *flow, const unsigned char *mask, float *maxrad, int B, int H, int W, void *stream)
 {
     return launch_flow_maxrad(flow, mask, maxrad, B, H, W, (hipStream_t)stream);

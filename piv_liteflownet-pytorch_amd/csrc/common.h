@@ -401,6 +401,16 @@ int launch_pressure_setup(const double *g, const unsigned char *valid, int F, in
 int launch_pressure_cg(void *ws, size_t ws_bytes, int F, int h, int w, double tol, int iters, hipStream_t st);
 int launch_pressure_read(const void *ws, size_t ws_bytes, int F, int h, int w, double *p, unsigned char *flag, double *status, hipStream_t st);
 
+// ---- smoothing and gap filling (smooth.hip): the fp64 2-D DCT on the matrix cores, penalised least squares by DCT-preconditioned CG ------
+size_t dct2_workspace_bytes(int P, int H, int W);
+int launch_dct2(const double *x, double *out, int P, int H, int W, int inverse, void *ws, size_t ws_bytes, hipStream_t st);
+size_t smooth_workspace_bytes(int F, int H, int W);
+int launch_smooth_setup(const float *flows, const float *weights, const unsigned char *mask, int F, int H, int W, double s, void *ws,
+                        size_t ws_bytes, hipStream_t st);
+int launch_smooth_pcg(void *ws, size_t ws_bytes, int F, int H, int W, double s, double tol, int iters, hipStream_t st);
+int launch_smooth_read(const void *ws, size_t ws_bytes, int F, int H, int W, double *z, float *z32, unsigned char *filled, double *status,
+                       hipStream_t st);
+
 // ---- stereo calibration (calibrate.hip): template matching, marker centres of the correlation map, image dewarp -------------------------
 size_t template_match_workspace_bytes(int th, int tw);
 int launch_template_match(const unsigned char *images, const unsigned char *templ, float *r, int B, int H, int W, int th, int tw,

@@ -21,6 +21,7 @@ from .twopoint import TwoPointResult, TwoPointStats                     # noqa: 
 from .distribution import DistributionResult, FlowDistribution          # noqa: F401
 from .spectrum import TemporalSpectrum, TemporalSpectrumResult          # noqa: F401
 from .pressure import PressureField, PressureResult                     # noqa: F401
+from .smooth import Smoothed, dct2, smooth_flow, smooth_param, smooth_wavelength, weights_from_uncertainty  # noqa: F401
 from .calibrate import (calibrate_camera, dewarp_frames, find_markers, fit_mapping, gen_template, index_lattice,  # noqa: F401
                         target_points, template_match, write_coeff)
 from .particles import BAD, PairParticles, ParticleImageGen, ParticleImages, displace_particles, render_particles  # noqa: F401
@@ -36,5 +37,6 @@ __all__ = ["FunctionCorrelation", "ModuleCorrelation", "LiteFlowNet", "LiteFlowN
            "vortex_gamma", "VortexField", "FlowMap", "FTLEField", "OUT", "LOST", "UNDEFINED", "FlowPOD", "PODResult", "TwoPointStats", "TwoPointResult",
            "FlowDistribution", "DistributionResult",
            "TemporalSpectrum", "TemporalSpectrumResult", "PressureField", "PressureResult",
+           "smooth_flow", "Smoothed", "smooth_param", "smooth_wavelength", "weights_from_uncertainty", "dct2",
            "gen_template", "template_match", "target_points", "find_markers", "index_lattice", "fit_mapping", "dewarp_frames", "calibrate_camera",
            "write_coeff", "ParticleImageGen", "ParticleImages", "PairParticles", "displace_particles", "render_particles", "BAD"]

@@ -88,6 +88,14 @@ SIGNATURES = {
                                                                                           ctypes.c_void_p]),
     "pivlfn_pressure_cg": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 3 + [ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
     "pivlfn_pressure_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4),
+    "pivlfn_dct2_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "pivlfn_dct2": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "pivlfn_smooth_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "pivlfn_smooth_setup": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t,
+                                                                                       ctypes.c_void_p]),
+    "pivlfn_smooth_pcg": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 3 + [ctypes.c_double] * 2
+                          + [ctypes.c_int, ctypes.c_void_p]),
+    "pivlfn_smooth_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 5),
     "pivlfn_snapshot_gram_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_long]),
     "pivlfn_snapshot_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_size_t, ctypes.c_void_p]),

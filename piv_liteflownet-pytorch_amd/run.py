@@ -13,6 +13,7 @@
                 [--spectrum [L] [--spectrum-overlap O] [--spectrum-cell C] [--spectrum-fps F] [--spectrum-image]]
                 [--pressure [CELL] [--pressure-rho R] [--pressure-nu NU] [--pressure-dt DT] [--pressure-calib C] [--pressure-tol T]
                  [--pressure-image]]
+                [--smooth [WAVELENGTH] [--smooth-tol T]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -87,6 +88,12 @@ Differences, all deliberate:
     |grad p| on the lattice (1e10 where a node has no value; the first and the last pair of a directory get none), the parameters and
     per-pair summaries in <save>/pressure.json, with `--pressure-image` <name>_pres.png (blue - white - red on a symmetric range);
     with --validate flag|mask the rejected vectors are left out of the block means.  A single process, not with -b/-c;
+  * `--smooth [WAVELENGTH]` smooths every flow and fills its gaps in one solve, on the device (pivlfn.smooth.smooth_flow: penalised
+    least squares, conjugate gradients preconditioned in the DCT basis), directly after --validate: under flag|mask the rejected
+    vectors are the gaps, under replace only those the median step could not replace, and unknown vectors always are.  Waves of
+    WAVELENGTH pixels (default 8) keep half their amplitude; `--smooth-tol T` is the relative residual to reach (default 1e-8).  The
+    .flo files and every later stage get the smoothed, complete flow; the parameters and per pair the filled vectors, iterations,
+    residual and converged go to <save>/smooth.json.  A single process, not with -b/-c;
   * `--pod K` decomposes the flows of every input directory after it has been processed (pivlfn.pod.FlowPOD, snapshot POD: the
     Gram matrix of the flows in float64 on the device, its eigenvectors on the host): the first K modes, the mean, the coefficients
     and the energy fractions go to <save>/pod.npz, one line per mode is printed, and with --color the modes are drawn as
@@ -134,6 +141,7 @@ from pivlfn.pipeline import PairLoader, stream_pairs     # noqa: E402
 from pivlfn.pod import FlowPOD                           # noqa: E402
 from pivlfn.pressure import PressureField                # noqa: E402
 from pivlfn.pressure import check_params as check_pressure               # noqa: E402
+from pivlfn.smooth import check_params as check_smooth, smooth_flow, summarize as summarize_smooth      # noqa: E402
 from pivlfn.postpro import FlowStats                     # noqa: E402
 from pivlfn.preproc import FrameBackground, Preprocessor                 # noqa: E402
 from pivlfn.distribution import FlowDistribution         # noqa: E402
@@ -326,6 +334,13 @@ parser.add_argument("--pressure-tol", type=float, default=None, metavar="T",
                     help="with --pressure: the relative residual at which the conjugate gradients stop (default 1e-8)")
 parser.add_argument("--pressure-image", action="store_true",
                     help="with --pressure: also <name>_pres.png, p in blue - white - red on a symmetric range, nodes without a value black")
+parser.add_argument("--smooth", type=float, nargs="?", const=8.0, default=None, metavar="WAVELENGTH",
+                    help="smooth every flow and fill its gaps by penalised least squares (pivlfn.smooth.smooth_flow), directly after "
+                         "--validate, whose rejected vectors are the gaps: waves of WAVELENGTH pixels (default 8) keep half their "
+                         "amplitude; the .flo files and every later stage get the smoothed flow, the summaries go to <save>/smooth.json")
+parser.add_argument("--smooth-tol", type=float, default=None, metavar="T",
+                    help="with --smooth: the relative residual at which the conjugate gradients stop (default 1e-8)")
+SMOOTH_FLAGS = ("smooth", "smooth_tol")
 PRESSURE_FLAGS = ("pressure", "pressure_rho", "pressure_nu", "pressure_dt", "pressure_calib", "pressure_tol", "pressure_image")
 SPECTRUM_FLAGS = ("spectrum", "spectrum_overlap", "spectrum_cell", "spectrum_fps", "spectrum_image")
 TWOPOINT_FLAGS = ("twopoint", "twopoint_step", "twopoint_mean")
@@ -336,7 +351,7 @@ UNCERTAINTY_FLAGS = ("uncertainty", "uncertainty_lag", "uncertainty_image", "unc
 VORTEX_FLAGS = ("vortex", "vortex_spacing", "vortex_image")
 PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
 FTLE_FLAGS = ("ftle", "ftle_steps", "ftle_image", "ftle_max")
-VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + UNCERTAINTY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + PDF_FLAGS + SPECTRUM_FLAGS + PRESSURE_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + UNCERTAINTY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + PDF_FLAGS + SPECTRUM_FLAGS + PRESSURE_FLAGS + SMOOTH_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -534,6 +549,47 @@ class Validate(Stage):
         write_json(self.file, {"mode": self.mode, **self.params,
                                "pairs": {name: dict(zip(keys, row)) for name, row in zip(names, rows)},
                                "total": {k: sum(row[i] for row in rows) for i, k in enumerate(keys)}})
+
+
+class Smooth(Stage):
+    """smooth_flow on the device, directly after validation: under "flag" and "mask" the raw flow with the validator's flags as the gaps,
+    under "replace" the replaced flow with only the NOT_REPLACED vectors as gaps, without validation the flow as it is (unknown vectors
+    are gaps by themselves).  Sets what the .flo files and every later stage get to the smoothed flow -- complete, so the flags and the
+    mode are cleared.  The iterations are driven as the Pressure stage drives its own: in chunks, the states read in between.  The
+    per-pair records stay on the device until finish() copies them once."""
+
+    def __init__(self, wavelength, tol, file):
+        self.wavelength, self.tol, self.file = wavelength, tol, file
+        self.mode, self.s, self.max_iter, self._rows = None, None, None, []
+
+    def __call__(self, batch):
+        if batch.mode in ("flag", "mask"):
+            flow, gaps = batch.raw, batch.flag
+        elif batch.mode == "replace":
+            flow, gaps = batch.flow, batch.flag & NOT_REPLACED
+        else:
+            flow, gaps = batch.flow, None
+        try:
+            res = smooth_flow(flow, wavelength=self.wavelength, mask=gaps, tol=self.tol)
+        except ValueError as e:
+            raise SystemExit(f"run.py: --smooth: {e}")
+        if not self._rows:
+            self.mode, self.s, self.max_iter = batch.mode, res.s, res.max_iter
+        self._rows.append((res.filled.flatten(1).sum(1), res.status))
+        batch.flow, batch.flag, batch.mode = res.flow, None, None
+
+    def finish(self, names, ctx):
+        """<save>/smooth.json: the parameters, per pair name the filled vectors, iterations, residual and converged, and the count of
+        unconverged pairs."""
+        filled = _cat([f for f, _ in self._rows])
+        status = _cat([st for _, st in self._rows])
+        frames = summarize_smooth(status.numpy(), filled.tolist(), self.tol) if self._rows else []
+        assert len(frames) == len(names)
+        doc = {"wavelength": self.wavelength, "s": self.s, "tol": self.tol, "max_iter": self.max_iter, "validation": self.mode,
+               "pairs": dict(zip(names, frames)), "unconverged": int(sum(not fr["converged"] for fr in frames))}
+        write_json(self.file, json_strict(doc), allow_nan=False)
+        print(f"Smoothed {len(frames)} pairs at {self.wavelength} px: {sum(fr['filled'] for fr in frames)} vectors filled, "
+              f"{doc['unconverged']} pairs not converged -> '{self.file}'")
 
 
 class Stats(Stage):
@@ -1201,6 +1257,8 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
     if args.validate is not None:
         stages.append(Validate(args.validate, args.validate_radius, args.validate_spacing, args.validate_eps, args.validate_thresh,
                                layout.sibling("validation.json")))
+    if args.smooth is not None:
+        stages.append(Smooth(args.smooth, 1e-8 if args.smooth_tol is None else args.smooth_tol, layout.sibling("smooth.json")))
     if args.stats:
         stages.append(Stats(layout.sibling("stats.npz")))
     if args.twopoint is not None:
@@ -1386,7 +1444,7 @@ def args_lines(args) -> List[str]:
                     (args.pod is None and k in POD_FLAGS) or (args.ftle is None and k in FTLE_FLAGS) or
                     (args.pdf is None and k in PDF_FLAGS) or
                     (args.twopoint is None and k in TWOPOINT_FLAGS) or (args.spectrum is None and k in SPECTRUM_FLAGS) or
-                    (args.pressure is None and k in PRESSURE_FLAGS))]
+                    (args.pressure is None and k in PRESSURE_FLAGS) or (args.smooth is None and k in SMOOTH_FLAGS))]
 
 
 def load_weights(args) -> Tuple[dict, str]:
@@ -1451,6 +1509,12 @@ def main(argv: Optional[List[str]] = None) -> int:
             raise SystemExit("run.py: --pressure is not available with -p (the pairs of a pair folder are not a time series)")
         refuse_sharded("--pressure", "a pressure field follows the pairs of a directory in order, on one device")
         checked("--pressure: ", check_pressure, *pressure_params(args))
+    if args.smooth_tol is not None and args.smooth is None:
+        raise SystemExit("run.py: --smooth-tol needs --smooth")
+    if args.smooth is not None:
+        refuse_mods(args, "--smooth is")
+        refuse_sharded("--smooth", "smooth.json lists the pairs of one process")
+        checked("--smooth: ", check_smooth, None, args.smooth, 1e-8 if args.smooth_tol is None else args.smooth_tol)
     if args.pod_cell is not None and args.pod is None:
         raise SystemExit("run.py: --pod-cell needs --pod")
     if args.pod is not None:

@@ -1,0 +1,325 @@
+"""GPU: pivlfn.smooth -- the fp64 2-D DCT on the matrix cores against scipy.fft, and the penalised-least-squares solve against the dense
+operator of tests/smooth_restatement.py.
+
+Bounds.  Transform: elementwise (H + W + 16) 2^-52 (|C_H| |X| |C_W|^T), the forward error bound of the two chained products plus a few
+ulp for the table entries (numpy's own product stays under 0.31 of it on these shapes).  Solve, from the GPU's fp64 z, with
+r = W y - A z formed in numpy:  |r| <= 2 tol |W y|  (the factor 2 covers the gap between the recursively updated residual and the
+recomputed one) and |z - z_direct| <= 2 |r| / lambda_min(A)."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+from scipy.fft import dctn, idctn
+
+import smooth_restatement as sr
+from guarded import check_guards, guarded
+from pivlfn import _lib, smooth
+from pivlfn.flo import read_flow
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1), (1, 9), (5, 7), (63, 65), (64, 64), (65, 130), (129, 31)]       # one tile, ragged tiles, around the K chunk of 32
+TOL = 1e-8
+
+
+def _planes(P, H, W, seed):
+    """Values spread over six decades, both signs."""
+    rng = np.random.default_rng(seed)
+    return rng.standard_normal((P, H, W)) * 10.0 ** rng.uniform(-3.0, 3.0, (P, H, W))
+
+
+# ---- 1. the transform -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("H,W", SHAPES)
+def test_dct2_against_scipy(H, W, dev):
+    x = _planes(3, H, W, 100 * H + W)
+    xd = torch.from_numpy(x).to(dev)
+    fwd, inv = smooth.dct2(xd), smooth.dct2(xd, inverse=True)
+    back = smooth.dct2(fwd, inverse=True)
+    fb, ib = sr.dct_bound(x), sr.dct_bound(x, inverse=True)
+    ef = np.abs(fwd.cpu().numpy() - dctn(x, axes=(1, 2), norm="ortho"))
+    ei = np.abs(inv.cpu().numpy() - idctn(x, axes=(1, 2), norm="ortho"))
+    er = np.abs(back.cpu().numpy() - x)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        print(f"{H}x{W}: forward {np.nanmax(ef / fb):.3f}, inverse {np.nanmax(ei / ib):.3f}, round trip {np.nanmax(er / fb):.3f} of the bound")
+    assert (ef <= fb).all() and (ei <= ib).all()
+    assert (er <= fb).all()
+    for p in range(3):                                                      # a plane alone and inside the batch
+        assert torch.equal(smooth.dct2(xd[p:p + 1])[0], fwd[p]) and torch.equal(smooth.dct2(xd[p], inverse=True), inv[p])
+
+
+@pytest.mark.parametrize("H,W", [(5, 7), (65, 130)])
+def test_dct2_writes_nothing_outside_its_output(H, W, dev):
+    lib = _lib.load()
+    x = _planes(2, H, W, 7)
+    want = smooth.dct2(torch.from_numpy(x).to(dev))
+    xin = guarded((2, H, W), torch.float64, dev)
+    out = guarded((2, H, W), torch.float64, dev)
+    xin.copy_(torch.from_numpy(x))
+    nbytes = lib.pivlfn_dct2_workspace_bytes(2, H, W)
+    ws = guarded((nbytes // 8,), torch.float64, dev)                       # dirty: the guards' NaN pattern fills the payload too
+    assert lib.pivlfn_dct2(xin.data_ptr(), out.data_ptr(), 2, H, W, 0, ws.data_ptr(), nbytes, _lib.stream_ptr(dev)) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(out, want)
+    for t, name in ((xin, "x"), (out, "out"), (ws, "workspace")):
+        check_guards(t, name)
+    assert torch.equal(xin.cpu(), torch.from_numpy(x))
+
+
+# ---- 2. the solve against the dense operator ---------------------------------------------------------------------------------------------
+CASES = [(24, 20, 1), (33, 17, 2)]
+
+
+@pytest.fixture(scope="module")
+def fields():
+    return {(H, W): sr.solve_case(H, W, seed) for H, W, seed in CASES}
+
+
+def _check_solve(res, flow, w, s, what):
+    z = res.z.cpu().numpy()
+    assert res.converged.all(), (what, res.state, res.residual)
+    A, lmin = sr.operator(w, s), sr.lambda_min(w, s)
+    for c in range(2):
+        y = flow[c].astype(np.float64)
+        b = sr.rhs(w, y).ravel()
+        r = b - A @ z[0, c].ravel()
+        direct = sr.solve_direct(w, y, s)
+        _, its, _, _ = sr.pcg(w, y, s, TOL)
+        err, bound = np.linalg.norm(z[0, c] - direct), 2.0 * np.linalg.norm(r) / lmin
+        print(f"{what} c={c}: {int(res.iterations[0, c])} iterations (numpy {its}), |r|/|b| = {np.linalg.norm(r) / np.linalg.norm(b):.2e}, "
+              f"error {err:.2e} of bound {bound:.2e}")
+        assert np.linalg.norm(r) <= 2.0 * TOL * np.linalg.norm(b)
+        assert err <= bound
+        assert int(res.iterations[0, c]) <= 2 * its
+
+
+@pytest.mark.parametrize("s", [0.05, 1.0, 50.0])
+@pytest.mark.parametrize("H,W,seed", CASES)
+def test_solve_against_the_dense_operator(H, W, seed, s, fields, dev):
+    flow, mask = fields[(H, W)]
+    res = smooth.smooth_flow(torch.from_numpy(flow[None]).to(dev), s=s, mask=torch.from_numpy(mask[None]).to(dev), tol=TOL)
+    _check_solve(res, flow, sr.weights_of(flow, None, mask), s, f"{H}x{W} s={s}")
+    assert torch.equal(res.filled[0].cpu(), torch.from_numpy(mask != 0))
+    assert torch.equal(res.flow, res.z.to(torch.float32))
+
+
+def test_solve_with_fractional_weights(fields, dev):
+    flow, mask = fields[(24, 20)]
+    wts = np.random.default_rng(5).uniform(0.05, 1.0, mask.shape).astype(np.float32)
+    res = smooth.smooth_flow(torch.from_numpy(flow[None]).to(dev), s=1.0, weights=torch.from_numpy(wts[None]).to(dev),
+                             mask=torch.from_numpy(mask[None]).to(dev), tol=TOL)
+    _check_solve(res, flow, sr.weights_of(flow, wts, mask), 1.0, "24x20 fractional weights")
+
+
+# ---- 3. no gaps, unit weights ------------------------------------------------------------------------------------------------------------
+def test_without_gaps_the_start_is_the_solution(fields, dev):
+    flow, _ = fields[(33, 17)]
+    s = 3.0
+    res = smooth.smooth_flow(torch.from_numpy(flow[None]).to(dev), s=s, tol=TOL)
+    assert (res.iterations == 0).all() and res.converged.all() and (res.state == smooth.CONVERGED).all()
+    assert not res.filled.any()
+    y = flow.astype(np.float64)
+    spec = dctn(y, axes=(1, 2), norm="ortho")
+    g = sr.gamma(33, 17, s)
+    want = idctn(g * spec, axes=(1, 2), norm="ortho")
+    # test 1's two bounds: the inverse's own on what it is given, and the forward's carried through Gamma and the inverse's tables
+    carried = np.abs(sr.dct_table(33)).T @ (g * sr.dct_bound(y)) @ np.abs(sr.dct_table(17))
+    err = np.abs(res.z[0].cpu().numpy() - want)
+    print(f"no gaps: {float((err / (sr.dct_bound(g * spec, inverse=True) + carried)).max()):.3f} of the bound")
+    assert (err <= sr.dct_bound(g * spec, inverse=True) + carried).all()
+
+
+# ---- 4. gaps are data-free ---------------------------------------------------------------------------------------------------------------
+def test_the_value_of_a_gap_is_never_read(fields, dev):
+    flow, mask = fields[(24, 20)]
+    m = torch.from_numpy(mask[None]).to(dev)
+    outs = []
+    for fill in (float("nan"), 1e10, 1e30, -3.0):
+        f = flow.copy()
+        f[:, mask != 0] = fill
+        outs.append(smooth.smooth_flow(torch.from_numpy(f[None]).to(dev), s=1.0, mask=m, tol=TOL))
+    for o in outs[1:]:
+        assert torch.equal(o.z, outs[0].z) and torch.equal(o.status, outs[0].status)
+    assert torch.isfinite(outs[0].z).all()
+    # the unknown rule alone marks the first three as gaps as well
+    f = flow.copy()
+    f[0, mask != 0] = np.nan
+    unmasked = smooth.smooth_flow(torch.from_numpy(f[None]).to(dev), s=1.0, tol=TOL)
+    assert torch.equal(unmasked.z, outs[0].z) and torch.equal(unmasked.filled[0].cpu(), torch.from_numpy(mask != 0))
+
+
+def test_a_constant_field_with_holes_stays_constant(fields, dev):
+    _, mask = fields[(24, 20)]
+    flow = np.full((2, 24, 20), -2.5, dtype=np.float32)
+    res = smooth.smooth_flow(torch.from_numpy(flow[None]).to(dev), s=1.0, mask=torch.from_numpy(mask[None]).to(dev), tol=TOL)
+    w = sr.weights_of(flow, None, mask)
+    A, lmin = sr.operator(w, 1.0), sr.lambda_min(w, 1.0)
+    for c in range(2):
+        z = res.z[0, c].cpu().numpy()
+        r = sr.rhs(w, flow[c].astype(np.float64)).ravel() - A @ z.ravel()
+        assert np.linalg.norm(z + 2.5) <= 2.0 * np.linalg.norm(r) / lmin + 1e-300
+    assert res.converged.all()
+
+
+def test_an_empty_frame_reads_back_unknown_and_leaves_its_neighbours_alone(fields, dev):
+    flow, mask = fields[(24, 20)]
+    flows = torch.from_numpy(np.stack([flow, flow[::-1].copy(), 2.0 * flow])).to(dev)
+    masks = torch.from_numpy(np.stack([mask, np.ones_like(mask), mask])).to(dev)
+    res = smooth.smooth_flow(flows, s=1.0, mask=masks, tol=TOL)
+    assert (res.state[1] == smooth.EMPTY).all() and (res.z[1] == 1e10).all() and (res.flow[1] == 1e10).all() and res.filled[1].all()
+    assert res.converged.all()
+    for k in (0, 2):
+        alone = smooth.smooth_flow(flows[k:k + 1], s=1.0, mask=masks[k:k + 1], tol=TOL)
+        assert torch.equal(alone.z[0], res.z[k]) and torch.equal(alone.status[0], res.status[k])
+
+
+# ---- 5. independence ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def batch(fields):
+    flow, mask = fields[(33, 17)]
+    rng = np.random.default_rng(11)
+    masks = np.stack([mask, (rng.random(mask.shape) < 0.3).astype(np.uint8), np.roll(mask, 5, axis=0)])
+    flows = np.stack([flow, 0.5 * flow[::-1], flow + 1.0]).astype(np.float32)
+    return flows, masks
+
+
+def test_a_frame_does_not_depend_on_its_batch(batch, dev):
+    flows, masks = torch.from_numpy(batch[0]).to(dev), torch.from_numpy(batch[1]).to(dev)
+    together = smooth.smooth_flow(flows, s=0.05, mask=masks, tol=TOL)
+    assert together.converged.all() and len(set(together.iterations.ravel().tolist())) > 1       # the systems do stop at different times
+    for k in range(3):
+        alone = smooth.smooth_flow(flows[k:k + 1], s=0.05, mask=masks[k:k + 1], tol=TOL)
+        assert torch.equal(alone.z[0], together.z[k]) and torch.equal(alone.status[0], together.status[k])
+        assert np.array_equal(alone.iterations[0], together.iterations[k])
+
+
+def test_how_the_iterations_are_cut_changes_no_bit(batch, dev):
+    flows, masks = torch.from_numpy(batch[0]).to(dev), torch.from_numpy(batch[1]).to(dev)
+    want = smooth.smooth_flow(flows, s=0.05, mask=masks, tol=TOL, max_iter=60, sync_every=None)
+    for every in (1, 7):
+        got = smooth.smooth_flow(flows, s=0.05, mask=masks, tol=TOL, max_iter=60, sync_every=every)
+        assert torch.equal(got.z, want.z) and torch.equal(got.status, want.status), every
+    # the ABI: 5 + 5 + ... against one call of 60
+    lib, st = _lib.load(), _lib.stream_ptr(dev)
+    B, H, W = 3, 33, 17
+    nbytes = lib.pivlfn_smooth_workspace_bytes(B, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    z, status = torch.empty_like(want.z), torch.empty_like(want.status)
+    assert lib.pivlfn_smooth_setup(flows.data_ptr(), None, masks.data_ptr(), B, H, W, 0.05, ws.data_ptr(), nbytes, st) == 0
+    for _ in range(12):
+        assert lib.pivlfn_smooth_pcg(ws.data_ptr(), nbytes, B, H, W, 0.05, TOL, 5, st) == 0
+    assert lib.pivlfn_smooth_read(ws.data_ptr(), nbytes, B, H, W, z.data_ptr(), None, None, status.data_ptr(), st) == 0
+    assert torch.equal(z, want.z) and torch.equal(status, want.status)
+
+
+def test_u_and_v_swapped_give_swapped_outputs(batch, dev):
+    flows, masks = torch.from_numpy(batch[0][:1]).to(dev), torch.from_numpy(batch[1][:1]).to(dev)
+    a = smooth.smooth_flow(flows, s=1.0, mask=masks, tol=TOL)
+    b = smooth.smooth_flow(flows.flip(1).contiguous(), s=1.0, mask=masks, tol=TOL)
+    assert torch.equal(a.z.flip(1), b.z) and torch.equal(a.status.flip(1), b.status)
+
+
+def test_a_capped_frame_is_reported_unconverged(batch, dev):
+    flows, masks = torch.from_numpy(batch[0][:1]).to(dev), torch.from_numpy(batch[1][:1]).to(dev)
+    res = smooth.smooth_flow(flows, s=0.05, mask=masks, tol=TOL, max_iter=2)
+    assert not res.converged.any() and (res.iterations == 2).all() and (res.state == smooth.RUNNING).all()
+    assert res.summary()["unconverged"] == 1
+
+
+# ---- 6. stream and capture ---------------------------------------------------------------------------------------------------------------
+def test_a_side_stream_gives_the_same_bits(batch, dev):
+    flows, masks = torch.from_numpy(batch[0]).to(dev), torch.from_numpy(batch[1]).to(dev)
+    x = torch.from_numpy(_planes(2, 65, 130, 3)).to(dev)
+    want, want_dct = smooth.smooth_flow(flows, s=1.0, mask=masks, tol=TOL), smooth.dct2(x)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(dev)
+    with torch.cuda.stream(side):
+        got, got_dct = smooth.smooth_flow(flows, s=1.0, mask=masks, tol=TOL), smooth.dct2(x)
+    side.synchronize()
+    assert torch.equal(got.z, want.z) and torch.equal(got.status, want.status) and torch.equal(got_dct, want_dct)
+
+
+def test_dct2_and_one_pcg_call_can_be_captured(batch, dev):
+    lib = _lib.load()
+    flows, masks = torch.from_numpy(batch[0]).to(dev), torch.from_numpy(batch[1]).to(dev)
+    B, H, W = 3, 33, 17
+    x = torch.from_numpy(_planes(2, H, W, 4)).to(dev)
+    want_dct = smooth.dct2(x)
+    want = smooth.smooth_flow(flows, s=1.0, mask=masks, tol=TOL, max_iter=4, sync_every=None)
+    nbytes, dbytes = lib.pivlfn_smooth_workspace_bytes(B, H, W), lib.pivlfn_dct2_workspace_bytes(2, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dws = torch.empty(dbytes, dtype=torch.uint8, device=dev)
+    out, z, status = torch.empty_like(x), torch.empty_like(want.z), torch.empty_like(want.status)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(dev)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            st = _lib.stream_ptr(dev)
+            rcs = [lib.pivlfn_dct2(x.data_ptr(), out.data_ptr(), 2, H, W, 0, dws.data_ptr(), dbytes, st),
+                   lib.pivlfn_smooth_pcg(ws.data_ptr(), nbytes, B, H, W, 1.0, TOL, 4, st),
+                   lib.pivlfn_smooth_read(ws.data_ptr(), nbytes, B, H, W, z.data_ptr(), None, None, status.data_ptr(), st)]
+        assert rcs == [0, 0, 0], lib.pivlfn_last_error()
+        for _ in range(2):                                                  # the setup is eager: each replay iterates a fresh workspace
+            out.zero_()
+            assert lib.pivlfn_smooth_setup(flows.data_ptr(), None, masks.data_ptr(), B, H, W, 1.0, ws.data_ptr(), nbytes,
+                                           _lib.stream_ptr(dev)) == 0
+            graph.replay()
+            side.synchronize()
+            assert torch.equal(out, want_dct) and torch.equal(z, want.z) and torch.equal(status, want.status)
+
+
+# ---- 7. run.py -----------------------------------------------------------------------------------------------------------------------------
+VALIDATE = ["--validate-radius", "2", "--validate-eps", "0.01", "--validate-thresh", "0.5"]
+
+
+def test_run_py_smooth(tmp_path, dev):
+    import PIL.Image
+    import pivlfn
+    import run as runpy
+    from pivlfn import synth
+    from pivlfn import validate as V
+    from pivlfn.pipeline import read_image_u8, u8_to_input
+    jj, ii = torch.meshgrid(torch.arange(64.0), torch.arange(64.0), indexing="ij")
+    truth = torch.stack([torch.stack([2.0 * torch.sin(jj / (8.0 + k)), 1.5 * torch.cos(ii / (9.0 + k))]) for k in range(3)]).to(dev)
+    img1, img2, _ = pivlfn.ParticleImageGen(seed=40, device=dev).create_pair_from_flow(truth.contiguous())
+    seq = tmp_path / "seq"
+    seq.mkdir()
+    for k in range(3):
+        PIL.Image.fromarray(img1[k].cpu().numpy()).save(str(seq / f"p{k}_img1.png"))
+        PIL.Image.fromarray(img2[k].cpu().numpy()).save(str(seq / f"p{k}_img2.png"))
+    net = pivlfn.Network(model="piv", params=synth.generate_weights("piv", 0)).to(dev).eval()
+    a = torch.from_numpy(np.stack([read_image_u8(str(seq / f"p{k}_img1.png")) for k in range(3)])).to(dev)
+    b = torch.from_numpy(np.stack([read_image_u8(str(seq / f"p{k}_img2.png")) for k in range(3)])).to(dev)
+    est = torch.cat([pivlfn.estimate(net, u8_to_input(a[lo:hi]), u8_to_input(b[lo:hi]), tensor=True) for lo, hi in ((0, 2), (2, 3))])
+    params = dict(radius=2, spacing=1, eps=0.01, thresh=0.5)
+    masked = V.validate_flow(est, mode="mask", **params)
+    assert int((masked.flag != 0).sum()) > 0
+
+    def run(out, flags):
+        assert runpy.main(["--model", "piv", "-i", str(seq), "-p", "--batch", "2", "-o", str(out)] + flags) == 3
+        save = out / "piv-synthetic" / "seq"
+        return save, [read_flow(str(save / "flow" / f"p{k}_out.flo")) for k in range(3)]
+
+    save, got = run(tmp_path / "smooth", ["--validate", "mask", "--smooth", "8"] + VALIDATE)
+    want = torch.cat([smooth.smooth_flow(est[lo:hi], wavelength=8.0, mask=masked.flag[lo:hi]).flow for lo, hi in ((0, 2), (2, 3))])
+    doc = json.load(open(save / "smooth.json"))
+    assert doc["unconverged"] == 0 and len(doc["pairs"]) == 3 and doc["wavelength"] == 8.0 and doc["validation"] == "mask"
+    filled = (masked.flag != 0).flatten(1).sum(1).tolist()
+    for k, (name, row) in enumerate(doc["pairs"].items()):
+        assert row["converged"] and row["filled"] == filled[k] and f"p{k}" in name, (name, row)
+        assert np.abs(got[k]).max() <= 1e9
+        assert np.array_equal(got[k], want[k].permute(1, 2, 0).cpu().numpy())
+    assert "smooth: 8.0\n" in list(open(save / "args.txt"))
+
+    # without --smooth: what the files were before the flag existed
+    save, got = run(tmp_path / "plain", ["--validate", "mask"] + VALIDATE)
+    for k in range(3):
+        assert np.array_equal(got[k], masked.flow[k].permute(1, 2, 0).cpu().numpy())
+    lines = list(open(save / "args.txt"))
+    assert not [ln for ln in lines if ln.startswith("smooth")] and not os.path.exists(save / "smooth.json")
+    ref = runpy.parser.parse_args(["--model", "piv", "-i", str(seq), "-p", "--batch", "2", "-o", str(tmp_path / "plain"), "--validate", "mask"]
+                                  + VALIDATE)
+    assert lines == [f"{k}: {v}\n" for k, v in sorted(vars(ref).items())
+                     if k not in runpy.PREP_FLAGS + runpy.TRUTH_FLAGS + runpy.VIZ_FLAGS]
