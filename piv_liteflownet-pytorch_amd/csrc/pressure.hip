@@ -10,13 +10,8 @@
 // writes recB; the second reads recB and writes recA; one thread of the frame's first workgroup writes), and so does the search direction
 // d, whose new value a neighbouring workgroup needs while the old one is still being read.
 //
-// The tree of the contract over the N = h*w leaves of a frame: a thread owns four consecutive leaves (levels 0, 1), the six levels above
-// cross the lanes of a wave (partner lane ^ 1 .. ^ 32; an addition commutes, so both lanes hold the node), two more cross the four waves
-// in LDS: a chunk of 1024 leaves.  A workgroup walks `chunks` consecutive chunks (1 up to 2^21 nodes, a power of two beyond) and combines
-// their roots with a binary counter, which is the tree's order again, into ONE partial; a frame has at most 2048 partials, and each
-// workgroup of the next launch finishes the tree over them in LDS by itself.  Padding is +0.0 and x + (+0.0) = x for every x but -0.0;
-// the leaves r*z and r*r are never negative zero, and of sigma = T(d*q) only `sigma > 0` and rho/sigma for such a sigma are used, so
-// levels that add padding above a root change no bit of any result.
+// The tree T(.) of the contract, the walk of a workgroup over its tile of nodes and the record of a frame are cg_shared.h, shared with
+// smooth.hip.
 //
 // What an iteration moves per node: the first kernel reads z and d (the four neighbours of each from cache) and the adjacency byte and
 // writes d and q; the second reads d, q, x, r and the byte and writes x, r, z: 11 doubles and 2 bytes, 90 bytes.
@@ -27,36 +22,12 @@
 // last d is never formed.
 #include <cmath>
 #include "launch_checks.h"
+#include "cg_shared.h"
 
 namespace pivlfn {
 
-constexpr int PR_THREADS = 256, PR_OWN = 4, PR_CHUNK = PR_THREADS * PR_OWN, PR_MAX_PART = 2048;
-constexpr int PR_FRESH = 0, PR_PENDING = 1, PR_MID = 2;    // what the record and the partials hold: setup's, a half-finished step 5, d*q
-
-struct PrRec {                                 // 64 bytes per frame
-    double rho, rr, bb;
-    int state, iters, phase, dsel;             // dsel: which of the two d buffers holds the current direction
-    double unused[3];
-};
-
-// field by field, so that a record lives in registers and not in a scratch copy
-__device__ __forceinline__ PrRec pr_load(const PrRec *src)
-{
-    PrRec r;
-    r.rho = src->rho, r.rr = src->rr, r.bb = src->bb;
-    r.state = src->state, r.iters = src->iters, r.phase = src->phase, r.dsel = src->dsel;
-    r.unused[0] = r.unused[1] = r.unused[2] = 0.0;
-    return r;
-}
-
-__device__ __forceinline__ void pr_store(PrRec *dst, const PrRec &r)
-{
-    dst->rho = r.rho, dst->rr = r.rr, dst->bb = r.bb;
-    dst->state = r.state, dst->iters = r.iters, dst->phase = r.phase, dst->dsel = r.dsel;
-}
-
 struct PrWs {
-    PrRec *recA, *recB;                        // [F]
+    CgRec *recA, *recB;                        // [F]
     double *prz, *prr, *pdq;                   // [F][NB] block partials of r*z, r*r, d*q
     double *b, *x, *r, *z, *d[2], *q;          // [F][N]
     unsigned char *adj;                        // [F][N]: bit 0 left, 1 right, 2 up, 3 down edge active; bit 4 the node is valid
@@ -74,34 +45,30 @@ static PrLayout pr_layout(void *base, int F, int h, int w)
 {
     PrLayout L;
     const size_t N = (size_t)h * w;
-    size_t P2 = 1;
-    while (P2 < N) P2 <<= 1;
-    const size_t chunks = P2 > (size_t)PR_CHUNK * PR_MAX_PART ? P2 / ((size_t)PR_CHUNK * PR_MAX_PART) : 1;
-    const size_t tile = chunks * PR_CHUNK, NB = (N + tile - 1) / tile;
-    unsigned char *p = static_cast<unsigned char *>(base);
-    size_t at = 0;
-    auto take = [&](size_t bytes) { size_t o = at; at += (bytes + 7) & ~(size_t)7; return o; };
-    L.ws.recA = reinterpret_cast<PrRec *>(p + take(sizeof(PrRec) * F));
-    L.ws.recB = reinterpret_cast<PrRec *>(p + take(sizeof(PrRec) * F));
-    L.ws.prz = reinterpret_cast<double *>(p + take(8 * NB * F));
-    L.ws.prr = reinterpret_cast<double *>(p + take(8 * NB * F));
-    L.ws.pdq = reinterpret_cast<double *>(p + take(8 * NB * F));
-    L.off_b = take(8 * N * F);
-    L.ws.b = reinterpret_cast<double *>(p + L.off_b);
-    L.off_x = take(8 * N * F);
-    L.ws.x = reinterpret_cast<double *>(p + L.off_x);
-    L.ws.r = reinterpret_cast<double *>(p + take(8 * N * F));
-    L.ws.z = reinterpret_cast<double *>(p + take(8 * N * F));
-    L.ws.d[0] = reinterpret_cast<double *>(p + take(8 * N * F));
-    L.ws.d[1] = reinterpret_cast<double *>(p + take(8 * N * F));
-    L.ws.q = reinterpret_cast<double *>(p + take(8 * N * F));
-    L.off_adj = take(N * F);
-    L.ws.adj = p + L.off_adj;
+    const PrPlan plan = pr_plan(N);
+    const size_t NB = plan.NB;
+    WsCarver cv = {static_cast<unsigned char *>(base)};
+    L.ws.recA = cv.take<CgRec>(F);
+    L.ws.recB = cv.take<CgRec>(F);
+    L.ws.prz = cv.take<double>(NB * F);
+    L.ws.prr = cv.take<double>(NB * F);
+    L.ws.pdq = cv.take<double>(NB * F);
+    L.off_b = cv.at;
+    L.ws.b = cv.take<double>(N * F);
+    L.off_x = cv.at;
+    L.ws.x = cv.take<double>(N * F);
+    L.ws.r = cv.take<double>(N * F);
+    L.ws.z = cv.take<double>(N * F);
+    L.ws.d[0] = cv.take<double>(N * F);
+    L.ws.d[1] = cv.take<double>(N * F);
+    L.ws.q = cv.take<double>(N * F);
+    L.off_adj = cv.at;
+    L.ws.adj = cv.take<unsigned char>(N * F);
     L.ws.N = (unsigned)N;
     L.ws.w = w;
-    L.ws.chunks = (int)chunks;
-    L.ws.NB = (int)NB;
-    L.bytes = at;
+    L.ws.chunks = plan.chunks;
+    L.ws.NB = plan.NB;
+    L.bytes = cv.at;
     return L;
 }
 
@@ -114,70 +81,6 @@ size_t pressure_workspace_offset(int F, int h, int w, int what)
     if (!pr_shape_ok(F, h, w)) return 0;
     const PrLayout L = pr_layout(nullptr, F, h, w);
     return what == PIVLFN_PRESSURE_WS_B ? L.off_b : what == PIVLFN_PRESSURE_WS_X ? L.off_x : what == PIVLFN_PRESSURE_WS_ADJ ? L.off_adj : 0;
-}
-
-// ---- the tree ---------------------------------------------------------------------------------------------------------------------------
-// v[k]: the sum of a thread's four leaves, as (l0 + l1) + (l2 + l3).  Afterwards every thread holds the root of the workgroup's 1024
-// leaves.  Called by whole workgroups; sw is [K][4].
-template <int K>
-__device__ __forceinline__ void pr_chunk_root(double (&v)[K], double (*sw)[4])
-{
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1)
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] = v[k] + __shfl_xor(v[k], m);
-    __syncthreads();                                                           // the last chunk's sums have been read
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) sw[k][wave] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = (sw[k][0] + sw[k][1]) + (sw[k][2] + sw[k][3]);
-}
-
-// The binary counter over the chunks of a workgroup: up[k] waits for its right sibling at level k above a chunk's root.
-// Written without a break so that every index is static and the counter stays in registers.
-struct PrCounter {
-    double up[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    __device__ __forceinline__ double add(double root, int c)
-    {
-#pragma clang fp contract(off)
-        bool carry = true;                                                     // still climbing: every lower bit of c was set
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            const bool bit = (c >> k) & 1;
-            const double sum = up[k] + root;
-            up[k] = (carry && !bit) ? root : up[k];
-            root = (carry && bit) ? sum : root;
-            carry = carry && bit;
-        }
-        return root;                                                           // after the last of 2^n chunks: their root
-    }
-};
-
-// The roots of the trees over a frame's NB <= 2048 partials, K trees at once, in every thread: the partials are the leaves of one or two
-// chunks, reduced like the nodes' (the padding above a root of fewer than 1024 partials adds +0.0, which changes no result -- see the
-// head of the file).  sw is [K][4].
-template <int K>
-__device__ __forceinline__ void pr_finish(const double *const (&part)[K], int NB, double (*sw)[4], double (&out)[K])
-{
-#pragma clang fp contract(off)
-    for (int c = 0; c * PR_CHUNK < NB; ++c) {
-        const int base = c * PR_CHUNK + (int)threadIdx.x * PR_OWN;
-        double v[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double l[PR_OWN];
-#pragma unroll
-            for (int j = 0; j < PR_OWN; ++j) l[j] = base + j < NB ? part[k][base + j] : 0.0;
-            v[k] = (l[0] + l[1]) + (l[2] + l[3]);
-        }
-        pr_chunk_root<K>(v, sw);
-#pragma unroll
-        for (int k = 0; k < K; ++k) out[k] = c ? out[k] + v[k] : v[k];
-    }
 }
 
 __device__ __forceinline__ double pr_deg(unsigned a) { return (double)__popc(a & 15u); }
@@ -223,8 +126,9 @@ __global__ __launch_bounds__(PR_THREADS) void pressure_gradient_kernel(const flo
 }
 
 // ---- setup ------------------------------------------------------------------------------------------------------------------------------
-// blockIdx.x = frame * NB + the workgroup's tile of the frame
-__global__ __launch_bounds__(PR_THREADS) void pressure_setup_kernel(const double *g, const unsigned char *valid, double s, const PrWs ws)
+// blockIdx.x = frame * NB + the workgroup's tile of the frame.  At most four waves a SIMD: the kernel's 96 registers would admit a fifth,
+// and with five workgroups a CU 2 x 1024 x 1024 nodes take 108 us instead of 102 (measured).
+__global__ __launch_bounds__(PR_THREADS) __attribute__((amdgpu_waves_per_eu(1, 4))) void pressure_setup_kernel(const double *g, const unsigned char *valid, double s, const PrWs ws)
 {
 #pragma clang fp contract(off)
     __shared__ double sw[2][4];
@@ -233,47 +137,33 @@ __global__ __launch_bounds__(PR_THREADS) void pressure_setup_kernel(const double
     const size_t fo = (size_t)f * N;
     const double *gx = g + 2 * fo, *gy = gx + N;
     const unsigned char *va = valid + fo;
-    PrCounter crz, crr;
-    double root_rz = 0.0, root_rr = 0.0;
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-        double lrz[PR_OWN], lrr[PR_OWN];
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j) {
-            lrz[j] = lrr[j] = 0.0;
-            if (base + j < N) {
-                const unsigned i = (unsigned)(base + j);
-                const unsigned col = i % (unsigned)w;
-                const bool me = va[i] != 0;
-                const bool eL = me && col > 0 && va[i - 1] != 0, eR = me && col + 1 < (unsigned)w && va[i + 1] != 0;
-                const bool eU = me && i >= (unsigned)w && va[i - w] != 0, eD = me && i + (unsigned)w < N && va[i + w] != 0;
-                const unsigned a = (eL ? 1u : 0u) | (eR ? 2u : 0u) | (eU ? 4u : 0u) | (eD ? 8u : 0u);
-                const double L = eL ? (0.5 * (gx[i - 1] + gx[i])) * s : 0.0;
-                const double R = eR ? -((0.5 * (gx[i] + gx[i + 1])) * s) : 0.0;
-                const double U = eU ? (0.5 * (gy[i - w] + gy[i])) * s : 0.0;
-                const double D = eD ? -((0.5 * (gy[i] + gy[i + w])) * s) : 0.0;
-                const double b = ((L + R) + U) + D;
-                const double z = a ? b / pr_deg(a) : 0.0;
-                ws.adj[fo + i] = (unsigned char)(a | (me ? 16u : 0u));
-                ws.b[fo + i] = b;
-                ws.x[fo + i] = 0.0;
-                ws.r[fo + i] = b;
-                ws.z[fo + i] = z;
-                lrz[j] = b * z;
-                lrr[j] = b * b;
-            }
-        }
-        double v[2] = {(lrz[0] + lrz[1]) + (lrz[2] + lrz[3]), (lrr[0] + lrr[1]) + (lrr[2] + lrr[3])};
-        pr_chunk_root<2>(v, sw);
-        root_rz = crz.add(v[0], c);
-        root_rr = crr.add(v[1], c);
-    }
+    double root[2];                                                            // r*z, r*r
+    pr_tile_roots<2>(ws.chunks, N, blk, sw, root, [&](unsigned i, double (&l)[2]) {
+        const unsigned col = i % (unsigned)w;
+        const bool me = va[i] != 0;
+        const bool eL = me && col > 0 && va[i - 1] != 0, eR = me && col + 1 < (unsigned)w && va[i + 1] != 0;
+        const bool eU = me && i >= (unsigned)w && va[i - w] != 0, eD = me && i + (unsigned)w < N && va[i + w] != 0;
+        const unsigned a = (eL ? 1u : 0u) | (eR ? 2u : 0u) | (eU ? 4u : 0u) | (eD ? 8u : 0u);
+        const double L = eL ? (0.5 * (gx[i - 1] + gx[i])) * s : 0.0;
+        const double R = eR ? -((0.5 * (gx[i] + gx[i + 1])) * s) : 0.0;
+        const double U = eU ? (0.5 * (gy[i - w] + gy[i])) * s : 0.0;
+        const double D = eD ? -((0.5 * (gy[i] + gy[i + w])) * s) : 0.0;
+        const double b = ((L + R) + U) + D;
+        const double z = a ? b / pr_deg(a) : 0.0;
+        ws.adj[fo + i] = (unsigned char)(a | (me ? 16u : 0u));
+        ws.b[fo + i] = b;
+        ws.x[fo + i] = 0.0;
+        ws.r[fo + i] = b;
+        ws.z[fo + i] = z;
+        l[0] = b * z;
+        l[1] = b * b;
+    });
     if (tid == 0) {
-        ws.prz[(size_t)f * ws.NB + blk] = root_rz;
-        ws.prr[(size_t)f * ws.NB + blk] = root_rr;
+        ws.prz[(size_t)f * ws.NB + blk] = root[0];
+        ws.prr[(size_t)f * ws.NB + blk] = root[1];
         if (blk == 0) {
-            PrRec rec = {0.0, 0.0, 0.0, PIVLFN_PRESSURE_RUNNING, 0, PR_FRESH, 0, {0.0, 0.0, 0.0}};
-            pr_store(ws.recA + f, rec);
+            CgRec rec = {0.0, 0.0, 0.0, PIVLFN_PRESSURE_RUNNING, 0, CG_FRESH, 0, {0.0, 0.0, 0.0}};
+            cg_store(ws.recA + f, rec);
         }
     }
 }
@@ -286,17 +176,14 @@ __global__ __launch_bounds__(PR_THREADS) void pressure_cg_dq_kernel(const PrWs w
     __shared__ double sw[2][4];
     const unsigned N = ws.N, f = blockIdx.x / (unsigned)ws.NB, blk = blockIdx.x - f * (unsigned)ws.NB;
     const int tid = threadIdx.x, w = ws.w;
-    const PrRec in = pr_load(ws.recA + f);
+    const CgRec in = cg_load(ws.recA + f);
     const bool writer = blk == 0 && tid == 0;
-    if (in.state != PIVLFN_PRESSURE_RUNNING) {                                 // frozen: the record passes through, nothing else moves
-        if (writer) pr_store(ws.recB + f, in);
-        return;
-    }
+    if (cg_frozen(in, ws.recB + f, writer)) return;
     const double *const parts[2] = {ws.prz + (size_t)f * ws.NB, ws.prr + (size_t)f * ws.NB};
     double top[2];
     pr_finish<2>(parts, ws.NB, sw, top);
-    PrRec out = in;
-    const bool fresh = in.phase == PR_FRESH;
+    CgRec out = in;
+    const bool fresh = in.phase == CG_FRESH;
     double beta = 0.0;
     out.rho = top[0];
     out.rr = top[1];
@@ -306,10 +193,10 @@ __global__ __launch_bounds__(PR_THREADS) void pressure_cg_dq_kernel(const PrWs w
         beta = top[0] / in.rho;
         out.iters = in.iters + 1;
     }
-    out.phase = PR_MID;
+    out.phase = CG_MID;
     if (out.bb > 0.0 && out.rr <= (tol * tol) * out.bb) {                      // b = 0 is left to the breakdown rule
         out.state = PIVLFN_PRESSURE_CONVERGED;
-        if (writer) pr_store(ws.recB + f, out);
+        if (writer) cg_store(ws.recB + f, out);
         return;
     }
     const size_t fo = (size_t)f * N;
@@ -318,36 +205,24 @@ __global__ __launch_bounds__(PR_THREADS) void pressure_cg_dq_kernel(const PrWs w
     double *dnew = (odd ? ws.d[0] : ws.d[1]) + fo, *q = ws.q + fo;
     const unsigned char *adj = ws.adj + fo;
     out.dsel = (in.dsel & 1) ^ 1;
-    PrCounter cnt;
-    double root = 0.0;
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-        double leaf[PR_OWN];
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j) {
-            leaf[j] = 0.0;
-            if (base + j < N) {
-                const unsigned i = (unsigned)(base + j), a = adj[i];
-                // the direction of a node, its own or a neighbour's: an edge is active only where the neighbour exists
+    double root[1];                                                            // d*q
+    pr_tile_roots<1>(ws.chunks, N, blk, sw, root, [&](unsigned i, double (&l)[1]) {
+        const unsigned a = adj[i];
+        // the direction of a node, its own or a neighbour's: an edge is active only where the neighbour exists
 #define PR_D(k) (fresh ? z[k] : z[k] + beta * dold[k])
-                const double dc = PR_D(i);
-                // (the bounds hold for every byte setup writes; they keep a workspace that never saw setup inside itself)
-                const double dl = ((a & 1u) && i > 0) ? PR_D(i - 1) : 0.0, dr = ((a & 2u) && i + 1 < N) ? PR_D(i + 1) : 0.0;
-                const double du = ((a & 4u) && i >= (unsigned)w) ? PR_D(i - w) : 0.0, dd = ((a & 8u) && i + (unsigned)w < N) ? PR_D(i + w) : 0.0;
+        const double dc = PR_D(i);
+        // (the bounds hold for every byte setup writes; they keep a workspace that never saw setup inside itself)
+        const double dl = ((a & 1u) && i > 0) ? PR_D(i - 1) : 0.0, dr = ((a & 2u) && i + 1 < N) ? PR_D(i + 1) : 0.0;
+        const double du = ((a & 4u) && i >= (unsigned)w) ? PR_D(i - w) : 0.0, dd = ((a & 8u) && i + (unsigned)w < N) ? PR_D(i + w) : 0.0;
 #undef PR_D
-                const double qv = pr_deg(a) * dc - (((dl + dr) + du) + dd);
-                dnew[i] = dc;
-                q[i] = qv;
-                leaf[j] = dc * qv;
-            }
-        }
-        double v[1] = {(leaf[0] + leaf[1]) + (leaf[2] + leaf[3])};
-        pr_chunk_root<1>(v, sw);
-        root = cnt.add(v[0], c);
-    }
+        const double qv = pr_deg(a) * dc - (((dl + dr) + du) + dd);
+        dnew[i] = dc;
+        q[i] = qv;
+        l[0] = dc * qv;
+    });
     if (tid == 0) {
-        ws.pdq[(size_t)f * ws.NB + blk] = root;
-        if (blk == 0) pr_store(ws.recB + f, out);
+        ws.pdq[(size_t)f * ws.NB + blk] = root[0];
+        if (blk == 0) cg_store(ws.recB + f, out);
     }
 }
 
@@ -358,56 +233,31 @@ __global__ __launch_bounds__(PR_THREADS) void pressure_cg_xr_kernel(const PrWs w
     __shared__ double sw[2][4];
     const unsigned N = ws.N, f = blockIdx.x / (unsigned)ws.NB, blk = blockIdx.x - f * (unsigned)ws.NB;
     const int tid = threadIdx.x;
-    const PrRec in = pr_load(ws.recB + f);
+    const CgRec in = cg_load(ws.recB + f);
     const bool writer = blk == 0 && tid == 0;
-    if (in.state != PIVLFN_PRESSURE_RUNNING) {
-        if (writer) pr_store(ws.recA + f, in);
-        return;
-    }
-    const double *const parts[1] = {ws.pdq + (size_t)f * ws.NB};
-    double top[1];
-    pr_finish<1>(parts, ws.NB, sw, top);
-    const double sigma = top[0];
-    PrRec out = in;
-    if (!(sigma > 0.0)) {                                                      // NaN included
-        out.state = PIVLFN_PRESSURE_BREAKDOWN;
-        if (writer) pr_store(ws.recA + f, out);
-        return;
-    }
-    const double alpha = in.rho / sigma;
+    double alpha;
+    if (cg_frozen(in, ws.recA + f, writer) || !cg_alpha(in, ws.recA + f, writer, ws.pdq + (size_t)f * ws.NB, ws.NB, sw, alpha)) return;
     const size_t fo = (size_t)f * N;
     const double *d = ((in.dsel & 1) ? ws.d[1] : ws.d[0]) + fo, *q = ws.q + fo;
     double *x = ws.x + fo, *r = ws.r + fo, *z = ws.z + fo;
     const unsigned char *adj = ws.adj + fo;
-    PrCounter crz, crr;
-    double root_rz = 0.0, root_rr = 0.0;
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-        double lrz[PR_OWN], lrr[PR_OWN];
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j) {
-            lrz[j] = lrr[j] = 0.0;
-            if (base + j < N) {
-                const unsigned i = (unsigned)(base + j), a = adj[i] & 15u;
-                x[i] = x[i] + alpha * d[i];
-                const double rn = r[i] - alpha * q[i];
-                const double zn = a ? rn / pr_deg(a) : 0.0;
-                r[i] = rn;
-                z[i] = zn;
-                lrz[j] = rn * zn;
-                lrr[j] = rn * rn;
-            }
-        }
-        double v[2] = {(lrz[0] + lrz[1]) + (lrz[2] + lrz[3]), (lrr[0] + lrr[1]) + (lrr[2] + lrr[3])};
-        pr_chunk_root<2>(v, sw);
-        root_rz = crz.add(v[0], c);
-        root_rr = crr.add(v[1], c);
-    }
-    out.phase = PR_PENDING;
+    double root[2];                                                            // r*z, r*r
+    pr_tile_roots<2>(ws.chunks, N, blk, sw, root, [&](unsigned i, double (&l)[2]) {
+        const unsigned a = adj[i] & 15u;
+        x[i] = x[i] + alpha * d[i];
+        const double rn = r[i] - alpha * q[i];
+        const double zn = a ? rn / pr_deg(a) : 0.0;
+        r[i] = rn;
+        z[i] = zn;
+        l[0] = rn * zn;
+        l[1] = rn * rn;
+    });
+    CgRec out = in;
+    out.phase = CG_PENDING;
     if (tid == 0) {
-        ws.prz[(size_t)f * ws.NB + blk] = root_rz;
-        ws.prr[(size_t)f * ws.NB + blk] = root_rr;
-        if (blk == 0) pr_store(ws.recA + f, out);
+        ws.prz[(size_t)f * ws.NB + blk] = root[0];
+        ws.prr[(size_t)f * ws.NB + blk] = root[1];
+        if (blk == 0) cg_store(ws.recA + f, out);
     }
 }
 
@@ -421,33 +271,23 @@ __global__ __launch_bounds__(PR_THREADS) void pressure_read_kernel(const PrWs ws
     const int tid = threadIdx.x;
     const size_t fo = (size_t)f * N;
     if (blk == 0) {                                                            // the whole workgroup: pr_finish synchronises it
-        PrRec rec = pr_load(ws.recA + f);
+        CgRec rec = cg_load(ws.recA + f);
         if (rec.state == PIVLFN_PRESSURE_RUNNING) {
             const double *const parts[1] = {ws.prr + (size_t)f * ws.NB};
             double top[1];
             pr_finish<1>(parts, ws.NB, sw, top);
             rec.rr = top[0];
-            if (rec.phase == PR_FRESH) rec.bb = top[0];
+            if (rec.phase == CG_FRESH) rec.bb = top[0];
             else rec.iters += 1;
         }
-        if (tid == 0) {
-            status[4 * (size_t)f + 0] = (double)rec.state;
-            status[4 * (size_t)f + 1] = (double)rec.iters;
-            status[4 * (size_t)f + 2] = rec.rr;
-            status[4 * (size_t)f + 3] = rec.bb;
-        }
+        if (tid == 0) cg_write_status(status + 4 * (size_t)f, rec);
     }
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j)
-            if (base + j < N) {
-                const size_t i = fo + base + j;
-                const unsigned a = ws.adj[i];
-                p[i] = (a & 15u) ? ws.x[i] : __longlong_as_double(0x7ff8000000000000LL);
-                flag[i] = !(a & 16u) ? PIVLFN_PRESSURE_INVALID : !(a & 15u) ? PIVLFN_PRESSURE_ISOLATED : 0;
-            }
-    }
+    pr_tile_for_each(ws.chunks, N, blk, [&](size_t node) {
+        const size_t i = fo + node;
+        const unsigned a = ws.adj[i];
+        p[i] = (a & 15u) ? ws.x[i] : __longlong_as_double(0x7ff8000000000000LL);
+        flag[i] = !(a & 16u) ? PIVLFN_PRESSURE_INVALID : !(a & 15u) ? PIVLFN_PRESSURE_ISOLATED : 0;
+    });
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------

@@ -15,37 +15,18 @@
 // system ping-pongs between two copies, and so does the search direction.  A system is one component of one frame, 2f + c.  One
 // iteration is eight launches: direction and first Laplacian (recA -> recB), second Laplacian and d*q, the x / r update (recB -> recA),
 // the four matrix products of the preconditioner (skipped plane by plane for a system that is not running) and r*z.
+//
+// The tree T(.) of the contract, the walk of a workgroup over its tile of nodes and the record of a system are cg_shared.h, shared with
+// pressure.hip.
 #include <cmath>
 #include "launch_checks.h"
-#include "tree_reduce.h"
+#include "cg_shared.h"
 
 namespace pivlfn {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr int DC_BLK = 64, DC_KC = 32, DC_LD = DC_KC + 2, DC_THREADS = 256;
-constexpr int SM_FRESH = 0, SM_PENDING = 1, SM_MID = 2;    // what the record and the partials hold, as in pressure.hip
-
-struct SmRec {                                 // 64 bytes per system
-    double rho, rr, bb;
-    int state, iters, phase, dsel;
-    double unused[3];
-};
-
-__device__ __forceinline__ SmRec sm_load(const SmRec *src)
-{
-    SmRec r;
-    r.rho = src->rho, r.rr = src->rr, r.bb = src->bb;
-    r.state = src->state, r.iters = src->iters, r.phase = src->phase, r.dsel = src->dsel;
-    r.unused[0] = r.unused[1] = r.unused[2] = 0.0;
-    return r;
-}
-
-__device__ __forceinline__ void sm_store(SmRec *dst, const SmRec &r)
-{
-    dst->rho = r.rho, dst->rr = r.rr, dst->bb = r.bb;
-    dst->state = r.state, dst->iters = r.iters, dst->phase = r.phase, dst->dsel = r.dsel;
-}
 
 // ---- the DCT tables -----------------------------------------------------------------------------------------------------------------------
 struct DctTables { double *ch, *cw, *lh, *lw; };           // C_H [H][H], C_W [W][W], lambda_H [H], lambda_W [W]
@@ -105,7 +86,7 @@ struct MmParams {
     int a_kfast, b_kfast;                      // k is the operand's contiguous index in memory
     const double *lamM, *lamN;                 // not null: D *= 1 / (1 + s (lamM[m] + lamN[n])^2)
     double s;
-    const SmRec *rec;                          // not null: plane p is skipped unless rec[p] is running
+    const CgRec *rec;                          // not null: plane p is skipped unless rec[p] is running
 };
 
 __global__ __launch_bounds__(DC_THREADS) void dct_mm_kernel(const MmParams p)
@@ -186,7 +167,7 @@ __global__ __launch_bounds__(DC_THREADS) void dct_mm_kernel(const MmParams p)
 
 // The transform of P planes: in -> tmp -> out.  gamma: the forward transform's result is multiplied by Gamma (s is then read).
 static void dct_enqueue(const DctTables &tb, const double *in, double *tmp, double *out, int P, int H, int W, bool inverse, bool gamma, double s,
-                        const SmRec *rec, hipStream_t st)
+                        const CgRec *rec, hipStream_t st)
 {
     const long HW = (long)H * W;
     const dim3 grid((unsigned)cdiv(W, DC_BLK), (unsigned)cdiv(H, DC_BLK), (unsigned)P), block(DC_THREADS);
@@ -241,7 +222,7 @@ int launch_dct2(const double *x, double *out, int P, int H, int W, int inverse, 
 
 // ---- the solver's workspace -------------------------------------------------------------------------------------------------------------
 struct SmWs {
-    SmRec *recA, *recB;                        // [S], S = 2F systems
+    CgRec *recA, *recB;                        // [S], S = 2F systems
     double *prz, *prr, *pdq, *pbb, *pw;        // [S][NB] block partials of r*z, r*r, d*q, b*b;  [F][NB] of the weights
     DctTables tb;
     double *w;                                 // [F][N]
@@ -256,36 +237,32 @@ static SmLayout sm_layout(void *base, int F, int H, int W)
 {
     SmLayout L;
     const size_t N = (size_t)H * W, S = 2 * (size_t)F;
-    size_t P2 = 1;
-    while (P2 < N) P2 <<= 1;
-    const size_t chunks = P2 > (size_t)PR_CHUNK * PR_MAX_PART ? P2 / ((size_t)PR_CHUNK * PR_MAX_PART) : 1;
-    const size_t tile = chunks * PR_CHUNK, NB = (N + tile - 1) / tile;
-    unsigned char *p = static_cast<unsigned char *>(base);
-    size_t at = 0;
-    auto take = [&](size_t bytes) { size_t o = at; at += (bytes + 7) & ~(size_t)7; return reinterpret_cast<double *>(p + o); };
-    L.ws.recA = reinterpret_cast<SmRec *>(take(sizeof(SmRec) * S));
-    L.ws.recB = reinterpret_cast<SmRec *>(take(sizeof(SmRec) * S));
-    L.ws.prz = take(8 * NB * S);
-    L.ws.prr = take(8 * NB * S);
-    L.ws.pdq = take(8 * NB * S);
-    L.ws.pbb = take(8 * NB * S);
-    L.ws.pw = take(8 * NB * F);
-    L.ws.tb = dct_tables_at(take(8 * dct_table_doubles(H, W)), H, W);
-    L.ws.w = take(8 * N * F);
-    L.ws.b = take(8 * N * S);
-    L.ws.x = take(8 * N * S);
-    L.ws.r = take(8 * N * S);
-    L.ws.z = take(8 * N * S);
-    L.ws.d[0] = take(8 * N * S);
-    L.ws.d[1] = take(8 * N * S);
-    L.ws.t = take(8 * N * S);
-    L.ws.q = take(8 * N * S);
+    const PrPlan plan = pr_plan(N);
+    const size_t NB = plan.NB;
+    WsCarver cv = {static_cast<unsigned char *>(base)};
+    L.ws.recA = cv.take<CgRec>(S);
+    L.ws.recB = cv.take<CgRec>(S);
+    L.ws.prz = cv.take<double>(NB * S);
+    L.ws.prr = cv.take<double>(NB * S);
+    L.ws.pdq = cv.take<double>(NB * S);
+    L.ws.pbb = cv.take<double>(NB * S);
+    L.ws.pw = cv.take<double>(NB * F);
+    L.ws.tb = dct_tables_at(cv.take<double>(dct_table_doubles(H, W)), H, W);
+    L.ws.w = cv.take<double>(N * F);
+    L.ws.b = cv.take<double>(N * S);
+    L.ws.x = cv.take<double>(N * S);
+    L.ws.r = cv.take<double>(N * S);
+    L.ws.z = cv.take<double>(N * S);
+    L.ws.d[0] = cv.take<double>(N * S);
+    L.ws.d[1] = cv.take<double>(N * S);
+    L.ws.t = cv.take<double>(N * S);
+    L.ws.q = cv.take<double>(N * S);
     L.ws.N = (unsigned)N;
     L.ws.H = H;
     L.ws.W = W;
-    L.ws.chunks = (int)chunks;
-    L.ws.NB = (int)NB;
-    L.bytes = at;
+    L.ws.chunks = plan.chunks;
+    L.ws.NB = plan.NB;
+    L.bytes = cv.at;
     return L;
 }
 
@@ -320,39 +297,24 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_prep_kernel(const float *fl
     const int tid = threadIdx.x;
     const size_t fo = (size_t)f * N;
     const float *fu = flows + 2 * fo, *fv = fu + N;
-    PrCounter cw, cu, cv;
-    double root_w = 0.0, root_u = 0.0, root_v = 0.0;
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-        double lw[PR_OWN], lu[PR_OWN], lv[PR_OWN];
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j) {
-            lw[j] = lu[j] = lv[j] = 0.0;
-            if (base + j < N) {
-                const unsigned i = (unsigned)(base + j);
-                const float u = fu[i], v = fv[i];
-                const float wf = weights ? weights[fo + i] : 1.0f;
-                const bool pos = sm_known(u, v) && !(mask && mask[fo + i]) && wf > 0.0f && wf <= 3.402823466e38f;
-                const double wd = pos ? (double)wf : 0.0;
-                const double bu = pos ? wd * (double)u : 0.0, bv = pos ? wd * (double)v : 0.0;     // a weight-0 value enters no product
-                ws.w[fo + i] = wd;
-                ws.b[2 * fo + i] = bu;
-                ws.b[2 * fo + N + i] = bv;
-                lw[j] = wd;
-                lu[j] = bu * bu;
-                lv[j] = bv * bv;
-            }
-        }
-        double v[3] = {(lw[0] + lw[1]) + (lw[2] + lw[3]), (lu[0] + lu[1]) + (lu[2] + lu[3]), (lv[0] + lv[1]) + (lv[2] + lv[3])};
-        pr_chunk_root<3>(v, sw);
-        root_w = cw.add(v[0], c);
-        root_u = cu.add(v[1], c);
-        root_v = cv.add(v[2], c);
-    }
+    double root[3];                                                            // w, b*b of u, b*b of v
+    pr_tile_roots<3>(ws.chunks, N, blk, sw, root, [&](unsigned i, double (&l)[3]) {
+        const float u = fu[i], v = fv[i];
+        const float wf = weights ? weights[fo + i] : 1.0f;
+        const bool pos = sm_known(u, v) && !(mask && mask[fo + i]) && wf > 0.0f && wf <= 3.402823466e38f;
+        const double wd = pos ? (double)wf : 0.0;
+        const double bu = pos ? wd * (double)u : 0.0, bv = pos ? wd * (double)v : 0.0;             // a weight-0 value enters no product
+        ws.w[fo + i] = wd;
+        ws.b[2 * fo + i] = bu;
+        ws.b[2 * fo + N + i] = bv;
+        l[0] = wd;
+        l[1] = bu * bu;
+        l[2] = bv * bv;
+    });
     if (tid == 0) {
-        ws.pw[(size_t)f * ws.NB + blk] = root_w;
-        ws.pbb[(size_t)(2 * f) * ws.NB + blk] = root_u;
-        ws.pbb[(size_t)(2 * f + 1) * ws.NB + blk] = root_v;
+        ws.pw[(size_t)f * ws.NB + blk] = root[0];
+        ws.pbb[(size_t)(2 * f) * ws.NB + blk] = root[1];
+        ws.pbb[(size_t)(2 * f + 1) * ws.NB + blk] = root[2];
     }
 }
 
@@ -363,12 +325,7 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_lap_kernel(const SmWs ws)
     const double *x = ws.x + (size_t)sys * N;
     double *t = ws.t + (size_t)sys * N;
     auto val = [&](unsigned k) { return x[k]; };
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)threadIdx.x * PR_OWN;
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j)
-            if (base + j < N) t[base + j] = sm_lap(val, (unsigned)(base + j), ws.H, ws.W);
-    }
+    pr_tile_for_each(ws.chunks, N, blk, [&](size_t i) { t[i] = sm_lap(val, (unsigned)i, ws.H, ws.W); });
 }
 
 // r = b - (w*x + s*(D t)), the partials of r*r, and the first record of the system
@@ -381,33 +338,20 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_resid_kernel(const SmWs ws,
     const size_t so = (size_t)sys * N, fo = (size_t)(sys >> 1) * N;
     const double *t = ws.t + so;
     auto val = [&](unsigned k) { return t[k]; };
-    PrCounter cnt;
-    double root = 0.0;
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-        double leaf[PR_OWN];
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j) {
-            leaf[j] = 0.0;
-            if (base + j < N) {
-                const unsigned i = (unsigned)(base + j);
-                const double rn = ws.b[so + i] - (ws.w[fo + i] * ws.x[so + i] + s * sm_lap(val, i, ws.H, ws.W));
-                ws.r[so + i] = rn;
-                leaf[j] = rn * rn;
-            }
-        }
-        double v[1] = {(leaf[0] + leaf[1]) + (leaf[2] + leaf[3])};
-        pr_chunk_root<1>(v, sw);
-        root = cnt.add(v[0], c);
-    }
-    if (tid == 0) ws.prr[(size_t)sys * ws.NB + blk] = root;
+    double root[1];                                                            // r*r
+    pr_tile_roots<1>(ws.chunks, N, blk, sw, root, [&](unsigned i, double (&l)[1]) {
+        const double rn = ws.b[so + i] - (ws.w[fo + i] * ws.x[so + i] + s * sm_lap(val, i, ws.H, ws.W));
+        ws.r[so + i] = rn;
+        l[0] = rn * rn;
+    });
+    if (tid == 0) ws.prr[(size_t)sys * ws.NB + blk] = root[0];
     if (blk == 0) {                                                            // the whole workgroup: pr_finish synchronises it
         const double *const parts[2] = {ws.pw + (size_t)(sys >> 1) * ws.NB, ws.pbb + (size_t)sys * ws.NB};
         double top[2];
         pr_finish<2>(parts, ws.NB, sw, top);
         if (tid == 0) {
-            SmRec rec = {0.0, 0.0, top[1], top[0] > 0.0 ? PIVLFN_SMOOTH_RUNNING : PIVLFN_SMOOTH_EMPTY, 0, SM_FRESH, 0, {0.0, 0.0, 0.0}};
-            sm_store(ws.recA + sys, rec);
+            CgRec rec = {0.0, 0.0, top[1], top[0] > 0.0 ? PIVLFN_SMOOTH_RUNNING : PIVLFN_SMOOTH_EMPTY, 0, CG_FRESH, 0, {0.0, 0.0, 0.0}};
+            cg_store(ws.recA + sys, rec);
         }
     }
 }
@@ -421,18 +365,9 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_rz_kernel(const SmWs ws)
     const int tid = threadIdx.x;
     if (ws.recA[sys].state != PIVLFN_SMOOTH_RUNNING) return;
     const double *r = ws.r + (size_t)sys * N, *z = ws.z + (size_t)sys * N;
-    PrCounter cnt;
-    double root = 0.0;
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-        double leaf[PR_OWN];
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j) leaf[j] = base + j < N ? r[base + j] * z[base + j] : 0.0;
-        double v[1] = {(leaf[0] + leaf[1]) + (leaf[2] + leaf[3])};
-        pr_chunk_root<1>(v, sw);
-        root = cnt.add(v[0], c);
-    }
-    if (tid == 0) ws.prz[(size_t)sys * ws.NB + blk] = root;
+    double root[1];
+    pr_tile_roots<1>(ws.chunks, N, blk, sw, root, [&](size_t i, double (&l)[1]) { l[0] = r[i] * z[i]; });
+    if (tid == 0) ws.prz[(size_t)sys * ws.NB + blk] = root[0];
 }
 
 // ---- one iteration ------------------------------------------------------------------------------------------------------------------------
@@ -443,17 +378,14 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_pcg_dir_kernel(const SmWs w
     __shared__ double sw[2][4];
     const unsigned N = ws.N, sys = blockIdx.x / (unsigned)ws.NB, blk = blockIdx.x - sys * (unsigned)ws.NB;
     const int tid = threadIdx.x;
-    const SmRec in = sm_load(ws.recA + sys);
+    const CgRec in = cg_load(ws.recA + sys);
     const bool writer = blk == 0 && tid == 0;
-    if (in.state != PIVLFN_SMOOTH_RUNNING) {                                   // stopped: the record passes through, nothing else moves
-        if (writer) sm_store(ws.recB + sys, in);
-        return;
-    }
+    if (cg_frozen(in, ws.recB + sys, writer)) return;
     const double *const parts[2] = {ws.prz + (size_t)sys * ws.NB, ws.prr + (size_t)sys * ws.NB};
     double top[2];
     pr_finish<2>(parts, ws.NB, sw, top);
-    SmRec out = in;
-    const bool fresh = in.phase == SM_FRESH;
+    CgRec out = in;
+    const bool fresh = in.phase == CG_FRESH;
     double beta = 0.0;
     out.rho = top[0];
     out.rr = top[1];
@@ -461,10 +393,10 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_pcg_dir_kernel(const SmWs w
         beta = top[0] / in.rho;
         out.iters = in.iters + 1;
     }
-    out.phase = SM_MID;
+    out.phase = CG_MID;
     if (out.rr <= (tol * tol) * out.bb) {
         out.state = PIVLFN_SMOOTH_CONVERGED;
-        if (writer) sm_store(ws.recB + sys, out);
+        if (writer) cg_store(ws.recB + sys, out);
         return;
     }
     const size_t so = (size_t)sys * N;
@@ -473,17 +405,11 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_pcg_dir_kernel(const SmWs w
     double *dnew = (odd ? ws.d[0] : ws.d[1]) + so, *t = ws.t + so;
     out.dsel = (in.dsel & 1) ^ 1;
     auto val = [&](unsigned k) { return fresh ? z[k] : z[k] + beta * dold[k]; };
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j)
-            if (base + j < N) {
-                const unsigned i = (unsigned)(base + j);
-                dnew[i] = val(i);
-                t[i] = sm_lap(val, i, ws.H, ws.W);
-            }
-    }
-    if (writer) sm_store(ws.recB + sys, out);
+    pr_tile_for_each(ws.chunks, N, blk, [&](unsigned i) {
+        dnew[i] = val(i);
+        t[i] = sm_lap(val, i, ws.H, ws.W);
+    });
+    if (writer) cg_store(ws.recB + sys, out);
 }
 
 // q = w*d + s*(D t), the partials of d*q.  recB is only read.
@@ -493,32 +419,19 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_pcg_q_kernel(const SmWs ws,
     __shared__ double sw[1][4];
     const unsigned N = ws.N, sys = blockIdx.x / (unsigned)ws.NB, blk = blockIdx.x - sys * (unsigned)ws.NB;
     const int tid = threadIdx.x;
-    const SmRec in = sm_load(ws.recB + sys);
+    const CgRec in = cg_load(ws.recB + sys);
     if (in.state != PIVLFN_SMOOTH_RUNNING) return;
     const size_t so = (size_t)sys * N, fo = (size_t)(sys >> 1) * N;
     const double *d = ((in.dsel & 1) ? ws.d[1] : ws.d[0]) + so, *t = ws.t + so, *w = ws.w + fo;
     double *q = ws.q + so;
     auto val = [&](unsigned k) { return t[k]; };
-    PrCounter cnt;
-    double root = 0.0;
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-        double leaf[PR_OWN];
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j) {
-            leaf[j] = 0.0;
-            if (base + j < N) {
-                const unsigned i = (unsigned)(base + j);
-                const double dc = d[i], qv = w[i] * dc + s * sm_lap(val, i, ws.H, ws.W);
-                q[i] = qv;
-                leaf[j] = dc * qv;
-            }
-        }
-        double v[1] = {(leaf[0] + leaf[1]) + (leaf[2] + leaf[3])};
-        pr_chunk_root<1>(v, sw);
-        root = cnt.add(v[0], c);
-    }
-    if (tid == 0) ws.pdq[(size_t)sys * ws.NB + blk] = root;
+    double root[1];                                                            // d*q
+    pr_tile_roots<1>(ws.chunks, N, blk, sw, root, [&](unsigned i, double (&l)[1]) {
+        const double dc = d[i], qv = w[i] * dc + s * sm_lap(val, i, ws.H, ws.W);
+        q[i] = qv;
+        l[0] = dc * qv;
+    });
+    if (tid == 0) ws.pdq[(size_t)sys * ws.NB + blk] = root[0];
 }
 
 // finish sigma, the breakdown rule, x and r, the partials of r*r.  recB -> recA.
@@ -528,50 +441,25 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_pcg_xr_kernel(const SmWs ws
     __shared__ double sw[1][4];
     const unsigned N = ws.N, sys = blockIdx.x / (unsigned)ws.NB, blk = blockIdx.x - sys * (unsigned)ws.NB;
     const int tid = threadIdx.x;
-    const SmRec in = sm_load(ws.recB + sys);
+    const CgRec in = cg_load(ws.recB + sys);
     const bool writer = blk == 0 && tid == 0;
-    if (in.state != PIVLFN_SMOOTH_RUNNING) {
-        if (writer) sm_store(ws.recA + sys, in);
-        return;
-    }
-    const double *const parts[1] = {ws.pdq + (size_t)sys * ws.NB};
-    double top[1];
-    pr_finish<1>(parts, ws.NB, sw, top);
-    const double sigma = top[0];
-    SmRec out = in;
-    if (!(sigma > 0.0)) {                                                      // NaN included
-        out.state = PIVLFN_SMOOTH_BREAKDOWN;
-        if (writer) sm_store(ws.recA + sys, out);
-        return;
-    }
-    const double alpha = in.rho / sigma;
+    double alpha;
+    if (cg_frozen(in, ws.recA + sys, writer) || !cg_alpha(in, ws.recA + sys, writer, ws.pdq + (size_t)sys * ws.NB, ws.NB, sw, alpha)) return;
     const size_t so = (size_t)sys * N;
     const double *d = ((in.dsel & 1) ? ws.d[1] : ws.d[0]) + so, *q = ws.q + so;
     double *x = ws.x + so, *r = ws.r + so;
-    PrCounter cnt;
-    double root = 0.0;
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-        double leaf[PR_OWN];
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j) {
-            leaf[j] = 0.0;
-            if (base + j < N) {
-                const unsigned i = (unsigned)(base + j);
-                x[i] = x[i] + alpha * d[i];
-                const double rn = r[i] - alpha * q[i];
-                r[i] = rn;
-                leaf[j] = rn * rn;
-            }
-        }
-        double v[1] = {(leaf[0] + leaf[1]) + (leaf[2] + leaf[3])};
-        pr_chunk_root<1>(v, sw);
-        root = cnt.add(v[0], c);
-    }
-    out.phase = SM_PENDING;
+    double root[1];                                                            // r*r
+    pr_tile_roots<1>(ws.chunks, N, blk, sw, root, [&](unsigned i, double (&l)[1]) {
+        x[i] = x[i] + alpha * d[i];
+        const double rn = r[i] - alpha * q[i];
+        r[i] = rn;
+        l[0] = rn * rn;
+    });
+    CgRec out = in;
+    out.phase = CG_PENDING;
     if (tid == 0) {
-        ws.prr[(size_t)sys * ws.NB + blk] = root;
-        if (blk == 0) sm_store(ws.recA + sys, out);
+        ws.prr[(size_t)sys * ws.NB + blk] = root[0];
+        if (blk == 0) cg_store(ws.recA + sys, out);
     }
 }
 
@@ -583,35 +471,24 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_read_kernel(const SmWs ws, 
     const unsigned N = ws.N, sys = blockIdx.x / (unsigned)ws.NB, blk = blockIdx.x - sys * (unsigned)ws.NB;
     const int tid = threadIdx.x;
     const size_t so = (size_t)sys * N, fo = (size_t)(sys >> 1) * N;
-    SmRec rec = sm_load(ws.recA + sys);
+    CgRec rec = cg_load(ws.recA + sys);
     if (blk == 0) {                                                            // the whole workgroup: pr_finish synchronises it
         if (rec.state == PIVLFN_SMOOTH_RUNNING) {
             const double *const parts[1] = {ws.prr + (size_t)sys * ws.NB};
             double top[1];
             pr_finish<1>(parts, ws.NB, sw, top);
             rec.rr = top[0];
-            if (rec.phase != SM_FRESH) rec.iters += 1;
+            if (rec.phase != CG_FRESH) rec.iters += 1;
         }
-        if (tid == 0) {
-            status[4 * (size_t)sys + 0] = (double)rec.state;
-            status[4 * (size_t)sys + 1] = (double)rec.iters;
-            status[4 * (size_t)sys + 2] = rec.rr;
-            status[4 * (size_t)sys + 3] = rec.bb;
-        }
+        if (tid == 0) cg_write_status(status + 4 * (size_t)sys, rec);
     }
     const bool empty = rec.state == PIVLFN_SMOOTH_EMPTY;
-    for (int c = 0; c < ws.chunks; ++c) {
-        const size_t base = ((size_t)blk * ws.chunks + c) * PR_CHUNK + (size_t)tid * PR_OWN;
-#pragma unroll
-        for (int j = 0; j < PR_OWN; ++j)
-            if (base + j < N) {
-                const size_t i = base + j;
-                const double v = empty ? 1e10 : ws.x[so + i];
-                z[so + i] = v;
-                if (z32) z32[so + i] = (float)v;
-                if (filled && !(sys & 1)) filled[fo + i] = ws.w[fo + i] > 0.0 ? 0 : 1;
-            }
-    }
+    pr_tile_for_each(ws.chunks, N, blk, [&](size_t i) {
+        const double v = empty ? 1e10 : ws.x[so + i];
+        z[so + i] = v;
+        if (z32) z32[so + i] = (float)v;
+        if (filled && !(sys & 1)) filled[fo + i] = ws.w[fo + i] > 0.0 ? 0 : 1;
+    });
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
@@ -625,7 +502,7 @@ __global__ __launch_bounds__(PR_THREADS) void smooth_read_kernel(const SmWs ws, 
     if (int rc = check_workspace(fn, ws, ws_bytes, smooth_workspace_bytes(F, H, W), "F=%d H=%d W=%d", F, H, W)) return rc
 
 // z = M^-1 r for the planes of running systems (rec not null) or of all
-static void sm_precondition(const SmWs &ws, const double *in, double *out, int S, double s, const SmRec *rec, hipStream_t st)
+static void sm_precondition(const SmWs &ws, const double *in, double *out, int S, double s, const CgRec *rec, hipStream_t st)
 {
     dct_enqueue(ws.tb, in, ws.t, ws.q, S, ws.H, ws.W, false, true, s, rec, st);
     dct_enqueue(ws.tb, ws.q, ws.t, out, S, ws.H, ws.W, true, false, 0.0, rec, st);

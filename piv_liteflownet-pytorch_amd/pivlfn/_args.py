@@ -1,5 +1,5 @@
 """Argument checks shared by the analysis modules: the integer range, the finite non-negative float, the flow, mask and image tensors,
-and the call of an entry point that wants a workspace.  Private to the package; a new op calls these and keeps only what is its own."""
+the call of an entry point that wants a workspace, and the driver loop of the iterative solvers.  Private to the package; a new op calls these and keeps only what is its own."""
 from __future__ import annotations
 
 import math
@@ -91,6 +91,23 @@ def check_images(img1, img2, what: str):
 
 def ptr(t: Optional[torch.Tensor]):
     return t.data_ptr() if t is not None else None
+
+
+def run_iterations(step, read, status: torch.Tensor, cap: int, sync_every: Optional[int]) -> None:
+    """The driver loop of the iterative solvers (pressure, smooth): `step(n)` enqueues n iterations, `read()` enqueues the read-out that
+    fills `status` [..., 4] (state first; 1 is RUNNING in both ABIs).  At most `cap` iterations are enqueued, `sync_every` at a time with
+    a read-out in between that synchronises the host and ends the loop once no system is running; `sync_every=None` enqueues all `cap`
+    at once and looks at nothing.  Either way one last read-out follows."""
+    done = 0
+    while done < cap:
+        n = cap - done if sync_every is None else min(sync_every, cap - done)
+        step(n)
+        done += n
+        if sync_every is not None and done < cap:
+            read()
+            if not bool((status[..., 0] == 1).any()):                        # synchronises
+                break
+    read()
 
 
 def call_with_workspace(op: str, device, sizes, *args) -> None:

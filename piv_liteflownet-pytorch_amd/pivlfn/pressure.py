@@ -181,18 +181,15 @@ class PressureField:
                                                         st), "PressureField: gradient")
                 _lib.check(lib.pivlfn_pressure_setup(g.data_ptr(), valid.data_ptr(), F, ch, cw, float(self.cell), ws.data_ptr(), nbytes, st),
                            "PressureField: setup")
-                done = 0
-                while done < self.max_iter:
-                    n = self.max_iter - done if self.sync_every is None else min(self.sync_every, self.max_iter - done)
+
+                def step(n):
                     _lib.check(lib.pivlfn_pressure_cg(ws.data_ptr(), nbytes, F, ch, cw, self.tol, n, st), "PressureField: cg")
-                    done += n
-                    if self.sync_every is not None and done < self.max_iter:
-                        _lib.check(lib.pivlfn_pressure_read(ws.data_ptr(), nbytes, F, ch, cw, p.data_ptr(), flag.data_ptr(), status.data_ptr(), st),
-                                   "PressureField: read")
-                        if not bool((status[:, 0] == RUNNING).any()):            # synchronises
-                            break
-                _lib.check(lib.pivlfn_pressure_read(ws.data_ptr(), nbytes, F, ch, cw, p.data_ptr(), flag.data_ptr(), status.data_ptr(), st),
-                           "PressureField: read")
+
+                def read():
+                    _lib.check(lib.pivlfn_pressure_read(ws.data_ptr(), nbytes, F, ch, cw, p.data_ptr(), flag.data_ptr(), status.data_ptr(), st),
+                               "PressureField: read")
+
+                _args.run_iterations(step, read, status, self.max_iter, self.sync_every)
         scale_p = self.rho * (self.calib / self.dt) ** 2
         return PressureResult(p, g, flag, status, scale_p, self.rho * self.calib / (self.dt * self.dt), self.tol, self.reference)
 

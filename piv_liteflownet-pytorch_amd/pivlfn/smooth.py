@@ -176,22 +176,16 @@ def smooth_flow(flow: torch.Tensor, s: Optional[float] = None, wavelength: Optio
         nbytes = lib.pivlfn_smooth_workspace_bytes(B, H, W)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
 
+        def step(n):
+            _lib.check(lib.pivlfn_smooth_pcg(ws.data_ptr(), nbytes, B, H, W, s, float(tol), n, st), "smooth_flow: pcg")
+
         def read():
             _lib.check(lib.pivlfn_smooth_read(ws.data_ptr(), nbytes, B, H, W, z.data_ptr(), z32.data_ptr(), filled.data_ptr(), status.data_ptr(),
                                               st), "smooth_flow: read")
 
         _lib.check(lib.pivlfn_smooth_setup(flow.data_ptr(), _args.ptr(weights), _args.ptr(mask), B, H, W, s, ws.data_ptr(), nbytes, st),
                    "smooth_flow: setup")
-        done = 0
-        while done < cap:
-            n = cap - done if sync_every is None else min(sync_every, cap - done)
-            _lib.check(lib.pivlfn_smooth_pcg(ws.data_ptr(), nbytes, B, H, W, s, float(tol), n, st), "smooth_flow: pcg")
-            done += n
-            if sync_every is not None and done < cap:
-                read()
-                if not bool((status[..., 0] == RUNNING).any()):              # synchronises
-                    break
-        read()
+        _args.run_iterations(step, read, status, cap, sync_every)
     return Smoothed(z32, z, filled.bool(), status, s, float(tol), cap)
 
 

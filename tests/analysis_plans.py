@@ -9,6 +9,12 @@ line here, and a case where its plan has a step.
   pivlfn_pressure_setup / _cg / _read   NB = ceil(N / (chunks * 1024)) block partials per frame; NB > 256 puts partials into a second wave
                                   of pr_finish, NB > 1024 into its second chunk, N > 2^21 starts the PrCounter (chunks = 2), N > 2^22
                                   carries in it (chunks = 4).  PRESSURE_CASES, test_gpu_pressure.py::test_bits_where_the_partials_plan_changes.
+  pivlfn_smooth_setup / _pcg / _read   the same plan (pr_plan of csrc/cg_shared.h) with N = H W per system, a system being one component of
+                                  a frame.  SMOOTH_CASES, test_gpu_smooth.py::test_bb_where_the_partials_plan_changes.  The matrix
+                                  products of the preconditioner are pivlfn_dct2's.
+  pivlfn_dct2                     none in P (grid z); ceil(W / 64) x ceil(H / 64) workgroups a plane and ceil(K / 32) staged chunks of
+                                  the inner index, ragged edges staged as +0.0: the shapes of test_gpu_smooth.py::test_dct2_against_scipy
+                                  ((63, 65), (64, 64), (65, 130), (129, 31): around a tile and around a chunk).
   pivlfn_template_match           none in H, W (64 x 16 tiles, a flat 3-D grid); the template steps the packed row length and, from
                                   64 KiB of LDS on, the opt-in attribute: test_gpu_calibrate.py::test_match_reaches_the_32_bit_headroom
                                   (255 x 255) and the 25 x 25 / 5 x 5 cases of test_match_bits_of_the_restatement.
@@ -69,7 +75,7 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 # the constexpr values the formulas below depend on, per source file; tests/test_analysis_plans.py reads them back out of the text
 CONSTANTS = {
     "launch_checks.h": {"FRAME_GRID_THREADS": 256, "FRAME_GRID_BLOCKS": 16384, "FRAME_GRID_MIN_BLOCKS": 64},
-    "pressure.hip": {"PR_THREADS": 256, "PR_OWN": 4, "PR_CHUNK": 1024, "PR_MAX_PART": 2048},
+    "cg_shared.h": {"PR_THREADS": 256, "PR_OWN": 4, "PR_CHUNK": 1024, "PR_MAX_PART": 2048},
     "calibrate.hip": {"TP_BLOCK": 256},
     "twopoint.hip": {"TP_WAVES": 4, "TP_CHUNK": 256, "TP_SLOT": 16},
     "viz.hip": {"VZ_THREADS": 256, "VZ_MAX_BLOCKS": 4096},
@@ -78,7 +84,7 @@ CONSTANTS = {
 }
 FRAME_GRID_THREADS, FRAME_GRID_BLOCKS, FRAME_GRID_MIN_BLOCKS = (CONSTANTS["launch_checks.h"][k] for k in
                                                                  ("FRAME_GRID_THREADS", "FRAME_GRID_BLOCKS", "FRAME_GRID_MIN_BLOCKS"))
-PR_THREADS, PR_OWN, PR_CHUNK, PR_MAX_PART = (CONSTANTS["pressure.hip"][k] for k in ("PR_THREADS", "PR_OWN", "PR_CHUNK", "PR_MAX_PART"))
+PR_THREADS, PR_OWN, PR_CHUNK, PR_MAX_PART = (CONSTANTS["cg_shared.h"][k] for k in ("PR_THREADS", "PR_OWN", "PR_CHUNK", "PR_MAX_PART"))
 TP_BLOCK = CONSTANTS["calibrate.hip"]["TP_BLOCK"]
 TP_WAVES, TP_CHUNK, TP_SLOT = (CONSTANTS["twopoint.hip"][k] for k in ("TP_WAVES", "TP_CHUNK", "TP_SLOT"))
 VZ_THREADS, VZ_MAX_BLOCKS = CONSTANTS["viz.hip"]["VZ_THREADS"], CONSTANTS["viz.hip"]["VZ_MAX_BLOCKS"]
@@ -115,7 +121,8 @@ def pow2_at_least(n):
 
 # ---- the plans ------------------------------------------------------------------------------------------------------------------------
 def pressure(h, w):
-    """pr_layout of csrc/pressure.hip: chunks per workgroup and block partials per frame."""
+    """pr_plan of csrc/cg_shared.h, which pr_layout (pressure.hip) and sm_layout (smooth.hip) call: chunks per workgroup and block
+    partials per frame, or per system of the smoothing solver."""
     N = h * w
     P2 = pow2_at_least(N)
     chunks = P2 // (PR_CHUNK * PR_MAX_PART) if P2 > PR_CHUNK * PR_MAX_PART else 1
@@ -199,6 +206,14 @@ def _case(shape, branch, plan, crosses):
 
 
 PRESSURE_CASES = [          # (h, w), one frame; three iterations each (the restatement of 2048 x 2049 takes about a second an iteration)
+    _case((513, 512), "NB = 257: a partial in the second wave of pr_finish", pressure, lambda p: p["NB"] == 257 and p["chunks"] == 1),
+    _case((1024, 1025), "NB = 1025: the second chunk of pr_finish holds one partial", pressure,
+          lambda p: p["NB"] == PR_CHUNK + 1 and p["chunks"] == 1),
+    _case((2048, 1025), "chunks = 2: PrCounter level 0", pressure, lambda p: p["chunks"] == 2 and p["NB"] == 1025 and p["NB"] <= PR_MAX_PART),
+    _case((2048, 2049), "chunks = 4: a carry in PrCounter", pressure, lambda p: p["chunks"] == 4 and p["NB"] == 1025 and p["NB"] <= PR_MAX_PART),
+]
+
+SMOOTH_CASES = [            # (H, W), one frame: setup and read-out alone (bb of both systems against the restated tree)
     _case((513, 512), "NB = 257: a partial in the second wave of pr_finish", pressure, lambda p: p["NB"] == 257 and p["chunks"] == 1),
     _case((1024, 1025), "NB = 1025: the second chunk of pr_finish holds one partial", pressure,
           lambda p: p["NB"] == PR_CHUNK + 1 and p["chunks"] == 1),
@@ -294,7 +309,7 @@ SPECTRUM_CASES = [          # (L, N, K, first, pad)
 
 PROJECT_CASES = [(9, 5, 70), (9, 16, 300)]              # (n, K, P): the first and the last K of project_kernel<16>
 
-ALL_CASES = {"pressure": PRESSURE_CASES, "target_points": TARGET_POINTS_CASES, "twopoint": TWOPOINT_CASES, "vortex": VORTEX_CASES,
+ALL_CASES = {"pressure": PRESSURE_CASES, "smooth": SMOOTH_CASES, "target_points": TARGET_POINTS_CASES, "twopoint": TWOPOINT_CASES, "vortex": VORTEX_CASES,
              "quality": QUALITY_CASES, "stereo": STEREO_CASES, "field_absmax": VIZ_ABSMAX_CASES, "flow_maxrad": VIZ_MAXRAD_CASES,
              "viz_color": VIZ_COLOR_CASES, "particles": PARTICLES_CASES, "spectrum": SPECTRUM_CASES, "flow_fields": FIELDS_CASES,
              "flow_validate": VALIDATE_CASES, "flow_uncertainty": UNCERTAINTY_CASES, "frames_preprocess": PREPROC_CASES,

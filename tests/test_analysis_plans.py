@@ -22,8 +22,11 @@ def test_the_formulas_are_the_sources():
     """The expressions the restated plans copy, as they stand in the launchers (whitespace apart)."""
     squeeze = lambda s: re.sub(r"\s+", "", s)      # noqa: E731
     want = {
-        "pressure.hip": ["chunks = P2 > (size_t)PR_CHUNK * PR_MAX_PART ? P2 / ((size_t)PR_CHUNK * PR_MAX_PART) : 1",
-                         "tile = chunks * PR_CHUNK, NB = (N + tile - 1) / tile", "c * PR_CHUNK < NB"],
+        # the partials plan and the tree stand once, in the header; pr_layout and sm_layout call pr_plan
+        "cg_shared.h": ["chunks = P2 > (size_t)PR_CHUNK * PR_MAX_PART ? P2 / ((size_t)PR_CHUNK * PR_MAX_PART) : 1",
+                        "tile = chunks * PR_CHUNK, NB = (N + tile - 1) / tile", "c * PR_CHUNK < NB"],
+        "pressure.hip": ["plan = pr_plan(N)"],
+        "smooth.hip": ["plan = pr_plan(N)"],
         "calibrate.hip": ["per = (nblk + 255) / 256", "lo = min((int)threadIdx.x * per, nblk), hi = min(lo + per, nblk)",
                           "nblk = (hw + TP_BLOCK - 1) / TP_BLOCK"],
         "twopoint.hip": ["p.chunks = (1 << p.levels) > TP_CHUNK ? (1 << p.levels) / TP_CHUNK : 1",
@@ -54,7 +57,10 @@ def test_the_formulas_are_the_sources():
             assert squeeze(line) in text, f"csrc/{name} no longer holds `{line}`: restate the plan in tests/analysis_plans.py and revisit its cases"
     for name in sorted(os.listdir(ap.CSRC)):
         if name.endswith(".hip"):
-            assert "16384/(size_t)" not in squeeze(open(os.path.join(ap.CSRC, name)).read()), f"csrc/{name} has a frame-grid cap of its own"
+            text = squeeze(open(os.path.join(ap.CSRC, name)).read())
+            assert "16384/(size_t)" not in text, f"csrc/{name} has a frame-grid cap of its own"
+            assert "PR_CHUNK*PR_MAX_PART" not in text, f"csrc/{name} has a partials plan of its own: call pr_plan of cg_shared.h"
+            assert "PR_CHUNK" not in ap.source_constants(name) and "PR_CHUNK=" not in text, f"csrc/{name} defines PR_CHUNK: the tree is cg_shared.h's"
 
 
 @pytest.mark.parametrize("op,case", [(op, c) for op, cases in ap.ALL_CASES.items() for c in cases], ids=lambda v: v if isinstance(v, str) else str(v.shape))

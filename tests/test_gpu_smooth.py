@@ -227,6 +227,38 @@ def test_a_capped_frame_is_reported_unconverged(batch, dev):
     assert res.summary()["unconverged"] == 1
 
 
+def _smooth_shapes():
+    import analysis_plans as ap
+    return ap.shapes(ap.SMOOTH_CASES)
+
+
+@pytest.mark.parametrize("H,W", _smooth_shapes())
+def test_bb_where_the_partials_plan_changes(H, W, dev):
+    """One frame, unit weights, no mask, setup and the read-out with no iteration between them.  513 x 512: 257 partials, one in the
+    second wave of pr_finish; 1024 x 1025: 1025, one in its second chunk; 2048 x 1025 and 2048 x 2049: two and four chunks per workgroup,
+    PrCounter and its carry.  With unit weights b = y exactly and b*b rounds once, so bb = T(b*b) of a system is the restated tree over
+    y^2 bit for bit: the walk of csrc/cg_shared.h, its counters and pr_finish on the smoothing side."""
+    import analysis_plans as ap
+    import pressure_restatement as pr
+    plan = ap.pressure(H, W)
+    assert plan["NB"] > 256
+    lib, st = _lib.load(), _lib.stream_ptr(dev)
+    y = np.random.default_rng(1000 * H + W).standard_normal((1, 2, H, W)).astype(np.float32)
+    flow = torch.from_numpy(y).to(dev)
+    nbytes = lib.pivlfn_smooth_workspace_bytes(1, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    z = torch.empty(1, 2, H, W, dtype=torch.float64, device=dev)
+    status = torch.empty(1, 2, 4, dtype=torch.float64, device=dev)
+    assert lib.pivlfn_smooth_setup(flow.data_ptr(), None, None, 1, H, W, 1.0, ws.data_ptr(), nbytes, st) == 0, lib.pivlfn_last_error()
+    assert lib.pivlfn_smooth_read(ws.data_ptr(), nbytes, 1, H, W, z.data_ptr(), None, None, status.data_ptr(), st) == 0, lib.pivlfn_last_error()
+    got = status.cpu().numpy()[0]
+    for c in range(2):
+        want = pr.tree((y[0, c].astype(np.float64)) ** 2)
+        print(f"{H}x{W} c={c}: NB = {plan['NB']}, chunks = {plan['chunks']}, bb = {got[c, 3]!r}, restated {want!r}")
+        assert pr.same_bits(got[c, 3], want), (H, W, c, got[c, 3], want)
+        assert got[c, 0] == smooth.RUNNING and got[c, 1] == 0
+
+
 # ---- 6. stream and capture ---------------------------------------------------------------------------------------------------------------
 def test_a_side_stream_gives_the_same_bits(batch, dev):
     flows, masks = torch.from_numpy(batch[0]).to(dev), torch.from_numpy(batch[1]).to(dev)
