@@ -10,11 +10,17 @@ line here, and a case where its plan has a step.
                                   of pr_finish, NB > 1024 into its second chunk, N > 2^21 starts the PrCounter (chunks = 2), N > 2^22
                                   carries in it (chunks = 4).  PRESSURE_CASES, test_gpu_pressure.py::test_bits_where_the_partials_plan_changes.
   pivlfn_smooth_setup / _pcg / _read   the same plan (pr_plan of csrc/cg_shared.h) with N = H W per system, a system being one component of
-                                  a frame.  SMOOTH_CASES, test_gpu_smooth.py::test_bb_where_the_partials_plan_changes.  The matrix
-                                  products of the preconditioner are pivlfn_dct2's.
+                                  a frame.  SMOOTH_CASES, test_gpu_smooth.py::test_bb_where_the_partials_plan_changes (the setup
+                                  alone).  SMOOTH_SOLVE_CASES iterate: NB = 3 with a ragged last tile and rows that straddle a
+                                  thread's four nodes (37 x 61), NB = 9 (70 x 131), NB = 257 (513 x 512);
+                                  test_gpu_smooth.py::test_rr_follows_the_restated_iteration, test_solve_against_the_sparse_operator,
+                                  test_batch_cuts_and_frozen_systems, test_guarded_solve.  The matrix products of the
+                                  preconditioner are pivlfn_dct2's.
   pivlfn_dct2                     none in P (grid z); ceil(W / 64) x ceil(H / 64) workgroups a plane and ceil(K / 32) staged chunks of
-                                  the inner index, ragged edges staged as +0.0: the shapes of test_gpu_smooth.py::test_dct2_against_scipy
-                                  ((63, 65), (64, 64), (65, 130), (129, 31): around a tile and around a chunk).
+                                  the inner index, ragged edges staged as +0.0 (dct below): the shapes of
+                                  test_gpu_smooth.py::test_dct2_against_scipy ((63, 65), (64, 64), (65, 130), (129, 31): around a tile
+                                  and around a chunk).  With the Gamma epilogue and the skip of stopped planes: SMOOTH_SOLVE_CASES,
+                                  70 x 131 being 3 x 2 ragged blocks a plane with 5 and 3 chunks of the inner index.
   pivlfn_template_match           none in H, W (64 x 16 tiles, a flat 3-D grid); the template steps the packed row length and, from
                                   64 KiB of LDS on, the opt-in attribute: test_gpu_calibrate.py::test_match_reaches_the_32_bit_headroom
                                   (255 x 255) and the 25 x 25 / 5 x 5 cases of test_match_bits_of_the_restatement.
@@ -76,6 +82,7 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 CONSTANTS = {
     "launch_checks.h": {"FRAME_GRID_THREADS": 256, "FRAME_GRID_BLOCKS": 16384, "FRAME_GRID_MIN_BLOCKS": 64},
     "cg_shared.h": {"PR_THREADS": 256, "PR_OWN": 4, "PR_CHUNK": 1024, "PR_MAX_PART": 2048},
+    "smooth.hip": {"DC_BLK": 64, "DC_KC": 32},
     "calibrate.hip": {"TP_BLOCK": 256},
     "twopoint.hip": {"TP_WAVES": 4, "TP_CHUNK": 256, "TP_SLOT": 16},
     "viz.hip": {"VZ_THREADS": 256, "VZ_MAX_BLOCKS": 4096},
@@ -85,6 +92,7 @@ CONSTANTS = {
 FRAME_GRID_THREADS, FRAME_GRID_BLOCKS, FRAME_GRID_MIN_BLOCKS = (CONSTANTS["launch_checks.h"][k] for k in
                                                                  ("FRAME_GRID_THREADS", "FRAME_GRID_BLOCKS", "FRAME_GRID_MIN_BLOCKS"))
 PR_THREADS, PR_OWN, PR_CHUNK, PR_MAX_PART = (CONSTANTS["cg_shared.h"][k] for k in ("PR_THREADS", "PR_OWN", "PR_CHUNK", "PR_MAX_PART"))
+DC_BLK, DC_KC = CONSTANTS["smooth.hip"]["DC_BLK"], CONSTANTS["smooth.hip"]["DC_KC"]
 TP_BLOCK = CONSTANTS["calibrate.hip"]["TP_BLOCK"]
 TP_WAVES, TP_CHUNK, TP_SLOT = (CONSTANTS["twopoint.hip"][k] for k in ("TP_WAVES", "TP_CHUNK", "TP_SLOT"))
 VZ_THREADS, VZ_MAX_BLOCKS = CONSTANTS["viz.hip"]["VZ_THREADS"], CONSTANTS["viz.hip"]["VZ_MAX_BLOCKS"]
@@ -128,6 +136,21 @@ def pressure(h, w):
     chunks = P2 // (PR_CHUNK * PR_MAX_PART) if P2 > PR_CHUNK * PR_MAX_PART else 1
     tile = chunks * PR_CHUNK
     return {"N": N, "chunks": chunks, "NB": cdiv(N, tile)}
+
+
+def dct(H, W):
+    """dct_enqueue and dct_mm_kernel of csrc/smooth.hip: the grid of 64 x 64 blocks of a plane (x, y), whether its edge blocks are ragged,
+    and the staged chunks of the inner index of the product along the rows (K = W) and along the columns (K = H)."""
+    return {"grid": (cdiv(W, DC_BLK), cdiv(H, DC_BLK)), "blocks": cdiv(W, DC_BLK) * cdiv(H, DC_BLK),
+            "ragged": (W % DC_BLK != 0, H % DC_BLK != 0), "chunks": (cdiv(W, DC_KC), cdiv(H, DC_KC))}
+
+
+def smooth_solve(H, W):
+    """A system of the smoothing solver: the partials plan, the nodes of its last tile, and the matrix products of its preconditioner."""
+    p = pressure(H, W)
+    p["last_tile"] = p["N"] - (p["NB"] - 1) * p["chunks"] * PR_CHUNK
+    p["dct"] = dct(H, W)
+    return p
 
 
 def pressure_offset_b(F, h, w):
@@ -221,6 +244,16 @@ SMOOTH_CASES = [            # (H, W), one frame: setup and read-out alone (bb of
     _case((2048, 2049), "chunks = 4: a carry in PrCounter", pressure, lambda p: p["chunks"] == 4 and p["NB"] == 1025 and p["NB"] <= PR_MAX_PART),
 ]
 
+SMOOTH_SOLVE_CASES = [      # (H, W, iterations of the trajectory test): the smallest frames whose solve crosses tile seams and matrix blocks
+    _case((37, 61, 6), "NB = 3, a ragged last tile, rows that straddle a thread's four nodes, one matrix block", smooth_solve,
+          lambda p: p["NB"] == 3 and p["last_tile"] == 209 and 61 % PR_OWN != 0 and p["dct"]["blocks"] == 1 and p["dct"]["chunks"] == (2, 2)),
+    _case((70, 131, 6), "NB = 9; 3 x 2 ragged matrix blocks a plane: Gamma and the skip at m0, n0 > 0; 5 and 3 chunks of the inner index",
+          smooth_solve, lambda p: p["NB"] == 9 and p["dct"]["grid"] == (3, 2) and p["dct"]["ragged"] == (True, True)
+          and p["dct"]["chunks"] == (5, 3)),
+    _case((513, 512, 3), "NB = 257: the second wave of pr_finish inside the iteration kernels and cg_alpha", smooth_solve,
+          lambda p: p["NB"] == 257 and p["chunks"] == 1 and p["dct"]["grid"] == (8, 9)),
+]
+
 TARGET_POINTS_CASES = [     # (H, W)
     _case((257, 256), "per = 2, only thread 128 has a short range", tp_scan,
           lambda p: p["nblk"] == 257 and p["per"] == 2 and p["per"] * 256 > p["nblk"] and p["short"] == [128] and p["empty"][0] == 129),
@@ -309,7 +342,7 @@ SPECTRUM_CASES = [          # (L, N, K, first, pad)
 
 PROJECT_CASES = [(9, 5, 70), (9, 16, 300)]              # (n, K, P): the first and the last K of project_kernel<16>
 
-ALL_CASES = {"pressure": PRESSURE_CASES, "smooth": SMOOTH_CASES, "target_points": TARGET_POINTS_CASES, "twopoint": TWOPOINT_CASES, "vortex": VORTEX_CASES,
+ALL_CASES = {"pressure": PRESSURE_CASES, "smooth": SMOOTH_CASES, "smooth_solve": SMOOTH_SOLVE_CASES, "target_points": TARGET_POINTS_CASES, "twopoint": TWOPOINT_CASES, "vortex": VORTEX_CASES,
              "quality": QUALITY_CASES, "stereo": STEREO_CASES, "field_absmax": VIZ_ABSMAX_CASES, "flow_maxrad": VIZ_MAXRAD_CASES,
              "viz_color": VIZ_COLOR_CASES, "particles": PARTICLES_CASES, "spectrum": SPECTRUM_CASES, "flow_fields": FIELDS_CASES,
              "flow_validate": VALIDATE_CASES, "flow_uncertainty": UNCERTAINTY_CASES, "frames_preprocess": PREPROC_CASES,

@@ -26,7 +26,8 @@ def test_the_formulas_are_the_sources():
         "cg_shared.h": ["chunks = P2 > (size_t)PR_CHUNK * PR_MAX_PART ? P2 / ((size_t)PR_CHUNK * PR_MAX_PART) : 1",
                         "tile = chunks * PR_CHUNK, NB = (N + tile - 1) / tile", "c * PR_CHUNK < NB"],
         "pressure.hip": ["plan = pr_plan(N)"],
-        "smooth.hip": ["plan = pr_plan(N)"],
+        "smooth.hip": ["plan = pr_plan(N)", "grid((unsigned)cdiv(W, DC_BLK), (unsigned)cdiv(H, DC_BLK), (unsigned)P)",
+                       "m0 = blockIdx.y * DC_BLK, n0 = blockIdx.x * DC_BLK", "chunks = (p.K + DC_KC - 1) / DC_KC", "a.K = W", "b.K = H"],
         "calibrate.hip": ["per = (nblk + 255) / 256", "lo = min((int)threadIdx.x * per, nblk), hi = min(lo + per, nblk)",
                           "nblk = (hw + TP_BLOCK - 1) / TP_BLOCK"],
         "twopoint.hip": ["p.chunks = (1 << p.levels) > TP_CHUNK ? (1 << p.levels) / TP_CHUNK : 1",
@@ -74,6 +75,8 @@ def test_the_smaller_neighbour_of_a_case_stays_below_its_branch():
     """One step down and the branch is not taken: the cases are the first sizes, not just large ones."""
     assert ap.pressure(512, 512) == {"N": 1 << 18, "chunks": 1, "NB": 256} and ap.pressure(1024, 1024)["NB"] == 1024
     assert ap.pressure(2048, 1024)["chunks"] == 1 and ap.pressure(2048, 2048)["chunks"] == 2
+    assert ap.smooth_solve(24, 20)["NB"] == 1 and ap.smooth_solve(33, 17)["NB"] == 1 and ap.smooth_solve(64, 64)["dct"]["blocks"] == 1
+    assert ap.dct(64, 64) == {"grid": (1, 1), "blocks": 1, "ragged": (False, False), "chunks": (2, 2)} and ap.dct(65, 130)["grid"] == (3, 2)
     assert ap.tp_scan(256, 256)["per"] == 1 and ap.tp_scan(192, 320) == {"nblk": 240, "per": 1, "short": [], "empty": list(range(240, 256))}
     assert ap.twopoint(65, 300, 255)["slots"] == 1 and ap.twopoint(70, 131, 16)["slots"] == 1 and ap.twopoint(20, 300, 255)["chunks"] == 2
     assert ap.twopoint(5, 512, 8)["chunks"] == 2 and ap.twopoint(1024, 1024, 64) == {"levels": 10, "chunks": 4, "z": 4, "slots": 5, "lds": 2560}

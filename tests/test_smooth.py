@@ -1,4 +1,5 @@
-"""CPU: the yardsticks of tests/smooth_restatement.py against scipy, the parameter arithmetic and argument checks of pivlfn.smooth, the
+"""CPU: the yardsticks of tests/smooth_restatement.py against scipy and against each other (sparse against dense, the contract-order
+iteration against numpy's), three wrong variants of that iteration against the judgements the GPU tests use, the parameter arithmetic and argument checks of pivlfn.smooth, the
 host-side refusals of the pivlfn_dct2 / pivlfn_smooth_* entry points, and run.py's flags.  No GPU is touched."""
 import numpy as np
 import pytest
@@ -43,6 +44,124 @@ def test_the_restated_pcg_solves_the_dense_system():
     assert np.linalg.norm(z - sr.solve_direct(w, y, 1.0)) <= 2.0 * np.linalg.norm(r) / sr.lambda_min(w, 1.0)
     z0, its0, _, _ = sr.pcg(np.ones_like(w), y, 1.0, 1e-8)                   # no gaps: the start is the solution
     assert its0 == 0
+
+
+@pytest.mark.parametrize("H,W,seed", [(24, 20, 1), (33, 17, 2)])
+def test_the_sparse_operator_is_the_dense_one(H, W, seed):
+    flow, mask = sr.solve_case(H, W, seed)
+    w = sr.weights_of(flow, np.random.default_rng(seed).uniform(0.05, 1.0, mask.shape).astype(np.float32), mask)
+    y = flow[0].astype(np.float64)
+    for s in (0.05, 1.0, 50.0):
+        dense = sr.operator(w, s)
+        assert np.abs(sr.operator_sparse(w, s).toarray() - dense).max() <= 8 * 2.0 ** -52 * np.abs(dense).max()
+        lmin = sr.lambda_min(w, s)
+        assert abs(sr.lambda_min_sparse(w, s) - lmin) <= 1e-9 * lmin
+        # two backward-stable direct solves: each within a few cond(A) ulp of the solution
+        cond = np.linalg.eigvalsh(dense)[-1] / lmin
+        assert np.abs(sr.solve_sparse(w, y, s) - sr.solve_direct(w, y, s)).max() <= 64 * cond * 2.0 ** -52 * np.abs(y).max()
+
+
+def test_the_contract_order_restates_the_same_operator():
+    a = np.random.default_rng(3).standard_normal((9, 14))
+    assert np.abs(sr.lap_ordered(a) - sr.lap(a)).max() <= 8 * 2.0 ** -52 * np.abs(a).max()
+    assert np.abs(sr.gamma_contract(70, 131, 0.05) - sr.gamma(70, 131, 0.05)).max() <= 2.0 ** -40       # 2 - 2 cos cancels near k = 0
+    hist = []
+    flow, mask = sr.solve_case(24, 20, 1)
+    w, y = sr.weights_of(flow, None, mask), flow[0].astype(np.float64)
+    z, its, rr, _ = sr.pcg(w, y, 1.0, 1e-8, history=hist)
+    assert len(hist) == its + 1 and hist[-1] == rr
+    rr_tree, x = sr.pcg_tree(w, y, 1.0, its + 5, tol=1e-8)                  # the contract's stopping rule: the same count
+    assert len(rr_tree) == its + 1 and np.abs(x - z).max() <= 1e-12
+    assert np.abs(np.array(rr_tree) / np.array(hist) - 1.0).max() <= 1e-9
+
+
+def test_the_seam_cases_put_gaps_and_known_vectors_on_both_sides():
+    for H, W in ((37, 61), (70, 131), (513, 512)):
+        gap = sr.seam_case(H, W, 3)[1].reshape(-1) != 0
+        assert gap[1019:1030].all() and not gap[1015:1019].any() and not gap[1030:1034].any()          # the seam 1023 | 1024
+        assert not gap[2045:2051].any()                                                             # the seam 2047 | 2048 ...
+        for k in (2047, 2048):
+            assert gap[k - W] and gap[k + W], (H, W, k)                                             # ... and its vertical neighbours
+        assert 0.05 < gap.mean() < 0.2
+
+
+# ---- what the solve's judgements catch: three wrong variants of the restated iteration at 70 x 131 ----------------------------------------
+MUTANT_SHAPE = (70, 131, 3)
+MUTANT_ITERS = 6
+
+
+@pytest.fixture(scope="module")
+def mutant_case():
+    H, W, seed = MUTANT_SHAPE
+    flow, mask = sr.seam_case(H, W, seed)
+    w, y = sr.weights_of(flow, None, mask), flow[0].astype(np.float64)
+    assert H * W > 8 * sr.SEAM and H > 64 and W > 64
+    return w, y, {s: sr.trajectory_reference(w, y, s, MUTANT_ITERS) for s in (0.05, 1.0, 50.0)}
+
+
+def _mutants(w, s):
+    """(a) a pr_finish that loses the last workgroup's partial of sigma;  (b) a tile seam: nodes 1023 and 1024, neighbours in a row,
+    do not see each other;  (c) an epilogue that forgets m0: the Gamma rows of the second block of 64 are those of the first."""
+    import pressure_restatement as pr
+    H, W = w.shape
+    last = (H * W - 1) // sr.SEAM * sr.SEAM
+
+    def sigma_without_the_last_tile(leaves):
+        l = np.array(leaves, np.float64).reshape(-1)
+        l[last:] = 0.0
+        return pr.tree(l)
+
+    assert (sr.SEAM - 1) // W == sr.SEAM // W                                 # 1023 and 1024 lie in one row
+
+    def lap_with_a_seam(a):
+        l, r, u, d = (np.zeros_like(a) for _ in range(4))
+        l[:, 1:] = a[:, :-1] - a[:, 1:]
+        r[:, :-1] = a[:, 1:] - a[:, :-1]
+        u[1:, :] = a[:-1, :] - a[1:, :]
+        d[:-1, :] = a[1:, :] - a[:-1, :]
+        r.reshape(-1)[sr.SEAM - 1] = 0.0
+        l.reshape(-1)[sr.SEAM] = 0.0
+        return ((l + r) + u) + d
+
+    g = sr.gamma_contract(H, W, s)
+    g[64:] = g[:H - 64]
+    return {"a": {"sigma": sigma_without_the_last_tile}, "b": {"lap": lap_with_a_seam}, "c": {"gamma": g}}
+
+
+@pytest.mark.parametrize("s", [0.05, 1.0, 50.0])
+@pytest.mark.parametrize("which", ["a", "b", "c"])
+def test_a_wrong_part_leaves_the_trajectory(which, s, mutant_case):
+    w, y, refs = mutant_case
+    ref = refs[s]
+    assert sr.check_trajectory(ref["rr_pcg"], ref, f"numpy's own sums, s={s}") <= 1.0 / sr.ORDERS     # the yardstick passes its own check
+    rr, _ = sr.pcg_tree(w, y, s, MUTANT_ITERS, parts=_mutants(w, s)[which])
+    rel = np.abs(np.array(rr)[:ref["K"] + 1] / ref["rr_tree"][:ref["K"] + 1] - 1.0).max()
+    print(f"mutant ({which}) s={s}: rr leaves the restated trajectory by {rel:.2f} of its value")
+    assert rel >= 1e6 * max(sr.ORDERS * ref["Y"], sr.FLOOR)                 # far outside the bound, not a near miss
+    with pytest.raises(AssertionError):
+        sr.check_trajectory(rr, ref, f"mutant ({which}) s={s}")
+
+
+def test_the_residual_check_sees_a_wrong_operator_and_not_a_wrong_preconditioner(mutant_case):
+    """Run to the stopping rule at tol = 1e-8, s = 0.05.  Mutant (b) solves another system: its true residual fails.  Mutant (c) is still
+    a symmetric positive definite preconditioner: it converges to the right answer in under twice numpy's iterations and passes all of
+    check_solve, which is why the trajectory check exists."""
+    w, y, _ = mutant_case
+    s, tol = 0.05, 1e-8
+    ref = sr.solve_reference(w, y, s, tol)
+    good, x = sr.pcg_tree(w, y, s, 200, tol=tol)
+    sr.check_solve(x, len(good) - 1, ref, "the restated iteration")
+    assert len(good) - 1 == ref["its"]
+    rr, x = sr.pcg_tree(w, y, s, 200, tol=tol, parts=_mutants(w, s)["b"])
+    with pytest.raises(AssertionError):
+        sr.check_solve(x, len(rr) - 1, ref, "mutant (b)")
+    rr, x = sr.pcg_tree(w, y, s, 200, tol=tol, parts=_mutants(w, s)["c"])
+    assert ref["its"] < len(rr) - 1 <= 2 * ref["its"]
+    sr.check_solve(x, len(rr) - 1, ref, "mutant (c)")                       # passes: residual, error bound and iteration count
+    _, x6 = sr.pcg_tree(w, y, s, 6, parts=_mutants(w, s)["c"])
+    tref = sr.trajectory_reference(w, y, s, 6)
+    with pytest.raises(AssertionError):
+        sr.check_iterate(x6, tref, "mutant (c)")
 
 
 def test_weights_of_applies_the_unknown_rule():
