@@ -15,6 +15,8 @@ from typing import Callable, Iterable, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from . import _accum
+
 
 def shard_bounds(n_pairs: int, rank: int, world: int) -> Tuple[int, int]:
     """Contiguous shard [lo, hi) of rank `rank`; later ranks may be short or empty."""
@@ -105,5 +107,5 @@ def run_sharded(flow_fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], l
 
 def _default_device(group):
     if dist.get_backend(group) == "nccl":
-        return torch.device("cuda", torch.cuda.current_device())
+        return _accum.cuda_device()
     return torch.device("cpu")

@@ -29,7 +29,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 
 TERMS = ("n", "u", "v", "uu", "vv", "uv", "uuu", "vvv", "uuv", "vvu", "uuuu", "vvvv", "uuvv", "n1", "n2", "n3", "n4", "p1", "p2", "p3",
          "p4")                                                                   # acc[:, y, x]
@@ -231,10 +231,7 @@ class DistributionResult:
                "joint_bins": np.int64(self.joint_bins), "frac_bins": np.int64(self.frac_bins), "frames": np.int64(self.frames),
                "hole": np.float64(self.hole), "normalised": np.bool_(self.normalised), "centres": centres, "pdf_u": pdf_u,
                "pdf_v": self.pdf("v")[1], "frac_u": self.fraction("u"), "frac_v": self.fraction("v")}
-        if not path.endswith(".npz"):
-            path += ".npz"
-        np.savez(path, **extra, **out)
-        return path
+        return _accum.save_npz(path, **extra, **out)
 
     @classmethod
     def load(cls, path: str) -> "DistributionResult":
@@ -243,20 +240,7 @@ class DistributionResult:
                        int(f["frames"]), float(f["hole"]), bool(f["normalised"]))
 
 
-def _planes(given, keys, what, H, W, device):
-    """None, a [2,H,W] tensor or array, or the path of a FlowStats file (its arrays `keys`): float64 on the device."""
-    if given is None:
-        return None
-    if isinstance(given, str):
-        with np.load(given) as f:
-            given = np.stack([f[keys[0]], f[keys[1]]])
-    t = torch.as_tensor(given).detach().to(device=device, dtype=torch.float64).contiguous()
-    if tuple(t.shape) != (2, H, W):
-        raise ValueError(f"FlowDistribution: {what} {tuple(t.shape)}, expected [2,{H},{W}]")
-    return t
-
-
-class FlowDistribution:
+class FlowDistribution(_accum.FrameAccumulator):
     """Running distribution sums over a flow sequence of one size: acc [21,H,W] float64 (TERMS order) and the counters hist (int64
     holding the unsigned words of include/pivlfn.h) on the device, and the frame count.  update() enqueues two kernels on the current
     stream and never synchronises the host; result() / save() do.
@@ -269,16 +253,11 @@ class FlowDistribution:
     def __init__(self, H: int, W: int, bins: int = 256, range=(-8.0, 8.0), joint_bins: int = 64, frac_bins: int = 64,   # noqa: A002
                  mean=None, scale=None, hole: float = 0.0, device=None):
         check_params(bins, range, joint_bins, frac_bins, hole)
-        self.H, self.W = int(H), int(W)
-        if self.H <= 0 or self.W <= 0 or self.H * self.W >= 1 << 31:
-            raise ValueError(f"FlowDistribution: bad size {H} x {W} (positive, fewer than 2^31 vectors)")
+        super().__init__(H, W, device, int(H) * int(W) < 1 << 31, " (positive, fewer than 2^31 vectors)")
         self.bins, self.joint_bins, self.frac_bins = bins, joint_bins, frac_bins
         self.lo, self.hi, self.hole = float(range[0]), float(range[1]), float(hole)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise NotImplementedError("FlowDistribution: GPU devices only")
-        self.mean = _planes(mean, ("mean_u", "mean_v"), "mean", self.H, self.W, self.device)
-        self.scale = _planes(scale, ("rms_u", "rms_v"), "scale", self.H, self.W, self.device)
+        self.mean = _accum.load_planes(mean, ("mean_u", "mean_v"), "FlowDistribution: mean", self.H, self.W, self.device)
+        self.scale = _accum.load_planes(scale, ("rms_u", "rms_v"), "FlowDistribution: scale", self.H, self.W, self.device)
         if self.scale is not None:
             self.thr = (self.hole * self.scale[0] * self.scale[1]).contiguous()
         elif self.hole > 0.0:
@@ -287,27 +266,19 @@ class FlowDistribution:
             self.thr = None
         self.acc = torch.zeros([len(TERMS), self.H, self.W], dtype=torch.float64, device=self.device)
         self.hist = torch.zeros([hist_words(bins, joint_bins, frac_bins)], dtype=torch.int64, device=self.device)
-        self.count = 0
 
     def update(self, flows: torch.Tensor, mask: Optional[torch.Tensor] = None) -> None:
         """Add the frames of `flows` [B,2,H,W] (float32, on this device), in batch order; `mask` [B,H,W]: nonzero = leave the vector out."""
         flows = _args.check_flows(flows, "FlowDistribution.update")
-        if tuple(flows.shape[2:]) != (self.H, self.W) or flows.device != self.device:
-            raise ValueError(f"FlowDistribution.update: flows {tuple(flows.shape)} on {flows.device}, accumulators for [{self.H},{self.W}] on "
-                             f"{self.device}")
+        self._check_mine(flows.shape[2:], flows.device, lambda: f"flows {tuple(flows.shape)} on {flows.device}",
+                         "accumulators for [{H},{W}]")
         mask = _args.check_mask(mask, "FlowDistribution.update", truth=flows)
         B = flows.size(0)
-        if B == 0:
-            return
         lib = _lib.load()
-        with torch.cuda.device(self.device):
-            st = _lib.stream_ptr(self.device)
-            _lib.check(lib.pivlfn_flow_moments_accumulate(flows.data_ptr(), _args.ptr(mask), _args.ptr(self.mean), _args.ptr(self.thr),
-                                                          self.acc.data_ptr(), B, self.H, self.W, st), "FlowDistribution.update")
-            _lib.check(lib.pivlfn_flow_hist_accumulate(flows.data_ptr(), _args.ptr(mask), _args.ptr(self.mean), _args.ptr(self.scale),
-                                                       self.hist.data_ptr(), B, self.H, self.W, self.lo, self.hi, self.bins, self.joint_bins,
-                                                       self.frac_bins, st), "FlowDistribution.update")
-        self.count += B
+        self._enqueue(B, (lib.pivlfn_flow_moments_accumulate, flows.data_ptr(), _args.ptr(mask), _args.ptr(self.mean), _args.ptr(self.thr),
+                          self.acc.data_ptr(), B, self.H, self.W),
+                      (lib.pivlfn_flow_hist_accumulate, flows.data_ptr(), _args.ptr(mask), _args.ptr(self.mean), _args.ptr(self.scale),
+                       self.hist.data_ptr(), B, self.H, self.W, self.lo, self.hi, self.bins, self.joint_bins, self.frac_bins))
 
     def result(self) -> DistributionResult:
         return DistributionResult(self.acc.cpu().numpy(), self.hist.cpu().numpy().view(np.uint64), self.bins, (self.lo, self.hi),

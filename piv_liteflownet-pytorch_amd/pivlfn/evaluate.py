@@ -22,7 +22,7 @@ from typing import Dict, List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 
 FIELDS = ("n", "l1", "epe", "sq", "du", "dv", "max")         # the seven entries of a pair's sums, in order
 STAGES = ("M", "S", "R")
@@ -171,53 +171,28 @@ def finalize_errors(acc: np.ndarray, frames: int) -> Dict[str, np.ndarray]:
             "rms_u": rms(acc[3], bu), "rms_v": rms(acc[4], bv), "mean_epe": acc[5] / n}
 
 
-class ErrorStats:
+class ErrorStats(_accum.FrameAccumulator):
     """Per-pixel running error sums over a sequence of one size: acc [6,H,W] float64 on the device (ACC order) and the frame count.
     update() enqueues one kernel on the current stream and never synchronises the host; result() / save() do."""
 
     def __init__(self, H: int, W: int, device=None):
-        self.H, self.W = int(H), int(W)
-        if self.H <= 0 or self.W <= 0:
-            raise ValueError(f"ErrorStats: bad size {H} x {W}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise NotImplementedError("ErrorStats: GPU devices only")
+        super().__init__(H, W, device)
         self.acc = torch.zeros([len(ACC), self.H, self.W], dtype=torch.float64, device=self.device)
-        self.count = 0
 
     def update(self, flow: torch.Tensor, truth: torch.Tensor, mask: Optional[torch.Tensor] = None) -> None:
         """Add the frames of `flow` against `truth` (both [B,2,H,W] float32 on this device), in batch order; `mask` as flow_errors."""
         flow = _args.check_flows(flow, "ErrorStats.update")
         truth = _check_truth(truth, flow, "ErrorStats.update")
         mask = _args.check_mask(mask, "ErrorStats.update", truth=truth)
-        if tuple(flow.shape[2:]) != (self.H, self.W) or truth.shape != flow.shape or flow.device != self.device:
-            raise ValueError(f"ErrorStats.update: flows {tuple(flow.shape)} and truth {tuple(truth.shape)} on {flow.device}, accumulators "
-                             f"[{self.H},{self.W}] on {self.device}")
+        self._check_mine(flow.shape[2:], flow.device, lambda: f"flows {tuple(flow.shape)} and truth {tuple(truth.shape)} on {flow.device}",
+                         also=truth.shape == flow.shape)
         B = flow.size(0)
-        if B == 0:
-            return
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().pivlfn_error_stats_accumulate(flow.data_ptr(), truth.data_ptr(),
-                                                                 mask.data_ptr() if mask is not None else None, self.acc.data_ptr(), B,
-                                                                 self.H, self.W, _lib.stream_ptr(self.device)), "ErrorStats.update")
-        self.count += B
+        self._enqueue(B, (_lib.load().pivlfn_error_stats_accumulate, flow.data_ptr(), truth.data_ptr(),
+                          mask.data_ptr() if mask is not None else None, self.acc.data_ptr(), B, self.H, self.W))
 
     def merge(self, group=None) -> None:
         """Collective over `group`, as FlowStats.merge: the accumulators of all ranks added in rank order, on every rank."""
-        import torch.distributed as dist
-        world = dist.get_world_size(group)
-        on_dev = dist.get_backend(group) == "nccl"
-        acc = self.acc if on_dev else self.acc.cpu()
-        cnt = torch.tensor([self.count], dtype=torch.int64, device=acc.device)
-        accs = [torch.empty_like(acc) for _ in range(world)]
-        cnts = [torch.empty_like(cnt) for _ in range(world)]
-        dist.all_gather(accs, acc, group=group)
-        dist.all_gather(cnts, cnt, group=group)
-        total = accs[0].clone()
-        for a in accs[1:]:
-            total += a
-        self.acc.copy_(total)
-        self.count = int(sum(int(c.item()) for c in cnts))
+        self.count = _accum.merge_sums([self.acc], self.count, group)
 
     def result(self) -> Dict[str, np.ndarray]:
         """finalize_errors() of the current sums (RESULT)."""
@@ -230,7 +205,4 @@ class ErrorStats:
         acc = self.acc.cpu().numpy()
         res = finalize_errors(acc, self.count)
         maps = {k: v.astype(np.float32) for k, v in res.items() if k not in ("frames", "count")}
-        if not path.endswith(".npz"):
-            path += ".npz"
-        np.savez(path, acc=acc, frames=res["frames"], count=res["count"].astype(np.int32), **extra, **maps)
-        return path
+        return _accum.save_npz(path, acc=acc, frames=res["frames"], count=res["count"].astype(np.int32), **extra, **maps)

@@ -28,7 +28,7 @@ from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 
 OUT, LOST, UNDEFINED = 1, 2, 4          # the bits of a flag byte (PIVLFN_FLOWMAP_*)
 
@@ -83,11 +83,7 @@ class FlowMap:
     def __init__(self, H: int, W: int, spacing: int = 1, points=None, backward: bool = False, iters: int = 8, device="cuda"):
         self.h, self.w = check_params(H, W, spacing, iters)
         self.H, self.W, self.spacing, self.backward, self.iters = H, W, spacing, bool(backward), iters
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise NotImplementedError("FlowMap: GPU only")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _accum.cuda_device(device, "FlowMap: GPU only")
         self._points = None
         if points is not None:
             pts = torch.as_tensor(points)

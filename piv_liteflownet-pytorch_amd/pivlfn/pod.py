@@ -19,7 +19,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 
 MAX_SNAPSHOTS = 4096          # PIVLFN_POD_MAX_SNAPSHOTS
 MAX_MODES = 64
@@ -156,7 +156,7 @@ class FlowPOD:
         self.ld = -(-self.P // 4) * 4
         if self.P >= 1 << 31:
             raise ValueError(f"FlowPOD: {self.P} values per snapshot, must stay below 2^31; use a larger cell")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.device = _accum.cuda_device(device)             # a store on the host is refused by update()
         self.store = torch.zeros([capacity, self.ld], dtype=torch.float32, device=self.device)
         self.empty = torch.zeros([], dtype=torch.int64, device=self.device)
         self.n = 0

@@ -22,7 +22,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 
 KINDS = {"calc_vorticity": 0, "de_vort": 1}          # PIVLFN_FIELDS_CALC_VORTICITY, PIVLFN_FIELDS_DE_VORT
 PLANES = {"calc_vorticity": ("vort", "shear", "normal"), "de_vort": ("vort", "uy", "vx")}
@@ -59,7 +59,7 @@ def _fields_hw(flow, calib, kind: str):
         raise ValueError(f"{kind}: expected a flow [H,W,2], got shape {flow.shape}")
     if not torch.cuda.is_available():
         raise NotImplementedError(f"{kind}: needs a GPU (there is no CPU path)")
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _accum.cuda_device()
     t = torch.from_numpy(np.ascontiguousarray(flow[:, :, :2].transpose(2, 0, 1)))[None].to(dev)
     out = flow_fields(t, calib, kind, torch.float64)[0].cpu().numpy()
     return out[0], out[1], out[2]
@@ -92,51 +92,26 @@ def finalize(acc: np.ndarray, count: int) -> Dict[str, np.ndarray]:
             "cov_uv": acc[4] / n - mu * mv, "mean_vort": mw, "rms_vort": rms(acc[6], mw)}
 
 
-class FlowStats:
+class FlowStats(_accum.FrameAccumulator):
     """Per-pixel running sums over a flow sequence of one size: acc [7,H,W] float64 on the device (SUMS order) and the frame
     count.  update() enqueues one kernel on the current stream and never synchronises the host; result() / save() do."""
 
     def __init__(self, H: int, W: int, calib=1.0, device=None):
-        self.H, self.W, self.calib = int(H), int(W), _args.check_calib(calib)
-        if self.H <= 0 or self.W <= 0:
-            raise ValueError(f"FlowStats: bad size {H} x {W}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise NotImplementedError("FlowStats: GPU devices only")
+        self.calib = _args.check_calib(calib)
+        super().__init__(H, W, device)
         self.acc = torch.zeros([len(SUMS), self.H, self.W], dtype=torch.float64, device=self.device)
-        self.count = 0
 
     def update(self, flow: torch.Tensor) -> None:
         """Add the frames of `flow` [B,2,H,W] (float32, on this device), in batch order."""
         flow = _args.check_flows(flow, "FlowStats.update")
-        if tuple(flow.shape[2:]) != (self.H, self.W) or flow.device != self.device:
-            raise ValueError(f"FlowStats.update: flows {tuple(flow.shape)} on {flow.device}, accumulators [{self.H},{self.W}] on "
-                             f"{self.device}")
+        self._check_mine(flow.shape[2:], flow.device, lambda: f"flows {tuple(flow.shape)} on {flow.device}")
         B = flow.size(0)
-        if B == 0:
-            return
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().pivlfn_flow_stats_accumulate(flow.data_ptr(), self.acc.data_ptr(), B, self.H, self.W, self.calib,
-                                                                _lib.stream_ptr(self.device)), "FlowStats.update")
-        self.count += B
+        self._enqueue(B, (_lib.load().pivlfn_flow_stats_accumulate, flow.data_ptr(), self.acc.data_ptr(), B, self.H, self.W, self.calib))
 
     def merge(self, group=None) -> None:
         """Collective over `group`: every rank ends with the accumulators of all ranks added in rank order (the same bits on every
         rank) and the summed count.  Under gloo the exchange runs on host copies, as dist.gather_flows does."""
-        import torch.distributed as dist
-        world = dist.get_world_size(group)
-        on_dev = dist.get_backend(group) == "nccl"
-        acc = self.acc if on_dev else self.acc.cpu()
-        cnt = torch.tensor([self.count], dtype=torch.int64, device=acc.device)
-        accs = [torch.empty_like(acc) for _ in range(world)]
-        cnts = [torch.empty_like(cnt) for _ in range(world)]
-        dist.all_gather(accs, acc, group=group)
-        dist.all_gather(cnts, cnt, group=group)
-        total = accs[0].clone()
-        for a in accs[1:]:
-            total += a
-        self.acc.copy_(total)
-        self.count = int(sum(int(c.item()) for c in cnts))
+        self.count = _accum.merge_sums([self.acc], self.count, group)
 
     def result(self) -> Dict[str, np.ndarray]:
         """finalize() of the current sums: count, mean_u, mean_v, rms_u, rms_v, cov_uv, mean_vort, rms_vort."""
@@ -144,8 +119,4 @@ class FlowStats:
 
     def save(self, path: str, **extra) -> str:
         """An .npz with result()'s arrays, the raw accumulators (`acc`, SUMS order), `calib` and `extra`; returns the path written."""
-        res = self.result()
-        if not path.endswith(".npz"):
-            path += ".npz"
-        np.savez(path, acc=self.acc.cpu().numpy(), calib=np.float64(self.calib), **extra, **res)
-        return path
+        return _accum.save_npz(path, acc=self.acc.cpu().numpy(), calib=np.float64(self.calib), **extra, **self.result())

@@ -23,7 +23,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 
 
 def check_params(minmax, floor) -> None:
@@ -90,34 +90,22 @@ class Preprocessor:
         return preprocess_frames(frames_u8, self.background, self.minmax, self.floor)
 
 
-class FrameBackground:
+class FrameBackground(_accum.FrameAccumulator):
     """The per-pixel minimum of every frame seen: `min` uint8 [H,W,3] on the device, starting at 255, and the frame count.
     Particles are sparse and bright, so the minimum over a recording is its static background.  update() enqueues one kernel on the
     current stream and never synchronises the host."""
 
     def __init__(self, H: int, W: int, device=None):
-        self.H, self.W = int(H), int(W)
-        if self.H <= 0 or self.W <= 0:
-            raise ValueError(f"FrameBackground: bad size {H} x {W}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise NotImplementedError("FrameBackground: GPU devices only")
+        super().__init__(H, W, device)
         self.min = torch.full([self.H, self.W, 3], 255, dtype=torch.uint8, device=self.device)
-        self.count = 0
 
     def update(self, frames_u8: torch.Tensor) -> None:
         """Take the frames of `frames_u8` [n,H,W,3] (uint8, on the accumulator's device) into the minimum."""
         frames = _check_frames(frames_u8, "FrameBackground.update")
-        if tuple(frames.shape[1:3]) != (self.H, self.W) or frames.device != self.min.device:
-            raise ValueError(f"FrameBackground.update: frames {tuple(frames.shape)} on {frames.device}, background "
-                             f"[{self.H},{self.W},3] on {self.min.device}")
+        self._check_mine(frames.shape[1:3], frames.device, lambda: f"frames {tuple(frames.shape)} on {frames.device}",
+                         "background [{H},{W},3]")
         n = frames.size(0)
-        if n == 0:
-            return
-        with torch.cuda.device(self.min.device):
-            _lib.check(_lib.load().pivlfn_frames_background_min(frames.data_ptr(), self.min.data_ptr(), n, self.H, self.W,
-                                                                _lib.stream_ptr(self.min.device)), "FrameBackground.update")
-        self.count += n
+        self._enqueue(n, (_lib.load().pivlfn_frames_background_min, frames.data_ptr(), self.min.data_ptr(), n, self.H, self.W))
 
     def image(self) -> torch.Tensor:
         """The background, uint8 [H,W,3] on the device (the accumulator itself, not a copy)."""

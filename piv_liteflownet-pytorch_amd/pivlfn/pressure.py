@@ -26,7 +26,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _args, _lib, viz
+from . import _accum, _args, _lib, viz
 
 RUNNING, CONVERGED, BREAKDOWN = 1, 2, 3                  # PIVLFN_PRESSURE_*: the state of a frame
 OK, INVALID, ISOLATED = 0, 1, 2                          # the flag of a node
@@ -154,9 +154,7 @@ class PressureField:
         self.max_iter = 10 * max(self.ch, self.cw) + 50 if max_iter is None else int(max_iter)
         self.sync_every = sync_every
         self.nu_star = self.nu * self.dt / (self.calib * self.calib)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise NotImplementedError("PressureField: GPU devices only")
+        self.device = _accum.cuda_device(device, "PressureField: GPU devices only")
         self.halo = torch.empty([0, 2, self.ch, self.cw], dtype=torch.float32, device=self.device)
         self.count = 0                                    # frames solved so far
 

@@ -27,7 +27,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 
 MAX_SEGMENT = 1024
 WINDOWS = ("hann", "boxcar")
@@ -239,10 +239,7 @@ class TemporalSpectrumResult:
                "window": np.str_(self.window), "detrend": np.str_("none" if self.detrend is None else self.detrend), "fs": np.float64(self.fs),
                "cell": np.int64(self.cell), "frames": np.int64(self.frames), "launched": np.int64(self.launched), "H": np.int64(self.H),
                "W": np.int64(self.W), "freq": self.freq, "psd_uu": self.pooled("uu"), "psd_vv": self.pooled("vv")}
-        if not path.endswith(".npz"):
-            path += ".npz"
-        np.savez(path, **extra, **out)
-        return path
+        return _accum.save_npz(path, **extra, **out)
 
     @classmethod
     def load(cls, path: str) -> "TemporalSpectrumResult":
@@ -264,11 +261,7 @@ class TemporalSpectrum:
         self.H, self.W, self.L, self.window, self.detrend, self.cell, self.fs = int(H), int(W), int(segment), window, detrend, int(cell), float(fs)
         self.hop, self.K, self.N = self.L - self.overlap, self.kmax + 1, self.ch * self.cw
         self.ld = -(-2 * self.N // 4) * 4
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise NotImplementedError("TemporalSpectrum: GPU devices only")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _accum.cuda_device(device, "TemporalSpectrum: GPU devices only")
         self.ring = torch.zeros([self.L, self.ld], dtype=torch.float32, device=self.device)
         self.basis = torch.from_numpy(basis(self.L, window, detrend, self.K)).to(self.device)
         self.acc = torch.zeros([self.K, 4, self.N], dtype=torch.float64, device=self.device)

@@ -26,7 +26,7 @@ from typing import Dict, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 
 TERMS = ("n", "ua", "va", "ub", "vb", "uaua", "vava", "ubub", "vbvb", "uaub", "vavb", "uavb", "vaub", "lll", "ltt")    # acc[d, r, :, y]
 T = {name: i for i, name in enumerate(TERMS)}
@@ -224,7 +224,7 @@ class TwoPointResult:
         return doc
 
 
-class TwoPointStats:
+class TwoPointStats(_accum.FrameAccumulator):
     """Running two-point sums over a flow sequence of one size: acc [2, max_sep+1, 15, H] float64 on the device (TERMS order) and the
     frame count.  update() enqueues one kernel on the current stream and never synchronises the host; result() / save() do.
     `mean`: None, a [2,H,W] tensor or array (held as float64 on the device), or the path of a FlowStats file, whose mean_u and mean_v
@@ -232,57 +232,26 @@ class TwoPointStats:
 
     def __init__(self, H: int, W: int, max_sep: int = 64, step: int = 1, mean=None, device=None):
         check_params(max_sep, step)
-        self.H, self.W, self.max_sep, self.step = int(H), int(W), max_sep, step
-        if self.H <= 0 or self.W <= 0 or self.W > 16384:
-            raise ValueError(f"TwoPointStats: bad size {H} x {W} (positive, at most 16384 columns)")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise NotImplementedError("TwoPointStats: GPU devices only")
-        if isinstance(mean, str):
-            with np.load(mean) as f:
-                mean = np.stack([f["mean_u"], f["mean_v"]])
-        if mean is not None:
-            mean = torch.as_tensor(mean).detach().to(device=self.device, dtype=torch.float64).contiguous()
-            if tuple(mean.shape) != (2, self.H, self.W):
-                raise ValueError(f"TwoPointStats: mean {tuple(mean.shape)}, expected [2,{self.H},{self.W}]")
-        self.mean = mean
+        self.max_sep, self.step = max_sep, step
+        super().__init__(H, W, device, int(W) <= 16384, " (positive, at most 16384 columns)")
+        self.mean = _accum.load_planes(mean, ("mean_u", "mean_v"), "TwoPointStats: mean", self.H, self.W, self.device)
         self.acc = torch.zeros([2, max_sep + 1, len(TERMS), self.H], dtype=torch.float64, device=self.device)
-        self.count = 0
 
     def update(self, flows: torch.Tensor, mask: Optional[torch.Tensor] = None) -> None:
         """Add the frames of `flows` [B,2,H,W] (float32, on this device), in batch order; `mask` [B,H,W]: nonzero = leave the vector out."""
         flows = _args.check_flows(flows, "TwoPointStats.update")
-        if tuple(flows.shape[2:]) != (self.H, self.W) or flows.device != self.device:
-            raise ValueError(f"TwoPointStats.update: flows {tuple(flows.shape)} on {flows.device}, accumulators for [{self.H},{self.W}] on "
-                             f"{self.device}")
+        self._check_mine(flows.shape[2:], flows.device, lambda: f"flows {tuple(flows.shape)} on {flows.device}",
+                         "accumulators for [{H},{W}]")
         mask = _args.check_mask(mask, "TwoPointStats.update", truth=flows)
         B = flows.size(0)
-        if B == 0:
-            return
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().pivlfn_twopoint_accumulate(flows.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                                              self.mean.data_ptr() if self.mean is not None else None, self.acc.data_ptr(),
-                                                              B, self.H, self.W, self.max_sep, self.step, _lib.stream_ptr(self.device)),
-                       "TwoPointStats.update")
-        self.count += B
+        self._enqueue(B, (_lib.load().pivlfn_twopoint_accumulate, flows.data_ptr(), mask.data_ptr() if mask is not None else None,
+                          self.mean.data_ptr() if self.mean is not None else None, self.acc.data_ptr(), B, self.H, self.W,
+                          self.max_sep, self.step))
 
     def merge(self, group=None) -> None:
         """Collective over `group`: every rank ends with the accumulators of all ranks added in rank order (the same bits on every
         rank) and the summed count.  Under gloo the exchange runs on host copies, as FlowStats.merge does."""
-        import torch.distributed as dist
-        world = dist.get_world_size(group)
-        on_dev = dist.get_backend(group) == "nccl"
-        acc = self.acc if on_dev else self.acc.cpu()
-        cnt = torch.tensor([self.count], dtype=torch.int64, device=acc.device)
-        accs = [torch.empty_like(acc) for _ in range(world)]
-        cnts = [torch.empty_like(cnt) for _ in range(world)]
-        dist.all_gather(accs, acc, group=group)
-        dist.all_gather(cnts, cnt, group=group)
-        total = accs[0].clone()
-        for a in accs[1:]:
-            total += a
-        self.acc.copy_(total)
-        self.count = int(sum(int(c.item()) for c in cnts))
+        self.count = _accum.merge_sums([self.acc], self.count, group)
 
     def result(self) -> TwoPointResult:
         return TwoPointResult(self.acc.cpu().numpy(), self.step, self.count)
@@ -301,7 +270,4 @@ class TwoPointStats:
             out[f"pairs_{a}"] = res.pooled("uu", a).n
             for name, order, kind in (("d_ll", 2, "L"), ("d_tt", 2, "T"), ("d_lll", 3, "LLL"), ("d_ltt", 3, "LTT")):
                 out[f"{name}_{a}"] = res.structure(order, kind, a, rows=slice(None))
-        if not path.endswith(".npz"):
-            path += ".npz"
-        np.savez(path, **extra, **out)
-        return path
+        return _accum.save_npz(path, **extra, **out)

@@ -27,7 +27,7 @@ from typing import Dict, List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 from .quality import default_min_count
 
 FEW, FLAT, NO_PEAK, NO_VARIANCE, CENTRE_OUT = 1, 2, 4, 8, 16          # the bits of a flag byte (PIVLFN_UNCERTAINTY_*)
@@ -116,38 +116,26 @@ def flow_uncertainty(img1: torch.Tensor, img2: torch.Tensor, flow: torch.Tensor,
     return FlowUncertainty(u, flag)
 
 
-class UncertaintyStats:
+class UncertaintyStats(_accum.FrameAccumulator):
     """Per-pixel running sums of the squared uncertainties over a sequence of one size: acc [3,H,W] float64 on the device
     (STATS_SUMS order; the third plane counts the pairs that had an uncertainty at the pixel).  update() enqueues one kernel on the
     current stream and never synchronises the host; result() / save() do."""
 
     def __init__(self, H: int, W: int, device=None):
-        self.H, self.W = int(H), int(W)
-        if self.H <= 0 or self.W <= 0:
-            raise ValueError(f"UncertaintyStats: bad size {H} x {W}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise NotImplementedError("UncertaintyStats: GPU devices only")
+        super().__init__(H, W, device)
         self.acc = torch.zeros([len(STATS_SUMS), self.H, self.W], dtype=torch.float64, device=self.device)
-        self.count = 0
 
     def update(self, unc: FlowUncertainty) -> None:
         """Add the pairs of `unc` (a FlowUncertainty on this device), in batch order."""
         u, flag = unc.u, unc.flag
         if not isinstance(u, torch.Tensor) or u.dtype != torch.float32 or not isinstance(flag, torch.Tensor) or flag.dtype != torch.uint8:
             raise TypeError("UncertaintyStats.update: expected a FlowUncertainty (u float32 [B,2,H,W], flag uint8 [B,H,W])")
-        if u.dim() != 4 or tuple(u.shape[1:]) != (2, self.H, self.W) or tuple(flag.shape) != (u.size(0), self.H, self.W) \
-                or u.device != self.device or flag.device != self.device:
-            raise ValueError(f"UncertaintyStats.update: u {tuple(u.shape)} on {u.device} and flag {tuple(flag.shape)} on {flag.device}, "
-                             f"accumulators [{self.H},{self.W}] on {self.device}")
+        self._check_mine(u.shape[2:], u.device, lambda: f"u {tuple(u.shape)} on {u.device} and flag {tuple(flag.shape)} on {flag.device}",
+                         also=u.dim() == 4 and u.size(1) == 2 and tuple(flag.shape) == (u.size(0), self.H, self.W)
+                         and flag.device == self.device)
         B = u.size(0)
-        if B == 0:
-            return
         u, flag = u.detach().contiguous(), flag.contiguous()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().pivlfn_uncertainty_accumulate(u.data_ptr(), flag.data_ptr(), self.acc.data_ptr(), B, self.H, self.W,
-                                                                 _lib.stream_ptr(self.device)), "UncertaintyStats.update")
-        self.count += B
+        self._enqueue(B, (_lib.load().pivlfn_uncertainty_accumulate, u.data_ptr(), flag.data_ptr(), self.acc.data_ptr(), B, self.H, self.W))
 
     @staticmethod
     def finalize(acc, count: int) -> Dict[str, np.ndarray]:
@@ -172,11 +160,7 @@ class UncertaintyStats:
 
     def save(self, path: str, **extra) -> str:
         """An .npz with result()'s arrays, the raw accumulators (`acc`, STATS_SUMS order) and `extra`; returns the path written."""
-        res = self.result()
-        if not path.endswith(".npz"):
-            path += ".npz"
-        np.savez(path, acc=self.acc.cpu().numpy(), **extra, **res)
-        return path
+        return _accum.save_npz(path, acc=self.acc.cpu().numpy(), **extra, **self.result())
 
 
 COVERAGE_SUMS = ("n_x", "n_y", "inside_x", "inside_y", "sum_err2_x", "sum_err2_y", "sum_u2_x", "sum_u2_y")

@@ -23,7 +23,7 @@ from typing import Dict, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 from .postpro import SUMS
 
 MODES = {"flag": 0, "mask": 1, "replace": 2}         # PIVLFN_VALIDATE_FLAG, PIVLFN_VALIDATE_MASK, PIVLFN_VALIDATE_REPLACE
@@ -115,56 +115,29 @@ def finalize_masked(acc: np.ndarray, cnt: np.ndarray, count: int) -> Dict[str, n
             "rms_v": rms(acc[3], mv, n), "cov_uv": acc[4] / n - mu * mv, "mean_vort": mw, "rms_vort": rms(acc[6], mw, nw)}
 
 
-class MaskedFlowStats:
+class MaskedFlowStats(_accum.FrameAccumulator):
     """FlowStats that leaves flagged vectors out: acc [7,H,W] float64 (postpro.SUMS order) and cnt [2,H,W] float64 (COUNTS order) on
     the device.  A frame adds its u, v sums at a pixel only where its flag is 0, and its vorticity sums only where the flags of the
     whole 3 x 3 stencil are 0.  update() enqueues one kernel on the current stream and never synchronises the host."""
 
     def __init__(self, H: int, W: int, calib=1.0, device=None):
-        self.H, self.W, self.calib = int(H), int(W), _args.check_calib(calib)
-        if self.H <= 0 or self.W <= 0:
-            raise ValueError(f"MaskedFlowStats: bad size {H} x {W}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise NotImplementedError("MaskedFlowStats: GPU devices only")
+        self.calib = _args.check_calib(calib)
+        super().__init__(H, W, device)
         self.acc = torch.zeros([len(SUMS), self.H, self.W], dtype=torch.float64, device=self.device)
         self.cnt = torch.zeros([len(COUNTS), self.H, self.W], dtype=torch.float64, device=self.device)
-        self.count = 0
 
     def update(self, flow: torch.Tensor, flag: torch.Tensor) -> None:
         """Add the frames of `flow` [B,2,H,W] (float32, the flows validate_flow was given) under `flag` [B,H,W], in batch order."""
         flow = _args.check_flows(flow, "MaskedFlowStats.update")
         flag = _check_flags(flag, flow, "MaskedFlowStats.update")
-        if tuple(flow.shape[2:]) != (self.H, self.W) or flow.device != self.device:
-            raise ValueError(f"MaskedFlowStats.update: flows {tuple(flow.shape)} on {flow.device}, accumulators [{self.H},{self.W}] on "
-                             f"{self.device}")
+        self._check_mine(flow.shape[2:], flow.device, lambda: f"flows {tuple(flow.shape)} on {flow.device}")
         B = flow.size(0)
-        if B == 0:
-            return
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().pivlfn_flow_stats_accumulate_masked(flow.data_ptr(), flag.data_ptr(), self.acc.data_ptr(),
-                                                                       self.cnt.data_ptr(), B, self.H, self.W, self.calib,
-                                                                       _lib.stream_ptr(self.device)), "MaskedFlowStats.update")
-        self.count += B
+        self._enqueue(B, (_lib.load().pivlfn_flow_stats_accumulate_masked, flow.data_ptr(), flag.data_ptr(), self.acc.data_ptr(),
+                          self.cnt.data_ptr(), B, self.H, self.W, self.calib))
 
     def merge(self, group=None) -> None:
         """Collective over `group`, as FlowStats.merge: sums and counts of all ranks added in rank order, on every rank."""
-        import torch.distributed as dist
-        world = dist.get_world_size(group)
-        on_dev = dist.get_backend(group) == "nccl"
-        both = torch.cat([self.acc, self.cnt])
-        both = both if on_dev else both.cpu()
-        cnt = torch.tensor([self.count], dtype=torch.int64, device=both.device)
-        boths = [torch.empty_like(both) for _ in range(world)]
-        cnts = [torch.empty_like(cnt) for _ in range(world)]
-        dist.all_gather(boths, both, group=group)
-        dist.all_gather(cnts, cnt, group=group)
-        total = boths[0].clone()
-        for a in boths[1:]:
-            total += a
-        self.acc.copy_(total[:len(SUMS)])
-        self.cnt.copy_(total[len(SUMS):])
-        self.count = int(sum(int(c.item()) for c in cnts))
+        self.count = _accum.merge_sums([self.acc, self.cnt], self.count, group)
 
     def result(self) -> Dict[str, np.ndarray]:
         """finalize_masked() of the current sums (MASKED_RESULT): NaN where no frame contributed."""
@@ -172,8 +145,5 @@ class MaskedFlowStats:
 
     def save(self, path: str, **extra) -> str:
         """An .npz with result()'s arrays, the raw accumulators (`acc`, `cnt`), `calib` and `extra`; returns the path written."""
-        res = self.result()
-        if not path.endswith(".npz"):
-            path += ".npz"
-        np.savez(path, acc=self.acc.cpu().numpy(), cnt=self.cnt.cpu().numpy(), calib=np.float64(self.calib), **extra, **res)
-        return path
+        return _accum.save_npz(path, acc=self.acc.cpu().numpy(), cnt=self.cnt.cpu().numpy(), calib=np.float64(self.calib), **extra,
+                               **self.result())

@@ -27,7 +27,7 @@ from typing import Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _accum, _args, _lib
 from .postpro import flow_fields
 
 WHEELS = {"interp": 0, "original": 1}          # PIVLFN_WHEEL_INTERP, PIVLFN_WHEEL_ORIGINAL
@@ -129,7 +129,7 @@ def _numpy_flows(flow, what: str) -> Tuple[torch.Tensor, bool]:
         raise ValueError(f"{what}: expected a flow [H,W,2] or [L,H,W,2], got shape {flow.shape}")
     if not torch.cuda.is_available():
         raise NotImplementedError(f"{what}: needs a GPU (there is no CPU path)")
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _accum.cuda_device()
     seq = flow[None] if flow.ndim == 3 else flow
     return torch.from_numpy(np.ascontiguousarray(seq.transpose(0, 3, 1, 2))).to(dev), flow.ndim == 3
 
@@ -315,9 +315,7 @@ def color_wheel_image(size: int = 151, wheel: str = "interp", order: str = "rgb"
     through the kernel that colours the flows, normalised by 1; white outside the disc."""
     if not _args.is_int(size, 1):
         raise ValueError(f"color_wheel_image: size={size!r} must be a positive integer")
-    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if device.type != "cuda":
-        raise NotImplementedError("color_wheel_image: GPU devices only")
+    device = _accum.cuda_device(device, "color_wheel_image: GPU devices only")
     half = max(size - 1, 1) / 2.0                 # exactly 0 in the middle of an odd size and exactly -1, 1 at the ends
     ax = (torch.arange(size, dtype=torch.float32, device=device) - (size - 1) / 2.0) / half
     v, u = torch.meshgrid(ax, ax, indexing="ij")

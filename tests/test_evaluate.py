@@ -1,6 +1,6 @@
 """CPU: the C ABI of the scoring entry points and their host-side refusals, the numpy restatement of the contract
 (tests/evaluate_restatement.py) against the reference's recorded results and hand-computed cases, the names and signatures of
-src.loss, run.py's --truth argument handling, and ErrorStats' finalisation and merge.  No GPU.
+src.loss, run.py's --truth argument handling, and ErrorStats' finalisation (its merge: tests/test_accumulators.py).  No GPU.
 
 The tolerance against the reference's float64 results is derived, not tuned.  Reference and contract add the same N non-negative
 float64 terms (end-point errors, or |du| + |dv|) in different orders.  A sum of N non-negative terms computed in any order carries a
@@ -12,13 +12,10 @@ import inspect
 import json
 import os
 import re
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import evaluate_restatement as er
 
@@ -321,44 +318,6 @@ def test_finalize_errors_hand_made_accumulators():
         finalize_errors(acc, 0)
     with pytest.raises(ValueError):
         finalize_errors(acc[:5], 3)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _merge_worker(rank, world, port, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from pivlfn.evaluate import ErrorStats
-    st = ErrorStats.__new__(ErrorStats)                   # accumulators injected on the host: the constructor wants a GPU
-    st.H, st.W, st.device = 2, 3, torch.device("cpu")
-    st.acc = torch.arange(36, dtype=torch.float64).view(6, 2, 3) * (rank + 1) + 0.1 * rank
-    st.count = 4 + rank
-    st.merge()
-    want = torch.arange(36, dtype=torch.float64).view(6, 2, 3) + (torch.arange(36, dtype=torch.float64).view(6, 2, 3) * 2 + 0.1)
-    q.put((rank, bool(torch.equal(st.acc, want)) and st.count == 9))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-def test_error_stats_merge_two_rank_gloo():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_merge_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=120) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    assert res == [(0, True), (1, True)]
 
 
 # ---- run.py ----------------------------------------------------------------------------------------------------------------------

@@ -1,16 +1,11 @@
 """CPU: the two-point contract (include/pivlfn.h, pivlfn_twopoint_accumulate) as tests/twopoint_restatement.py states it -- the loop
 definition against the vectorised form bit for bit, tree order included --, the refusals of the C entry point, which all come before
 any launch and so need no GPU, pivlfn.twopoint.TwoPointResult on accumulators the restatement made from sequences whose
-correlation is known in closed form, TwoPointStats.merge between two gloo ranks, and the command line of run.py --twopoint."""
+correlation is known in closed form, and the command line of run.py --twopoint.  (TwoPointStats.merge: tests/test_accumulators.py.)"""
 import math
-import multiprocessing as mp
-import os
-import socket
 
 import numpy as np
 import pytest
-import torch
-import torch.distributed as dist
 
 import twopoint_restatement as tr
 
@@ -260,46 +255,6 @@ def test_taylor_fit_recovers_the_noise_share_within_the_sampling_error():
     assert abs(clean.noise - (1.0 - kappa)) <= 4 * _bound(0.0) and abs(fit.microscale / clean.microscale - 1.0) <= 4 * tol
     got = tr.parabola_fit(res.pooled("uu", "x").rho, 1)
     assert np.allclose(got, fit, rtol=1e-10)
-
-
-# ---- merge -------------------------------------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _merge_worker(rank, world, port, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from pivlfn.twopoint import TwoPointStats
-    st = TwoPointStats.__new__(TwoPointStats)             # accumulators injected on the host: the constructor wants a GPU
-    base = torch.arange(2 * 3 * 15 * 4, dtype=torch.float64).view(2, 3, 15, 4)
-    st.H, st.W, st.max_sep, st.step, st.mean, st.device = 4, 5, 2, 1, None, torch.device("cpu")
-    st.acc = base * (rank + 1) + 0.1 * rank
-    st.count = 4 + rank
-    st.merge()
-    want = base + (base * 2 + 0.1)                        # rank 0 + rank 1, in rank order
-    q.put((rank, bool(torch.equal(st.acc, want)) and st.count == 9))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-def test_twopoint_stats_merge_two_rank_gloo():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_merge_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=120) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    assert res == [(0, True), (1, True)]
 
 
 def test_run_py_twopoint_flags_parse_and_are_checked_before_a_gpu_is_needed(tmp_path):
