@@ -1160,6 +1160,33 @@ int pivlfn_smooth_pcg(void *workspace, size_t workspace_bytes, int F, int H, int
 int pivlfn_smooth_read(const void *workspace, size_t workspace_bytes, int F, int H, int W, double *z, float *z32, unsigned char *filled,
                        double *status, void *stream);
 
+/* ---- ensemble correlation: the window sums of sum-of-correlation PIV (Meinhart, Wereley & Santiago 2000), the displacement read
+ * straight from the images and averaged over a sequence.  Added without an ABI bump (additive).  Launches only on `stream`, no
+ * allocation, no host synchronisation, capturable into a graph.  One launch; B = 0 returns success without one.
+ *
+ * a, b: [B,H,W] bytes, any address;  offset: [2,ny,nx] int32, plane 0 ox and plane 1 oy, or NULL for no pre-shift;
+ * sums: [ny,nx,P,P,3] int64, sums_a: [ny,nx,2] int64, with P = 2*search + 1.
+ * Grid: window (j, i) of a has its top-left pixel at y_j = search + j*step, x_i = search + i*step;
+ *   ny = (H - window - 2*search)/step + 1 (integer division), nx likewise from W; both are at least 1.
+ *   Window (j, i) of b for displacement (dy, dx), each in -search..search, has its top-left pixel at (y_j + oy + dy, x_i + ox + dx).
+ * A window is OUTSIDE when  y_j + oy - search < 0  or  y_j + oy + search + window > H,  or the same in x with ox and W: it adds nothing,
+ *   in this call or any other.  Every other window adds, over its window^2 pixels and the B frames, as exact integers:
+ *       sums_a[j][i][0..1]                       += sum A, sum A^2
+ *       sums[j][i][dy+search][dx+search][0..2]   += sum B, sum B^2, sum A*B
+ *   The call ADDS to what sums and sums_a hold (the caller zeroes them once): a plain 64-bit load, add and store by the one lane that
+ *   owns the entry, no atomics; the stream orders successive calls.  A per-frame window sum fits 32 bits (255^2 * 128^2 = 1 065 369 600)
+ *   and is widened to 64 bits before the frames are added, so a frame adds the same integers alone and inside any batch.
+ * Ranges: window a multiple of 4 in 8..128;  search 1..32;  step >= 1;  H*W < 2^31;  B <= 65535.
+ * Errors (PIVLFN_ERR_ARG, before any launch): a null a, b, sums or sums_a;  an output that overlaps an input or the other output;  a
+ * value out of the ranges above;  H or W smaller than window + 2*search.
+ * Launch plan: a lane owns four vertically adjacent displacements of one window, so a window has items = ceil(P / 4) * P of them;
+ * ny*nx x ceil(items / T) workgroups of T threads, T = items rounded up to whole waves and kept within 128..512 (one block up to
+ * search 21, three at search 32).  Windows of 16, 32 and 64 pixels have a kernel of their own, every other window shares one.  The
+ * workgroup stages (window + 6) * window + (window + 2*search) * (window + 2*search rounded up to 4, + 4) bytes: at most 54784, no
+ * opt-in. */
+int pivlfn_ensemble_corr(const unsigned char *a, const unsigned char *b, const int *offset, long long *sums, long long *sums_a,
+                         int B, int H, int W, int window, int step, int search, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -425,6 +425,12 @@ int pivlfn_dewarp_frames(const void *frames, void *out, int is_f32, int B, int H
     return launch_dewarp_frames(frames, out, is_f32, B, H, W, A, x0, y0, mode, fill, (hipStream_t)stream);
 }
 
+int pivlfn_ensemble_corr(const unsigned char *a, const unsigned char *b, const int *offset, long long *sums, long long *sums_a,
+                         int B, int H, int W, int window, int step, int search, void *stream)
+{
+    return launch_ensemble_corr(a, b, offset, sums, sums_a, B, H, W, window, step, search, (hipStream_t)stream);
+}
+
 int pivlfn_create(const pivlfn_tensor *tensors, int n_tensors, float starting_scale, int lowest_level,
                   const float rgb_mean[6], pivlfn_net **out)
 {

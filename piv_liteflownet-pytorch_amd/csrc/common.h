@@ -421,6 +421,10 @@ int launch_target_points(const float *r, int B, int H, int W, float threshold, i
 int launch_dewarp_frames(const void *frames, void *out, int is_f32, int B, int H, int W, const double *A, double x0, double y0, int mode,
                          double fill, hipStream_t st);
 
+// ---- ensemble correlation (ensemble.hip): the integer window sums of sum-of-correlation PIV, added over frames and calls -----------------
+int launch_ensemble_corr(const unsigned char *a, const unsigned char *b, const int *offset, long long *sums, long long *sums_a, int B,
+                         int H, int W, int window, int step, int search, hipStream_t st);
+
 // ---- image pre-processing (preproc.hip): [n,H,W,3] uint8 frames -> background minimum [H,W,3], network input [n,3,H,W] fp32 --------
 int launch_frames_background_min(const unsigned char *frames, unsigned char *bg, int n, int H, int W, hipStream_t st);
 int launch_frames_preprocess(const unsigned char *frames, const unsigned char *bg, float *out, int n, int H, int W, int k, int floor,

@@ -20,6 +20,7 @@ from .pod import FlowPOD, PODResult                                     # noqa: 
 from .twopoint import TwoPointResult, TwoPointStats                     # noqa: F401
 from .distribution import DistributionResult, FlowDistribution          # noqa: F401
 from .spectrum import TemporalSpectrum, TemporalSpectrumResult          # noqa: F401
+from .ensemble import EnsembleCorrelation, EnsembleResult, predictor_offsets  # noqa: F401
 from .pressure import PressureField, PressureResult                     # noqa: F401
 from .smooth import Smoothed, dct2, smooth_flow, smooth_param, smooth_wavelength, weights_from_uncertainty  # noqa: F401
 from .calibrate import (calibrate_camera, dewarp_frames, find_markers, fit_mapping, gen_template, index_lattice,  # noqa: F401
@@ -37,6 +38,7 @@ __all__ = ["FunctionCorrelation", "ModuleCorrelation", "LiteFlowNet", "LiteFlowN
            "vortex_gamma", "VortexField", "FlowMap", "FTLEField", "OUT", "LOST", "UNDEFINED", "FlowPOD", "PODResult", "TwoPointStats", "TwoPointResult",
            "FlowDistribution", "DistributionResult",
            "TemporalSpectrum", "TemporalSpectrumResult", "PressureField", "PressureResult",
+           "EnsembleCorrelation", "EnsembleResult", "predictor_offsets",
            "smooth_flow", "Smoothed", "smooth_param", "smooth_wavelength", "weights_from_uncertainty", "dct2",
            "gen_template", "template_match", "target_points", "find_markers", "index_lattice", "fit_mapping", "dewarp_frames", "calibrate_camera",
            "write_coeff", "ParticleImageGen", "ParticleImages", "PairParticles", "displace_particles", "render_particles", "BAD"]

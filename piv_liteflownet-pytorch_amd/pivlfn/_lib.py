@@ -108,6 +108,7 @@ SIGNATURES = {
                              + [ctypes.c_size_t, ctypes.c_void_p]),
     "pivlfn_dewarp_frames": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_double)]
                              + [ctypes.c_double] * 2 + [ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
+    "pivlfn_ensemble_corr": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
     "pivlfn_create": (ctypes.c_int, [ctypes.POINTER(Tensor), ctypes.c_int, ctypes.c_float, ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_void_p)]),
     "pivlfn_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "pivlfn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_void_p] + [ctypes.c_int] * 3),

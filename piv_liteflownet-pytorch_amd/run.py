@@ -14,6 +14,7 @@
                 [--pressure [CELL] [--pressure-rho R] [--pressure-nu NU] [--pressure-dt DT] [--pressure-calib C] [--pressure-tol T]
                  [--pressure-image]]
                 [--smooth [WAVELENGTH] [--smooth-tol T]]
+                [--ensemble [WINDOW] [--ensemble-step S] [--ensemble-search R] [--ensemble-predictor STATS.npz]]
 
 Flags of the reference (run.py:24-42): --start/-s, --num_images/-n, --is_pair/-p, --brightness/-b, --contrast/-c,
 --model/-m, --version/-v, --input/-i, --output/-o, --no_cuda.  Output tree (run.py:232-266):
@@ -94,6 +95,15 @@ Differences, all deliberate:
     WAVELENGTH pixels (default 8) keep half their amplitude; `--smooth-tol T` is the relative residual to reach (default 1e-8).  The
     .flo files and every later stage get the smoothed, complete flow; the parameters and per pair the filled vectors, iterations,
     residual and converged go to <save>/smooth.json.  A single process, not with -b/-c;
+  * `--ensemble [WINDOW]` measures the mean displacement of every input directory a second way, straight from the frames the
+    network was given (after any pre-processing) and without the weights: ensemble correlation on the device
+    (pivlfn.ensemble.EnsembleCorrelation: the correlation planes of WINDOW x WINDOW interrogation windows, default 32, every
+    `--ensemble-step S` pixels, default half the window, at the displacements -R..R of `--ensemble-search R`, default 8, added over all
+    pairs; one peak per window is read from the sum).  `--ensemble-predictor STATS.npz` names the per-pixel mean of an earlier --stats
+    run: it supplies a whole-pixel pre-shift per window, for displacements beyond R, and is the field the result is compared with.
+    Writes <save>/ensemble.npz (the integer sums and every parameter), <save>/ensemble.flo (two bands on the window lattice, 1e10
+    where a window is flagged) and <save>/ensemble.json (the parameters, the pairs, the flag counts, the median peak height and peak
+    ratio, and with a predictor the bias and rms of the difference).  A single process, not with -b/-c;
   * `--pod K` decomposes the flows of every input directory after it has been processed (pivlfn.pod.FlowPOD, snapshot POD: the
     Gram matrix of the flows in float64 on the device, its eigenvectors on the host): the first K modes, the mean, the coefficients
     and the energy fractions go to <save>/pod.npz, one line per mode is printed, and with --color the modes are drawn as
@@ -133,8 +143,9 @@ from pivlfn import Network                               # noqa: E402
 from pivlfn import flowmap, quality, synth, uncertainty, viz, vortex  # noqa: E402
 from pivlfn.datasets import Run, image_files_from_folder, pair_files     # noqa: E402
 from pivlfn.dist import shard_bounds                     # noqa: E402
+from pivlfn import _accum, ensemble                     # noqa: E402
 from pivlfn.evaluate import ErrorStats, flow_errors, level_errors        # noqa: E402
-from pivlfn.flo import FloWriter, flowname_modifier      # noqa: E402
+from pivlfn.flo import FloWriter, flowname_modifier, write_flow     # noqa: E402
 from pivlfn.imagemod import mod_name                     # noqa: E402
 from pivlfn.inference import estimate                    # noqa: E402
 from pivlfn.pipeline import PairLoader, stream_pairs     # noqa: E402
@@ -340,7 +351,20 @@ parser.add_argument("--smooth", type=float, nargs="?", const=8.0, default=None, 
                          "amplitude; the .flo files and every later stage get the smoothed flow, the summaries go to <save>/smooth.json")
 parser.add_argument("--smooth-tol", type=float, default=None, metavar="T",
                     help="with --smooth: the relative residual at which the conjugate gradients stop (default 1e-8)")
+parser.add_argument("--ensemble", type=int, nargs="?", const=32, default=None, metavar="WINDOW",
+                    help="ensemble correlation of the frames of every input directory on the device (pivlfn.ensemble.EnsembleCorrelation; "
+                         "not a reference flag; not with -b/-c, single process only): the correlation planes of WINDOW x WINDOW "
+                         "interrogation windows (a multiple of 4 in 8..128, default 32) added over all pairs, one displacement per "
+                         "window to <save>/ensemble.flo, the sums to <save>/ensemble.npz, the summary to <save>/ensemble.json")
+parser.add_argument("--ensemble-step", type=int, default=None, metavar="S",
+                    help="with --ensemble: the pixels between two windows (default half the window)")
+parser.add_argument("--ensemble-search", type=int, default=None, metavar="R",
+                    help="with --ensemble: the largest displacement looked at around the pre-shift, 1..32 pixels (default 8)")
+parser.add_argument("--ensemble-predictor", type=str, default=None, metavar="FILE",
+                    help="with --ensemble: a stats.npz of an earlier --stats run over the same frames; its mean_u and mean_v, averaged "
+                         "over each window and rounded, pre-shift the window of the second frame, and the result is compared with them")
 SMOOTH_FLAGS = ("smooth", "smooth_tol")
+ENSEMBLE_FLAGS = ("ensemble", "ensemble_step", "ensemble_search", "ensemble_predictor")
 PRESSURE_FLAGS = ("pressure", "pressure_rho", "pressure_nu", "pressure_dt", "pressure_calib", "pressure_tol", "pressure_image")
 SPECTRUM_FLAGS = ("spectrum", "spectrum_overlap", "spectrum_cell", "spectrum_fps", "spectrum_image")
 TWOPOINT_FLAGS = ("twopoint", "twopoint_step", "twopoint_mean")
@@ -351,7 +375,7 @@ UNCERTAINTY_FLAGS = ("uncertainty", "uncertainty_lag", "uncertainty_image", "unc
 VORTEX_FLAGS = ("vortex", "vortex_spacing", "vortex_image")
 PICTURE_FLAGS = ("color", "color_max", "color_wheel", "vort_image", "vort_max", "quiver")
 FTLE_FLAGS = ("ftle", "ftle_steps", "ftle_image", "ftle_max")
-VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + UNCERTAINTY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + PDF_FLAGS + SPECTRUM_FLAGS + PRESSURE_FLAGS + SMOOTH_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
+VIZ_FLAGS = PICTURE_FLAGS + QUALITY_FLAGS + UNCERTAINTY_FLAGS + VORTEX_FLAGS + POD_FLAGS + FTLE_FLAGS + TWOPOINT_FLAGS + PDF_FLAGS + SPECTRUM_FLAGS + PRESSURE_FLAGS + SMOOTH_FLAGS + ENSEMBLE_FLAGS      # every flag of a further output beside the .flo: absent from args.txt unless used
 TRUTH_FLAGS = ("truth", "truth_levels")
 
 
@@ -644,6 +668,50 @@ class TwoPoint(Stage):
         scales = ", ".join(f"{key} {summary[key]['integral_scale']:.2f}{'+' if summary[key]['truncated'] else ''}"
                            for key in ("uu_x", "uu_y", "vv_x", "vv_y"))
         print(f"Two-point statistics of {self.stats.count} flows: integral scales in pixels {scales} ('+': the correlation did not reach zero)")
+
+
+class Ensemble(Stage):
+    """Adds the frames of every batch -- the tensors the network was given -- to an EnsembleCorrelation, created at the first batch's
+    size; with a predictor file its window means are the pre-shift and the field the result is compared with.  finish() writes the
+    sums, the displacement lattice and the summary."""
+
+    def __init__(self, window, step, search, predictor, file, flo_file, json_file):
+        self.window, self.step, self.search, self.predictor = window, step, search, predictor
+        self.file, self.flo_file, self.json_file = file, flo_file, json_file
+        self.acc, self.mean = None, None
+
+    def __call__(self, batch):
+        if self.acc is None:
+            H, W = batch.img1.shape[2:]
+            try:
+                offset = None
+                if self.predictor is not None:
+                    self.mean = _accum.load_planes(self.predictor, ("mean_u", "mean_v"), "EnsembleCorrelation: predictor", H, W, "cpu").numpy()
+                    offset = ensemble.predictor_offsets(self.mean, self.window, self.step, self.search)
+                self.acc = ensemble.EnsembleCorrelation(H, W, self.window, self.step, self.search, offset, device=batch.img1.device)
+            except ValueError as e:
+                raise SystemExit(f"run.py: --ensemble: {e}")
+        self.acc.update(batch.img1, batch.img2)
+
+    def finish(self, names, ctx):
+        """<save>/ensemble.npz (EnsembleResult.save), <save>/ensemble.flo (the displacement on the window lattice, 1e10 where a window
+        is flagged) and <save>/ensemble.json (the parameters, EnsembleResult.summary() and, with a predictor, the comparison); one
+        line with the counts."""
+        if self.acc is None:
+            return
+        res = self.acc.result()
+        res.save(self.file)
+        lattice = np.where(res.flag[None] != 0, 1e10, res.displacement).astype(np.float32)
+        write_flow(np.ascontiguousarray(lattice.transpose(1, 2, 0)), self.flo_file)
+        summary = res.summary()
+        doc = {"window": self.window, "step": self.step, "search": self.search, "predictor": self.predictor, "rows": res.ny,
+               "columns": res.nx, "summary": summary}
+        if self.mean is not None:
+            doc["comparison"] = {k: v for k, v in res.compare(self.mean).items() if k != "difference"}
+        write_json(self.json_file, json_strict(doc), allow_nan=False)
+        print(f"Ensemble correlation of {res.frames} pairs: {summary['valid']} of {summary['windows']} windows of {self.window} px give a "
+              f"displacement, median peak height {summary['median_height']:.3f}, median peak ratio {summary['median_ratio']:.1f} "
+              f"-> '{self.flo_file}'")
 
 
 def pdf_params(args):
@@ -1264,6 +1332,10 @@ def make_stages(args, layout, inputdir, net, device, rank, world, truth_paths=No
     if args.twopoint is not None:
         stages.append(TwoPoint(args.twopoint, args.twopoint_step or 1, args.twopoint_mean, layout.sibling("twopoint.npz"),
                                layout.sibling("twopoint.json")))
+    if args.ensemble is not None:
+        stages.append(Ensemble(args.ensemble, args.ensemble_step or args.ensemble // 2, 8 if args.ensemble_search is None else args.ensemble_search,
+                               args.ensemble_predictor, layout.sibling("ensemble.npz"), layout.sibling("ensemble.flo"),
+                               layout.sibling("ensemble.json")))
     if args.pdf is not None:
         stages.append(Distribution(pdf_params(args), args.pdf_mean, args.pdf_normalise, args.pdf_image, layout.sibling("pdf.npz"),
                                    layout.sibling("pdf.json"), layout.sibling("pdf_joint.png")))
@@ -1444,7 +1516,8 @@ def args_lines(args) -> List[str]:
                     (args.pod is None and k in POD_FLAGS) or (args.ftle is None and k in FTLE_FLAGS) or
                     (args.pdf is None and k in PDF_FLAGS) or
                     (args.twopoint is None and k in TWOPOINT_FLAGS) or (args.spectrum is None and k in SPECTRUM_FLAGS) or
-                    (args.pressure is None and k in PRESSURE_FLAGS) or (args.smooth is None and k in SMOOTH_FLAGS))]
+                    (args.pressure is None and k in PRESSURE_FLAGS) or (args.smooth is None and k in SMOOTH_FLAGS) or
+                    (args.ensemble is None and k in ENSEMBLE_FLAGS))]
 
 
 def load_weights(args) -> Tuple[dict, str]:
@@ -1481,6 +1554,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         checked("--twopoint: ", check_twopoint, args.twopoint, 1 if args.twopoint_step is None else args.twopoint_step)
         if args.twopoint_mean is not None and not os.path.isfile(args.twopoint_mean):
             raise SystemExit(f"run.py: --twopoint-mean '{args.twopoint_mean}' is not a file")
+    if _used(args, ENSEMBLE_FLAGS[1:]) and args.ensemble is None:
+        raise SystemExit("run.py: --ensemble-step, --ensemble-search and --ensemble-predictor need --ensemble")
+    if args.ensemble is not None:
+        refuse_mods(args, "--ensemble is")
+        refuse_sharded("--ensemble", "run.py has no process group to merge the sums of the ranks")
+        checked("--ensemble: ", ensemble.check_params, args.ensemble, args.ensemble // 2 if args.ensemble_step is None else args.ensemble_step,
+                8 if args.ensemble_search is None else args.ensemble_search)
+        if args.ensemble_predictor is not None and not os.path.isfile(args.ensemble_predictor):
+            raise SystemExit(f"run.py: --ensemble-predictor '{args.ensemble_predictor}' is not a file")
     if _used(args, PDF_FLAGS[1:]) and args.pdf is None:
         raise SystemExit("run.py: --pdf-range, --pdf-mean, --pdf-normalise, --pdf-hole and --pdf-image need --pdf")
     if args.pdf is not None:

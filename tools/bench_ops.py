@@ -7,6 +7,7 @@
   python tools/bench_ops.py spectrum                                  (pivlfn_spectrum_accumulate, and the same sums from snapshot_project + torch)
   python tools/bench_ops.py pressure                                  (pivlfn_pressure_cg: us per iteration at 256^2 x 8 and 1024^2 x 1)
   python tools/bench_ops.py calibrate                                 (pivlfn_template_match, _target_points, _dewarp_frames at --size squared)
+  python tools/bench_ops.py ensemble                                  (pivlfn_ensemble_corr, 8 frames at --size squared, against its integer-MAC bound)
 Times N back-to-back launches between two events on the current stream (so each figure includes one ~1.5 us
 kernel boundary) and checks that all variants agree.
 """
@@ -702,10 +703,32 @@ def bench_calibrate(args):
               f"byte bound {bound:6.2f} us = {100 * bound / med:5.1f} % of the time", flush=True)
 
 
+def bench_ensemble(args):
+    """pivlfn_ensemble_corr on 8 frames of --size squared (DESIGN quotes --size 1024), window 32, step 16, search 8, on the production
+    library, against the integer-MAC bound nwin P^2 window^2 B (the A.B products alone) at the v_dot4_u32_u8 rate."""
+    import numpy as np
+    from pivlfn import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    S, B, window, step, search = args.size, 8, 32, 16, 8
+    n1 = (S - window - 2 * search) // step + 1
+    P = 2 * search + 1
+    rng = np.random.default_rng(0)
+    a, b = (torch.from_numpy(rng.integers(0, 256, (B, S, S), dtype=np.uint8)).to(dev) for _ in range(2))
+    sums = torch.zeros(n1, n1, P, P, 3, dtype=torch.int64, device=dev)
+    sums_a = torch.zeros(n1, n1, 2, dtype=torch.int64, device=dev)
+    n, med = time_it(lambda: _lib.check(lib.pivlfn_ensemble_corr(a.data_ptr(), b.data_ptr(), None, sums.data_ptr(), sums_a.data_ptr(), B, S, S, window,
+                                                                 step, search, st)), n=20, rounds=7)
+    bound = float(n1 * n1) * P * P * window * window * B / INT_MAC_PER_S * 1e6
+    print(f"ensemble_corr {B}x{S}x{S}, window {window}, step {step}, search {search} ({n1 * n1} windows): min {n:8.1f} us, median {med:8.1f} us; "
+          f"integer-MAC bound {bound:6.1f} us = {100 * bound / med:5.1f} % of the time", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["warp_corr", "wc_ablate", "conv", "conv_stamps", "head", "preproc", "evaluate", "twopoint", "distribution", "spectrum", "pressure",
-                                     "calibrate"])
+                                     "calibrate", "ensemble"])
     ap.add_argument("--once", action="store_true", help="preproc: one launch per shape, for a kernel trace")
     ap.add_argument("--filter", default="")
     ap.add_argument("--tune3", type=int, default=0, help="ablation mask of the fp16 conv kernel (pivlfn_tune(3, mask))")
@@ -720,4 +743,4 @@ if __name__ == "__main__":
     a = ap.parse_args()
     {"conv_stamps": bench_conv_stamps, "warp_corr": bench_warp_corr, "wc_ablate": bench_wc_ablate, "conv": bench_conv, "head": bench_head,
      "preproc": bench_preproc, "evaluate": bench_evaluate, "twopoint": bench_twopoint, "distribution": bench_distribution, "spectrum": bench_spectrum, "pressure": bench_pressure,
-     "calibrate": bench_calibrate}[a.what](a)
+     "calibrate": bench_calibrate, "ensemble": bench_ensemble}[a.what](a)
