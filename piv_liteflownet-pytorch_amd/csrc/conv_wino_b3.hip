@@ -35,7 +35,10 @@
 //     weight fragments of plane k + 1 are produced / in flight, and the row-combined columns of the NEXT step replace the current
 //     ones as they die (column 0 after plane 0, 3 after plane 3, 1 and 2 after plane 1): one set of 64 column registers;
 //   * epilogue as conv_wino.hip: column half of A^T M A in registers, row half across the four waves through LDS, bias / LeakyReLU,
-//     16-byte NHWC stores.
+//     16-byte NHWC stores.  It is bound by what its one wave per SIMD can issue, not by LDS or store latency: a form that overlaps the
+//     exchange's round trips (four double-buffered passes) and reads the next tile's first image under the last one measures the same
+//     or slower (tools/kernels/conv_wino_b3_boundary_passes.patch.txt, profiles/b3_boundary_passes_ab.log), taking instructions out
+//     of it -- store offsets by a row step, the activation as a maximum -- 2400 cycles of a tile's 9600.
 // Summation order per output value: K steps ascending; inside a step the piece pairs smallest first (fixed order); the matrix core
 // adds the 16 products of an instruction in its own fixed order.  Independent of the grid and of the batch.
 #include <algorithm>
@@ -342,6 +345,12 @@ __global__ __launch_bounds__(256, 1) void conv_wino_b3_kernel(const ConvParamsW 
 #ifndef B3_PHASED
 #define B3_PHASED 0
 #endif
+#ifndef B3_XADDR
+// The store offsets of the epilogue as one product per tile and a row step per store (1) or as an expression of the tile row (0).  The
+// eight- and nine-term instances keep the expression: with the other form the register allocator spills 18 staged patch registers in
+// their K loop (they load the patch a phase later, B3_PATCH_POS) -- no spill in any instance
+#define B3_XADDR (TERMS == 6)
+#endif
 #if B3_PHASED
 #define B3_WAITVM()                                                                               \
     do {                                                                                          \
@@ -435,7 +444,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino_b3_kernel(const ConvParamsW 
 
 #ifdef PIVLFN_STAMPS
     // tools build: ticks (s_memtime) of wave 0 per category, summed over the workgroup's tiles: 0 tile start, 1 full steps, 2 last step,
-    // 3 epilogue, 4 load-stream tile switch, 5 whole, 6 tiles, 7 steps, 8-11 the four phases of the full steps, 12 their closing barrier
+    // 3 rest of the epilogue, 4 load-stream tile switch, 5 whole, 6 tiles, 7 steps, 8-11 the four phases of the full steps, 12 their closing
+    // barrier, 13-15 the epilogue: column halves + exchange writes + barriers, exchange reads + row halves + stores, zeroing (if not early)
     const bool stamp_ = p.stamps != nullptr && wave == 0;
     unsigned long long tk_ = 0, t_begin_ = 0, sd_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (stamp_) t_begin_ = tk_ = __builtin_amdgcn_s_memtime();
@@ -532,6 +542,47 @@ __global__ __launch_bounds__(256, 1) void conv_wino_b3_kernel(const ConvParamsW 
         const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(p.out + orow * p.out_stride, 0,
             (unsigned)min(((size_t)(p.H - y0) * p.W) * p.out_stride * 4, (size_t)0x7fffffff), 0x00020000);
         const int ox = x0 + 2 * rts + qq;
+        // A lane's store offsets: ONE product per channel block and tile, then a scalar row step per store (as an expression of the
+        // tile row the compiler put a v_mul_lo_u32, a v_readlane and a branch in front of every store).  A lane outside the image or past
+        // cout_store starts from WOOB and stays out of range: 7 row steps are below 2^31 (choose_conv_wb: 16 output rows < 2 GiB).
+        const unsigned rstep = 2u * (unsigned)p.W * (unsigned)p.out_stride * 4u;      // bytes from a tile row to the next: two image rows
+        unsigned vb[2];
+        const int chq = ng * 64 + 4 * rc4;      // the lane's channel quad in channel block 0
+// (made in front of the stores that use them, from the laundered lane id: not live across the column half)
+#define B3_XVB()                                                                                  \
+    if (B3_XADDR) _Pragma("unroll") for (int nw = 0; nw < 2; ++nw) {                              \
+        const int ch = chq + 32 * nw;                                                             \
+        vb[nw] = ox < p.W && ch < p.cout_store ? (unsigned)((pp * p.W + ox) * p.out_stride + ch) * 4u : WOOB; \
+    }
+        const float sg = pp ? -1.f : 1.f;
+        const float slope = p.lrelu ? 0.1f : 1.f;      // lrelu01(v) = max(v, 0.1 v) and v = max(v, 1 v): two instructions per value, no compare / select
+#ifdef B3_ABL_NOSTORE      // timing build: every store out of range (dropped by the range check)
+#define B3_XROWOK(R) (p.H < 0)
+#else
+#define B3_XROWOK(R) (y0 + 2 * (R) + pp < p.H)
+#endif
+// column half of rows 4 RG .. 4 RG + 3 of the accumulators (MB, NW) -> R0 = (M0 + M1) + M2, R1 = (M1 - M2) - M3 (scalar additions: the
+// packed form costs more of the wave's issue time than the pair, see the file header)
+#define B3_XCOL(MB, NW, RG, R0, R1)                                                               \
+    _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                               \
+        const float m0_ = acc[0][MB][NW][4 * (RG) + e], m1_ = acc[1][MB][NW][4 * (RG) + e], m2_ = acc[2][MB][NW][4 * (RG) + e], m3_ = acc[3][MB][NW][4 * (RG) + e]; \
+        R0[e] = (m0_ + m1_) + m2_;                                                                \
+        R1[e] = (m1_ - m2_) - m3_;                                                                \
+    }
+// row half of tile row R (0..7), channel block NW from the three exchange rows X0, X1, X2: pp = 0: (R_0 + R_1) + R_2;  pp = 1: (R_1 - R_2) - R_3
+// (sg * x is exact), bias, activation, store: eight lanes hold one pixel's 32 channels
+#define B3_XROW(X0, X1, X2, NW, R)                                                                \
+    do {                                                                                          \
+        f32x4 y_;                                                                                 \
+        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                           \
+            const float v_ = __builtin_fmaf(sg, X2[e], __builtin_fmaf(sg, X1[e], X0[e])) + bias4[NW][e]; \
+            y_[e] = __builtin_fmaxf(v_, slope * v_);                                              \
+        }                                                                                         \
+        const unsigned dead_ = B3_XROWOK(R) ? 0u : WOOB;      /* a tile row below the image (wave-uniform) */ \
+        const unsigned off_ = B3_XADDR ? vb[NW] + (unsigned)(R) * rstep                           \
+                                       : (ox < p.W && chq + 32 * (NW) < p.cout_store ? (unsigned)(((2 * (R) + pp) * p.W + ox) * p.out_stride + chq + 32 * (NW)) * 4u : WOOB); \
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y_), ors, (int)(off_ | dead_), 0, 0); \
+    } while (0)
 #ifdef B3_ABL_NOEPI      // timing build: no output transform at all
         if (p.H < 0)
 #endif
@@ -543,13 +594,11 @@ __global__ __launch_bounds__(256, 1) void conv_wino_b3_kernel(const ConvParamsW 
             for (int nw = 0; nw < 2; ++nw)
 #pragma unroll
                 for (int rg = 0; rg < 4; ++rg) {
-                    f32x4 m[4];
-#pragma unroll
-                    for (int jp = 0; jp < 4; ++jp)
-                        m[jp] = f32x4{acc[jp][mb][nw][4 * rg + 0], acc[jp][mb][nw][4 * rg + 1], acc[jp][mb][nw][4 * rg + 2], acc[jp][mb][nw][4 * rg + 3]};
+                    f32x4 r0, r1;
+                    B3_XCOL(mb, nw, rg, r0, r1)
                     const int wq = wpos + ((2 * rg + eg) ^ (en & 7));
-                    xch[((nw * 4 + wave) * 2 + 0) * 256 + wq] = (m[0] + m[1]) + m[2];
-                    xch[((nw * 4 + wave) * 2 + 1) * 256 + wq] = (m[1] - m[2]) - m[3];
+                    xch[((nw * 4 + wave) * 2 + 0) * 256 + wq] = r0;
+                    xch[((nw * 4 + wave) * 2 + 1) * 256 + wq] = r1;
                 }
 #if B3_ZERO_EARLY
 #pragma unroll
@@ -563,10 +612,9 @@ __global__ __launch_bounds__(256, 1) void conv_wino_b3_kernel(const ConvParamsW 
             BSTAMP(13 + 0 * mb);
             // branch-free (the row pair is a wave-uniform offset and a sign), B3_KB tile rows' reads in flight together: with one wave per
             // SIMD every LDS round trip that is waited for on its own is exposed
-            const float sg = pp ? -1.f : 1.f;
+            B3_XVB()
 #pragma unroll
             for (int nw = 0; nw < 2; ++nw) {
-                const int ch = (ng * 2 + nw) * 32 + 4 * rc4;
 #pragma unroll
                 for (int k0 = 0; k0 < 4; k0 += B3_KB) {
                     f32x4 xv[B3_KB][3];
@@ -575,23 +623,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_b3_kernel(const ConvParamsW 
 #pragma unroll
                         for (int i = 0; i < 3; ++i) xv[kk][i] = xch[((nw * 4 + pp + i) * 2 + qq) * 256 + (k0 + kk) * 64 + ln];
 #pragma unroll
-                    for (int kk = 0; kk < B3_KB; ++kk) {
-                        const int k = k0 + kk;
-                        f32x4 y;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            // pp = 0: (R_0 + R_1) + R_2;  pp = 1: (R_1 - R_2) - R_3  (sg * x is exact)
-                            const float v = __builtin_fmaf(sg, xv[kk][2][e], __builtin_fmaf(sg, xv[kk][1][e], xv[kk][0][e])) + bias4[nw][e];
-                            y[e] = p.lrelu ? lrelu01(v) : v;
-                        }
-                        const int oyl = 2 * (mb * 4 + k) + pp;
-                        const bool ok = y0 + oyl < p.H && ox < p.W && ch < p.cout_store;
-#ifdef B3_ABL_NOSTORE      // timing build: every store out of range (dropped by the range check)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), ors, (int)(ok && p.H < 0 ? (unsigned)((oyl * p.W + ox) * p.out_stride + ch) * 4u : WOOB), 0, 0);
-#else
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), ors, (int)(ok ? (unsigned)((oyl * p.W + ox) * p.out_stride + ch) * 4u : WOOB), 0, 0);
-#endif
-                    }
+                    for (int kk = 0; kk < B3_KB; ++kk) B3_XROW(xv[kk][0], xv[kk][1], xv[kk][2], nw, mb * 4 + k0 + kk);
                 }
             }
             BSTAMP(14);
@@ -600,6 +632,10 @@ __global__ __launch_bounds__(256, 1) void conv_wino_b3_kernel(const ConvParamsW 
         B3_ZERO_ACC();
 #endif
         BSTAMP(15);
+#undef B3_XCOL
+#undef B3_XROW
+#undef B3_XVB
+#undef B3_XROWOK
         BSTAMP(3);
 #ifdef PIVLFN_STAMPS
         if (stamp_) sd_[6] += 1;

@@ -46,11 +46,15 @@ def main():
         t = buf.view(-1, 16).cpu().numpy().astype(float)
         t = t[t[:, 5] > 0]
         tiles, steps = t[:, 6].mean(), t[:, 7].mean()
-        print(f"{ci}->{co} at {n}x{n}: {len(t)} workgroups, {tiles:.1f} tiles and {steps:.1f} full steps each; ticks per workgroup (100 MHz clock: 1 tick = 10 ns), mean:")
+        print(f"{ci}->{co} at {n}x{n}: {len(t)} workgroups, {tiles:.1f} tiles and {steps:.1f} full steps each; ticks per workgroup (s_memtime: about 2 ticks per ns on MI355X -- a 940 us launch reads 2.08 M), mean:")
         print("   " + "  ".join(f"{NAMES[i]} {t[:, i].mean():.0f}" for i in (5, 0, 1, 2, 3, 4)))
-        print(f"   per tile: start {t[:, 0].mean() / tiles:.1f}  last step {t[:, 2].mean() / tiles:.1f}  epilogue {t[:, 3].mean() / tiles:.1f}  switch {t[:, 4].mean() / tiles:.1f}"
+        epi = t[:, [3, 13, 14, 15]].sum(axis=1).mean() / tiles
+        start, switch = t[:, 0].mean() / tiles, t[:, 4].mean() / tiles
+        print(f"   per tile: start {start:.1f}  last step {t[:, 2].mean() / tiles:.1f}  epilogue {epi:.1f}  switch {switch:.1f}  boundary (start + epilogue + switch) {start + epi + switch:.1f}"
               f"   per full step: {t[:, 1].mean() / max(steps, 1):.1f} = phases " + " ".join(f"{t[:, i].mean() / max(steps, 1):.1f}" for i in (8, 9, 10, 11)) + f" + barrier {t[:, 12].mean() / max(steps, 1):.1f}")
-        print(f"   epilogue per tile: write halves + barriers {t[:, 13].mean() / tiles:.1f}  reads + stores {t[:, 14].mean() / tiles:.1f}  zeroing {t[:, 15].mean() / tiles:.1f}  rest {t[:, 3].mean() / tiles:.1f}")
+        # slots 13-15 and 3 are disjoint parts of the epilogue (both tile-block halves summed)
+        print(f"   epilogue per tile: column halves + exchange writes + barriers {t[:, 13].mean() / tiles:.1f}  exchange reads + row halves + stores {t[:, 14].mean() / tiles:.1f}"
+              f"  zeroing (when not under the writes) {t[:, 15].mean() / tiles:.1f}  rest {t[:, 3].mean() / tiles:.1f}")
         lib.pivlfn_conv_destroy(h)
 
 
