@@ -5,7 +5,7 @@
 #                     stamps); only tools/*.py load it
 set -e
 cd "$(dirname "$0")"
-SRCS="conv_mfma conv_wino conv_wino_b3 conv_dist_b3 conv_f16 conv_split conv_head warp_corr corr_bwd ops stereo postpro validate preproc evaluate viz quality uncertainty vortex flowmap particles twopoint distribution spectrum pressure smooth calibrate ensemble pod net_weights conv_layer net api"
+SRCS="conv_mfma conv_k1 conv_c3k7 conv_s2 conv_wino conv_wino_b3 conv_dist_b3 conv_f16 conv_split conv_head warp_corr corr_bwd ops stereo postpro validate preproc evaluate viz quality uncertainty vortex flowmap particles twopoint distribution spectrum pressure smooth calibrate ensemble pod net_weights conv_layer net api"
 build_one() {   # $1 = object dir, $2 = output .so, $3 = extra flags, $4 = extra sources (research kernels of tools/kernels/)
   local OBJ="$1" OUT="$2" EXTRA="$4"
   mkdir -p "$OBJ"

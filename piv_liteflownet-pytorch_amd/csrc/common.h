@@ -38,13 +38,15 @@ int ensure_dyn_lds(LdsAttr &slot, const void *fn, int bytes);
         }                                                                                    \
     } while (0)
 
-#define PIV_REQUIRE(cond, ...)                                                               \
+// say: leave the refusal's message as the last error (false for a choice's speculative attempts, conv_mfma.hip)
+#define PIV_REQUIRE_IF(say, cond, ...)                                                       \
     do {                                                                                     \
         if (!(cond)) {                                                                       \
-            pivlfn::set_error(__VA_ARGS__);                                                  \
+            if (say) pivlfn::set_error(__VA_ARGS__);                                         \
             return PIVLFN_ERR_ARG;                                                           \
         }                                                                                    \
     } while (0)
+#define PIV_REQUIRE(cond, ...) PIV_REQUIRE_IF(true, cond, __VA_ARGS__)
 
 int device_cus();      // compute units of the current device (cached per device; 256 when the query fails)
 
@@ -86,7 +88,7 @@ __device__ __forceinline__ Taps make_taps(float fx, float fy, int H, int W)
     return t;
 }
 
-// ---- convolution (conv_mfma.hip) -------------------------------------------------------------------
+// ---- convolution (conv_mfma.hip, conv_k1.hip, conv_c3k7.hip, conv_s2.hip; conv_direct.h) -----------
 struct ConvSeg {
     const float *ptr;   // NHWC base, channel offset already applied
     int cload;          // channels staged from this source, multiple of 4 (zero-weight lanes allowed)
@@ -130,7 +132,7 @@ struct ConvPlan { int family, rows, chans, staging, ksplit; };
 int choose_conv(const ConvParams &p, ConvPlan &pl);
 int launch_conv(const ConvParams &p, hipStream_t st);
 // NetC.conv1 with the two 1 x 1 layers that read its output at level 1 -- NetC_ext (32 -> 64, both frames) and Regularization's
-// moduleFeat (32 -> 128, first frame) -- computed from the activated accumulators in the same kernel (conv_mfma.hip).
+// moduleFeat (32 -> 128, first frame) -- computed from the activated accumulators in the same kernel (conv_c3k7.hip).
 struct Conv1Fuse {
     const float *w11;   // [6 blocks: 2 of NetC_ext, 4 of moduleFeat][4 groups][64 lanes][4]: W[32 blk + (lane & 31)][8 g + 4 (lane >> 5) + e]
     const float *b11;   // [64 + 128]
@@ -156,12 +158,12 @@ struct ConvChoice {
     int (*run)(const P &, hipStream_t);
     ConvKernelPlan pl;
 };
-// L = one instantiation's launcher: L::plan holds its own bounds and its grid, L::run launches it
-template <class L, class P>
-static inline int conv_take(const P &p, ConvChoice<P> &ch)
+// L = one instantiation's launcher: L::plan holds its own bounds and its grid, L::run launches it (C: also conv_direct.h's ConvChoiceD)
+template <class L, class P, class C, class... A>
+static inline int conv_take(const P &p, C &ch, A... more)
 {
     ch.run = &L::run;
-    return L::plan(p, ch.pl);
+    return L::plan(p, ch.pl, more...);
 }
 
 // ---- fp16-multiplicand variant (conv_f16.hip): optional reduced-precision mode, K chunks of 16 channels ----------------

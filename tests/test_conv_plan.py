@@ -1,6 +1,8 @@
 """The direct convolution's launcher, asked on the host which kernel it picks (pivlfn_conv2d_nhwc_plan; no GPU needed).
 
-launch_conv picks one of about thirty compiled kernels per call, from the layer geometry and from the batch.  TILE_CASES holds one
+launch_conv picks one of about thirty compiled kernels per call, from the layer geometry and from the batch: choose_conv
+(csrc/conv_mfma.hip, with the dedicated kernels' choices in conv_c3k7.hip, conv_k1.hip and conv_s2.hip) names a kernel's launch function
+and its plan in one statement, so a plan reported here is the kernel launched.  TILE_CASES holds one
 layer and shape for every plan -- (family, rows, channels, staging class, split-K shares) -- a fixed grid of layers and shapes can
 reach; tests/test_gpu_conv_tiles.py runs each against float64.  Here, on the plan function alone:
   * every case still reaches the plan it was chosen for;
@@ -146,7 +148,9 @@ def sweep():
     return {(g, res, leaky): [plan(*g, B, res, leaky) for B in BATCHES] for g, res, leaky in _grid()}
 
 
-# every kernel launch_conv can launch: (family, rows, channels, staging class)
+# every kernel launch_conv can launch: (family, rows, channels, staging class).  The library's own list is the take_nt2 / take_nt4
+# mappings and choose_conv1 of csrc/conv_mfma.hip and the launchers of conv_k1.hip, conv_c3k7.hip and conv_s2.hip (COL7 / ROW7: conv_layer.hip); a kernel
+# added or retired there shows here as a plan the grid reaches outside this set, or no longer reaches
 COMPILED = ({(V2, 16, 64, 505)}
             | {(V2, 8, 32 * nt, 309) for nt in (1, 2, 3, 4)} | {(V2, 8, 32 * nt, c) for nt in (1, 2) for c in (505, 913)}
             | {(V2, 4, 32 * nt, c) for nt in (1, 2, 3, 4) for c in (309, 913)}

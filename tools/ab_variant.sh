@@ -1,7 +1,7 @@
 #!/bin/bash
 # Timing-only variants of one source file, each compiled with extra flags into its own copy of the tools library and run through a
 # tools script on the GPU box (from the repo root, after csrc/build.sh tools):
-#   bash tools/ab_variant.sh conv_mfma "python3 tools/bench_s2.py" "-DS2_ABL_CT=0" "-DS2_ABL_CT=1" ...
+#   bash tools/ab_variant.sh conv_s2 "python3 tools/bench_s2.py" "-DS2_ABL_CT=0" "-DS2_ABL_CT=1" ...
 set -e
 SRC=$1; CMD=$2; shift 2
 OBJ=build/obj_tools
